@@ -4,7 +4,12 @@ SCAE.loss + backward [+ gradient all-reduce] + RMSprop step) on synthetic
 MNIST-shaped batches, BASELINE.json's metric / configs[1]:
 MNIST 40x40, 24 part / 24 object capsules, bs=128 per GPU, fp32.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  The headline is W warm-up steps, then exactly K timed steps; ms_per_step is
+  their time over K (--blocks B repeats that region B times and reports the
+  median block).  --dump-outputs writes the last timed step's loss, updated
+  parameters and gradients as DIR/<name>.npy; the inputs (model init, batches,
+  noise) are seeded, so two builds can be compared array for array.
   N>1 works both ways: under `python -m torch.distributed.run --nproc-per-node N
   ... bench.py --gpus N` (RANK/WORLD_SIZE in the environment) and bare
   (`python bench.py --gpus N`): the bare parent starts N fresh rank processes
@@ -94,10 +99,15 @@ def parse():
     ap.add_argument("--watchdog-s", type=float, default=1500.0,
                     help="a rank process ends itself (exit code 3) when the run takes longer "
                          "than this; 0: no watchdog")
-    ap.add_argument("--blocks", type=int, default=21,
+    ap.add_argument("--blocks", type=int, default=1,
                     help="the K-step timed region is repeated this many times "
                          "back to back (each bracketed by barrier + "
-                         "synchronize); ms_per_step is the median block")
+                         "synchronize); ms_per_step is the median block.  "
+                         "Default 1: exactly K timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed step computed in "
+                         "its last step -- loss, updated parameters, gradients -- as "
+                         "DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the extra_workloads legs (other BASELINE "
                          "configs, bf16, materialising / alternatives steps)")
@@ -649,6 +659,44 @@ def timing_summary(block_s, steps):
             "p90_ms": round(ms[-1 - len(ms) // 10], 4)}
 
 
+DUMP_BYTES = 60 << 20   # data of --dump-outputs (npy headers on top): under 64 MB in all
+
+
+def step_outputs(step):
+    """What a caller of the timed step holds after its last call: the loss it
+    returned, the parameters the optimiser updated and the gradients of that
+    step (the flat gradient buffer the optimiser read), each flattened in
+    ``model.named_parameters()`` order, not the flat buffers' internal layout.
+    -> {name: float32 numpy array}."""
+    params = [p for _, p in step.model.named_parameters() if p.requires_grad]
+    grad_of = {id(p): g for p, g in zip(step.flat.params, step.flat.grad_views())}
+    with torch.no_grad():
+        out = {"loss": step.loss.reshape(1),
+               "parameters": torch.cat([p.reshape(-1) for p in params]),
+               "gradients": torch.cat([grad_of[id(p)].reshape(-1) for p in params])}
+        return {k: v.float().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every array as ``out_dir/<name>.npy``.  When they hold more than
+    DUMP_BYTES in all, each is cut to the same share of its elements, a fixed
+    seeded sample (same sizes: same positions, on every run and every build).
+    -> {name: [elements written, elements computed]}."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        n = a.size
+        if total > DUMP_BYTES:
+            keep = max(1, n * DUMP_BYTES // total)
+            idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = [int(a.size), int(n)]
+    return written
+
+
 def capsule_state(model, image):
     """Where training has taken the part capsules: presence and the scale of
     the pose's linear part for a batch (eval mode: no presence noise).  On
@@ -1078,6 +1126,9 @@ def main():
                           before_block=before_block, after_block=after_block,
                           refresh=(lambda: step.restore(snap))
                           if args.steps > LIVE_SPAN else None)
+    # what the last timed step computed, before any other leg moves the state
+    dumped = dump_outputs(args.dump_outputs, step_outputs(step)) \
+        if args.dump_outputs and rank == 0 else None
     timing = timing_summary(blocks, args.steps)
     timing["state"] = (
         f"parameters + optimiser state restored to the build's init before "
@@ -1201,6 +1252,8 @@ def main():
                              "step on structured images",
             },
         }
+        if dumped is not None:
+            result["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if no_opt is not None:
             result["step_without_optimizer"] = no_opt
         if comm is not None:
