@@ -753,6 +753,50 @@ int scae_rmsprop_sums_step_f32(float *param, float *grad, float *square_avg, flo
                                float momentum, float grad_scale, const struct scae_sum_job *jobs,
                                int n_jobs, void *stream);
 
+/* Adam / RAdam / RMSprop step on the flat parameter buffers, LookAhead optionally fused in
+ *     replaces the reference's other two optimiser choices (base_experiment.py:44-77) and its
+ *     LookAhead wrapper over any of the three:
+ *     kind 0 = torch.optim.Adam(lr, betas, eps, weight_decay) (coupled L2: g <- g + wd p):
+ *       m <- m + (1-b1)(g-m);  v <- b2 v + (1-b2) g^2;
+ *       p <- p - lr/(1-b1^t) m / (sqrt(v)/sqrt(1-b2^t) + eps)
+ *     kind 1 = RAdam of torch_scae/optimizers.py:36-102 (degenerated_to_sgd; decoupled decay
+ *       p <- p - wd lr p first): the same moments (m <- b1 m + (1-b1) g); with
+ *       N_sma = N_max - 2t b2^t/(1-b2^t), N_max = 2/(1-b2) - 1: N_sma >= 5:
+ *       p <- p - lr rect(t) sqrt(1-b2^t)/(1-b1^t) m/(sqrt(v) + eps), else p <- p - lr/(1-b1^t) m.
+ *     kind 2 = the RMSprop of scae_rmsprop_step_f32, bit for bit, with beta1 = momentum,
+ *       beta2 = alpha, exp_avg = its momentum buffer, exp_avg_sq = square_avg (the form that
+ *       carries a step count: for LookAhead).
+ *     look_ahead_k > 0: LookAhead(k, alpha) of optimizers.py:105-190 after the update on every
+ *       step t with t % k == 0: the first such step sets slow := p (p unchanged), every later
+ *       one slow <- slow + alpha (p - slow), p := slow.  `slow` is read and written on those
+ *       steps only (may be NULL with look_ahead_k == 0).
+ *     g <- grad_scale g first.  The learning rate is read from lr_dev (device memory: the
+ *     per-epoch ExponentialLR of :73-76 under replay).  step_state: SCAE_FLAT_OPT_STATE_INTS
+ *     device ints -- [0] the steps taken so far (t - 1 of this step), [1] the slow buffer has
+ *     been made, the rest arrival counters that must be 0 (zeroed once; every launch leaves
+ *     them so).  The step's scalars come from
+ *     [0] in fp64, and with `advance` set the launch's last workgroup writes [0] + 1 (and
+ *     [1] = 1 on a sync step): one launch per optimiser step may advance, the last one when a
+ *     step is issued as several launches over parameter ranges.  Betas are doubles: their
+ *     powers are taken in fp64 (by repeated squaring), as torch takes them.  All buffers n floats, at the same offset
+ *     within a 16-byte line. */
+#define SCAE_FLAT_OPT_STATE_INTS 2112
+int scae_flat_opt_step_f32(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
+                           float *slow, int64_t n, const float *lr_dev, int32_t *step_state,
+                           int kind, double beta1, double beta2, float eps, float weight_decay,
+                           float grad_scale, int look_ahead_k, float look_ahead_alpha,
+                           int advance, void *stream);
+
+/* The step's last column sums riding in the launch above, as scae_rmsprop_sums_step_f32 does
+ * for plain RMSprop: bit for bit scae_sum_rows_multi_f32 followed by
+ * scae_flat_opt_step_f32(..., advance = 1).  No weight decay in this form. */
+int scae_flat_opt_sums_step_f32(float *param, float *grad, float *exp_avg, float *exp_avg_sq,
+                                float *slow, int64_t n, const float *lr_dev,
+                                int32_t *step_state, int kind, double beta1, double beta2,
+                                float eps, float grad_scale, int look_ahead_k,
+                                float look_ahead_alpha, const struct scae_sum_job *jobs,
+                                int n_jobs, void *stream);
+
 /* The batch hand-over of a training step (base_experiment.py:109-112): n_image
  * floats and n_label int64 labels (device memory) into the step's resident
  * input buffers, in one launch. */

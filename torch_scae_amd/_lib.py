@@ -6,8 +6,8 @@ tensor is not on a HIP device, the ops raise.
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_int64,
-                    c_void_p)
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int,
+                    c_int64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SCAE_HIP_LIB: another build of the same library, for A/B measurements)
@@ -259,6 +259,10 @@ SIGNATURES = {
                               c_float, c_float, c_float, P],
     "scae_rmsprop_sums_step_f32": [P, P, P, P, c_int64, c_float, P, c_float, c_float,
                                    c_float, c_float, POINTER(SumJob), c_int, P],
+    "scae_flat_opt_step_f32": [P, P, P, P, P, c_int64, P, P, c_int, c_double, c_double, c_float,
+                               c_float, c_float, c_int, c_float, c_int, P],
+    "scae_flat_opt_sums_step_f32": [P, P, P, P, P, c_int64, P, P, c_int, c_double, c_double,
+                                    c_float, c_float, c_int, c_float, POINTER(SumJob), c_int, P],
     "scae_capsule_head_fwd_f32": [P, P, c_float, c_int, P, P, P, P, P] + [c_int] * 4 + [P],
     "scae_capsule_head_conv_supported": [c_int] * 4,
     "scae_capsule_head_conv_preferred": [c_int] * 5,
@@ -314,6 +318,7 @@ _RESTYPES = {"scae_error_string": c_char_p,
              "scae_conv3x3_wf_floats": c_int64,
              "scae_launch_list_begin": P,
              "scae_launch_list_free": None}
+FLAT_OPT_STATE_INTS = 2112   # SCAE_FLAT_OPT_STATE_INTS: the step_state of scae_flat_opt_*
 ABI_VERSION = 2     # SCAE_ABI_VERSION of the include/scae_hip.h this binding mirrors
 
 _lib = None

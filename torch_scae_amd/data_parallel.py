@@ -11,6 +11,7 @@ reduction is a single large message -- the right shape for xGMI's per-link
 bound rings.
 """
 import ctypes
+import math
 
 import torch
 import torch.distributed as dist
@@ -215,8 +216,11 @@ class RMSpropFlat:
     so that ``decay_lr`` (the per-epoch ExponentialLR of :73-76) takes effect
     inside an already captured HIP graph."""
 
+    kind = 2      # scae_flat_opt_step_f32's kind (with LookAhead)
+
     def __init__(self, flat: FlatParameters, lr=3e-5, alpha=0.99, eps=1e-8,
-                 momentum=0.9, weight_decay=0.0):
+                 momentum=0.9, weight_decay=0.0, look_ahead=False,
+                 look_ahead_k=5, look_ahead_alpha=0.5):
         self.flat = flat
         self.lr, self.alpha, self.eps, self.momentum = lr, alpha, eps, momentum
         self.weight_decay = weight_decay
@@ -224,6 +228,7 @@ class RMSpropFlat:
         self.buf = torch.zeros_like(flat.flat_param)
         self.lr_dev = torch.full((1,), lr, device=flat.flat_param.device,
                                  dtype=flat.flat_param.dtype)
+        _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
 
     def set_lr(self, lr):
         self.lr = float(lr)
@@ -241,6 +246,11 @@ class RMSpropFlat:
         been launched yet: they ride in this step's launch
         (``scae_rmsprop_sums_step_f32``: the sum workgroups update the elements
         they produce), bit for bit the two launches' result."""
+        if self.look_ahead_k:     # (the fused form that counts steps)
+            _fused_step(self, self.buf, self.square_avg,
+                        (self.momentum, self.alpha), grad_scale, sum_units,
+                        self._cpu_update)
+            return
         g = self.flat.flat_grad
         if sum_units:
             from . import ops
@@ -295,3 +305,339 @@ class RMSpropFlat:
             for cur, old in zip((self.flat.flat_param, self.square_avg,
                                  self.buf), saved):
                 cur.copy_(torch.where(keep, cur, old))
+
+    def _cpu_update(self, g, t):
+        """The CPU form of the update (torch.optim.RMSprop's arithmetic) on
+        whole buffers; ``g`` already scaled."""
+        if self.weight_decay != 0:
+            g = g.add(self.flat.flat_param, alpha=self.weight_decay)
+        self.square_avg.mul_(self.alpha).addcmul_(g, g, value=1 - self.alpha)
+        avg = self.square_avg.sqrt().add_(self.eps)
+        if self.momentum > 0:
+            self.buf.mul_(self.momentum).addcdiv_(g, avg)
+            self.flat.flat_param.add_(self.buf, alpha=-self.lr)
+        else:
+            self.flat.flat_param.addcdiv_(g, avg, value=-self.lr)
+
+    @property
+    def counts_steps(self):
+        """The device step count is kept (only LookAhead needs one here)."""
+        return bool(self.look_ahead_k)
+
+    def state_buffers(self):
+        """(torch.optim.RMSprop's state key, flat buffer) pairs."""
+        return [("square_avg", self.square_avg), ("momentum_buffer", self.buf)]
+
+    def hyper_parameters(self):
+        return dict(lr=self.lr, momentum=self.momentum, alpha=self.alpha,
+                    eps=self.eps, weight_decay=self.weight_decay,
+                    centered=False)
+
+
+def _init_look_ahead(opt, look_ahead, k, alpha):
+    """The state every flat optimiser shares beside its moments: the step count
+    in device memory and LookAhead's slow buffer (torch_scae/optimizers.py:105-190)."""
+    flat = opt.flat
+    if look_ahead and (int(k) < 1 or not 0.0 <= float(alpha) <= 1.0):
+        raise ValueError(f"LookAhead needs k >= 1 and 0 <= alpha <= 1, got "
+                         f"k={k}, alpha={alpha}")
+    opt.look_ahead_k = int(k) if look_ahead else 0
+    opt.look_ahead_alpha = float(alpha)
+    # [0] steps taken, [1] the slow buffer has been made (LookAhead's first
+    # sync), the rest the kernel's arrival counters (0 between launches).  Read
+    # by the kernel at every step, so a captured graph follows it; the host
+    # reads it back only for state_dict()
+    from ._lib import FLAT_OPT_STATE_INTS
+    opt.step_state = torch.zeros(FLAT_OPT_STATE_INTS, dtype=torch.int32,
+                                 device=flat.flat_param.device)
+    opt.slow = torch.zeros_like(flat.flat_param) if opt.look_ahead_k else None
+
+
+def _split_sums(opt, g, sum_units):
+    """The column-sum units that may ride in the optimiser's launch (the rest
+    launched now); None when none ride."""
+    if not sum_units:
+        return None
+    from . import ops
+    if not g.is_cuda or opt.weight_decay != 0:
+        ops._launch_sum_units(sum_units)      # (the plain forms)
+        return None
+    if len(sum_units) > 16:
+        ops._launch_sum_units(sum_units[:-16])
+        return sum_units[-16:]
+    return sum_units
+
+
+@torch.no_grad()
+def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update):
+    """One step of ``opt`` through scae_flat_opt_step_f32 / scae_flat_opt_sums_step_f32
+    (HIP device) or ``cpu_update(g, t)`` + LookAhead in whole-buffer torch ops (CPU
+    tensors: the host-logic tests).  Parameters without a gradient are left alone,
+    like torch.optim does; without weight decay a zero gradient already is a no-op
+    (zero moments stay zero, LookAhead's slow copy of such a parameter equals it)."""
+    flat = opt.flat
+    g = flat.flat_grad
+    sum_units = _split_sums(opt, g, sum_units)
+    ranges = flat.active_ranges() if opt.weight_decay != 0 else \
+        [(0, g.numel())]
+    if g.is_cuda:
+        from . import _lib
+        P = ctypes.c_void_p
+        st = P(torch.cuda.current_stream(g.device).cuda_stream)
+        slow = opt.slow if opt.slow is not None else flat.flat_param
+        common = (P(opt.lr_dev.data_ptr()), P(opt.step_state.data_ptr()),
+                  opt.kind, float(betas[0]), float(betas[1]), float(opt.eps))
+        if sum_units:
+            from . import ops
+            arr = ops._sum_job_array(sum_units)
+            _lib.call("scae_flat_opt_sums_step_f32", P(flat.flat_param.data_ptr()),
+                      P(g.data_ptr()), P(m.data_ptr()), P(v.data_ptr()),
+                      P(slow.data_ptr()), g.numel(), *common, float(grad_scale),
+                      opt.look_ahead_k, opt.look_ahead_alpha, arr, len(sum_units), st)
+            return
+        for i, (off, n) in enumerate(ranges):
+            ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
+            # (one launch per step advances the count: the last, so that every
+            # range reads the same t)
+            _lib.call("scae_flat_opt_step_f32", ptr(flat.flat_param), ptr(g), ptr(m),
+                      ptr(v), ptr(slow), n, *common, float(opt.weight_decay),
+                      float(grad_scale), opt.look_ahead_k, opt.look_ahead_alpha,
+                      int(i == len(ranges) - 1), st)
+        return
+    if not ranges:
+        return
+    if grad_scale != 1.0:
+        g = g * grad_scale
+    bufs = [flat.flat_param, m, v] + ([opt.slow] if opt.slow is not None else [])
+    if opt.weight_decay != 0:
+        keep = torch.zeros_like(g, dtype=torch.bool)
+        for off, n in ranges:
+            keep[off:off + n] = True
+        saved = [b.clone() for b in bufs]
+    t = int(opt.step_state[0]) + 1
+    cpu_update(g, t)
+    k = opt.look_ahead_k
+    if k and t % k == 0:        # optimizers.py:118-128, 136-142
+        p = flat.flat_param
+        if int(opt.step_state[1]):
+            opt.slow.add_(p - opt.slow, alpha=opt.look_ahead_alpha)
+            p.copy_(opt.slow)
+        else:
+            opt.slow.copy_(p)
+        opt.step_state[1] = 1
+    if opt.weight_decay != 0:
+        for cur, old in zip(bufs, saved):
+            cur.copy_(torch.where(keep, cur, old))
+    opt.step_state[0] = t
+
+
+class _FlatAdamBase:
+    """What AdamFlat and RAdamFlat share: the surface of RMSpropFlat
+    (``step(grad_scale, sum_units)``, ``set_lr``, ``decay_lr``, ``lr``,
+    ``lr_dev``), two moment buffers, the step count in device memory and
+    optionally LookAhead(k, alpha) fused into the same pass."""
+
+    kind = None
+    counts_steps = True
+
+    def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999),
+                 eps=1e-8, weight_decay=0.0, look_ahead=False, look_ahead_k=5,
+                 look_ahead_alpha=0.5):
+        b1, b2 = (float(b) for b in betas)
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas must lie in [0, 1), got {betas}")
+        self.flat = flat
+        self.lr, self.betas, self.eps = float(lr), (b1, b2), float(eps)
+        self.weight_decay = float(weight_decay)
+        self.exp_avg = torch.zeros_like(flat.flat_param)
+        self.exp_avg_sq = torch.zeros_like(flat.flat_param)
+        self.lr_dev = torch.full((1,), self.lr, device=flat.flat_param.device,
+                                 dtype=flat.flat_param.dtype)
+        _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
+
+    def set_lr(self, lr):
+        self.lr = float(lr)
+        self.lr_dev.fill_(self.lr)
+
+    def decay_lr(self, gamma):
+        """One ExponentialLR step (call once per epoch, gamma = decay_rate)."""
+        self.set_lr(self.lr * gamma)
+
+    def step(self, grad_scale=1.0, sum_units=None):
+        """As ``RMSpropFlat.step``: ``grad_scale`` multiplies the gradient on
+        the fly, ``sum_units`` ride in the launch (scae_flat_opt_sums_step_f32)."""
+        _fused_step(self, self.exp_avg, self.exp_avg_sq, self.betas, grad_scale,
+                    sum_units, self._cpu_update)
+
+    def state_buffers(self):
+        """(torch.optim's state key, flat buffer) pairs."""
+        return [("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)]
+
+    def hyper_parameters(self):
+        return dict(lr=self.lr, betas=self.betas, eps=self.eps,
+                    weight_decay=self.weight_decay)
+
+
+class AdamFlat(_FlatAdamBase):
+    """torch.optim.Adam(lr, betas, eps, weight_decay) -- the reference's
+    ``optimizer.type: Adam`` (base_experiment.py:56-60) -- as ONE fused pass
+    over the flat buffers (scae_flat_opt_step_f32, kind 0): coupled L2 weight
+    decay, eps added after the bias correction of sqrt(v)."""
+
+    kind = 0
+
+    def _cpu_update(self, g, t):
+        b1, b2 = self.betas
+        if self.weight_decay != 0:
+            g = g.add(self.flat.flat_param, alpha=self.weight_decay)
+        self.exp_avg.lerp_(g, 1 - b1)
+        self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)
+        denom = (self.exp_avg_sq.sqrt() / math.sqrt(1 - b2 ** t)).add_(self.eps)
+        self.flat.flat_param.addcdiv_(self.exp_avg, denom,
+                                      value=-self.lr / (1 - b1 ** t))
+
+
+class RAdamFlat(_FlatAdamBase):
+    """The reference's RAdam (torch_scae/optimizers.py:36-102,
+    ``degenerated_to_sgd=True``; ``optimizer.type: RAdam``) as ONE fused pass
+    over the flat buffers (scae_flat_opt_step_f32, kind 1): decoupled weight
+    decay (p -= wd lr p), eps added to the raw sqrt(v), and the variance
+    rectification from the step N_sma = N_max - 2t b2^t / (1 - b2^t) reaches 5
+    on (t = 6 at b2 = 0.999); before that, SGD with momentum.
+    torch.optim.RAdam(decoupled_weight_decay=True) has the same arithmetic."""
+
+    kind = 1
+
+    def _cpu_update(self, g, t):
+        b1, b2 = self.betas
+        m, v, p = self.exp_avg, self.exp_avg_sq, self.flat.flat_param
+        v.mul_(b2).addcmul_(g, g, value=1 - b2)
+        m.mul_(b1).add_(g, alpha=1 - b1)
+        b2t = b2 ** t
+        n_max = 2 / (1 - b2) - 1
+        n_sma = n_max - 2 * t * b2t / (1 - b2t)
+        if self.weight_decay != 0:
+            p.add_(p, alpha=-self.weight_decay * self.lr)
+        if n_sma >= 5:
+            size = math.sqrt((1 - b2t) * (n_sma - 4) / (n_max - 4) * (n_sma - 2)
+                             / n_sma * n_max / (n_max - 2)) / (1 - b1 ** t)
+            p.addcdiv_(m, v.sqrt().add_(self.eps), value=-size * self.lr)
+        else:
+            p.add_(m, alpha=-self.lr / (1 - b1 ** t))
+
+
+def make_optimizer(kind, flat, lr, eps, betas=(0.9, 0.999), momentum=0.9,
+                   weight_decay=0.0, look_ahead=False, look_ahead_k=5,
+                   look_ahead_alpha=0.5):
+    """``kind``: "rmsprop" | "adam" | "radam" (any case) -> the flat optimiser."""
+    name = str(kind).lower()
+    la = dict(look_ahead=look_ahead, look_ahead_k=look_ahead_k,
+              look_ahead_alpha=look_ahead_alpha)
+    if name == "rmsprop":
+        return RMSpropFlat(flat, lr=lr, momentum=momentum, eps=eps,
+                           weight_decay=weight_decay, **la)
+    if name in ("adam", "radam"):
+        cls = AdamFlat if name == "adam" else RAdamFlat
+        return cls(flat, lr=lr, betas=betas, eps=eps,
+                   weight_decay=weight_decay, **la)
+    raise ValueError(f"unknown optimizer {kind!r}: expected 'rmsprop', 'adam' "
+                     "or 'radam'")
+
+
+def optimizer_state_dict(opt, params, steps=None):
+    """``opt``'s state in ``torch.optim``'s schema: ``state`` keyed by the
+    parameter's index in ``params`` (``model.parameters()``), with ``step`` and
+    the optimiser's own buffers (``exp_avg`` / ``exp_avg_sq``; ``square_avg`` /
+    ``momentum_buffer``), one ``param_groups`` entry.  Loads into the matching
+    stock optimiser built on ``params``.  ``steps``: the step count when ``opt``
+    keeps none (RMSprop without LookAhead).  With LookAhead, ``slow_state``
+    {index: {'slow_buffer': tensor}} once the slow weights exist, and the
+    group carries ``lookahead_k`` / ``lookahead_alpha`` / ``lookahead_step``
+    (the reference's LookAhead.state_dict keys its slow state by Python id()
+    instead, optimizers.py:169-182, which no other process can map back)."""
+    flat = opt.flat
+    where = {id(p): off for p, off in zip(flat.params, flat.offsets)}
+    t = int(opt.step_state[0]) if opt.counts_steps or steps is None \
+        else int(steps)
+    made = opt.slow is not None and bool(int(opt.step_state[1]))
+    bufs = [(k, b) for k, b in opt.state_buffers()
+            if not (k == "momentum_buffer" and opt.momentum <= 0)]
+    state, slow_state = {}, {}
+    for i, p in enumerate(params):
+        off = where.get(id(p))
+        if off is None:
+            continue
+        sl = slice(off, off + p.numel())
+        state[i] = dict(step=torch.tensor(float(t)),
+                        **{k: b[sl].view(p.shape).detach().cpu().clone()
+                           for k, b in bufs})
+        if made:
+            slow_state[i] = dict(
+                slow_buffer=opt.slow[sl].view(p.shape).detach().cpu().clone())
+    group = dict(opt.hyper_parameters(), params=list(range(len(params))))
+    out = dict(state=state, param_groups=[group])
+    if opt.look_ahead_k:
+        group.update(lookahead_k=opt.look_ahead_k,
+                     lookahead_alpha=opt.look_ahead_alpha, lookahead_step=t)
+        out["slow_state"] = slow_state
+    return out
+
+
+@torch.no_grad()
+def load_optimizer_state_dict(opt, params, sd):
+    """The inverse of ``optimizer_state_dict``: ``sd`` in ``torch.optim``'s
+    schema (e.g. a stock optimiser's ``state_dict()`` over ``params``).  The
+    learning rate is taken over; the other hyper-parameters must equal
+    ``opt``'s (a captured step holds them).  A parameter without state starts
+    from zero moments; LookAhead's slow weights come from ``slow_state`` (when
+    it is missing or empty the next sync creates them, as the reference
+    does).  Returns the step count."""
+    groups = sd["param_groups"]
+    if len(groups) != 1:
+        raise ValueError("one parameter group expected, got %d" % len(groups))
+    group = groups[0]
+    mine = opt.hyper_parameters()
+    for key, val in mine.items():
+        if key == "lr" or key not in group:
+            continue
+        a = val if isinstance(val, tuple) else (val,)
+        b = tuple(group[key]) if isinstance(group[key], (tuple, list)) \
+            else (group[key],)
+        if len(a) != len(b) or not all(
+                math.isclose(float(x), float(y), rel_tol=1e-6, abs_tol=0.0)
+                for x, y in zip(a, b)):
+            raise ValueError(f"{key}={group[key]!r} in the state dict, the "
+                             f"optimiser has {val!r}")
+    flat = opt.flat
+    where = {id(p): off for p, off in zip(flat.params, flat.offsets)}
+    bufs = [(k, b) for k, b in opt.state_buffers()
+            if not (k == "momentum_buffer" and opt.momentum <= 0)]
+    state = sd["state"]
+    slow_state = sd.get("slow_state") or {}
+    steps = set()
+    for i, p in enumerate(params):
+        off = where.get(id(p))
+        if off is None:
+            continue
+        sl = slice(off, off + p.numel())
+        st = state.get(i, state.get(str(i)))
+        for k, b in bufs:
+            if st is None:
+                b[sl].zero_()
+            else:
+                b[sl].copy_(st[k].reshape(-1))
+        if st is not None:
+            steps.add(int(float(st["step"])))
+        if opt.slow is not None:
+            ss = slow_state.get(i, slow_state.get(str(i)))
+            # (a parameter without slow weights: the reference would create
+            # them from the fast ones at its first sync with a gradient)
+            opt.slow[sl].copy_(ss["slow_buffer"].reshape(-1) if ss is not None
+                               else p.detach().reshape(-1))
+    if len(steps) > 1:
+        raise ValueError(f"one step count for all parameters, got {sorted(steps)}")
+    t = steps.pop() if steps else 0
+    opt.set_lr(group["lr"])
+    opt.step_state[:2].copy_(torch.tensor([t, int(bool(slow_state))],
+                                          dtype=torch.int32))
+    return t

@@ -150,3 +150,40 @@ def make_scae(model_params: dict):
                 part_decoder=TemplateBasedImageDecoder(**cfg.pcae_decoder),
                 obj_encoder=SetTransformer(**cfg.ocae_encoder_set_transformer),
                 obj_decoder=obj_decoder, **cfg.scae)
+
+
+_OPTIMIZERS = {"RMSprop": "rmsprop", "Adam": "adam", "RAdam": "radam"}
+
+
+def make_train_step(model, cfg: dict, **kw):
+    """The reference's hydra config (configs/config.yaml with one of
+    configs/optimizer/{rmsprop,adam,radam}.yaml), as a plain dict, -> the
+    matching ``train_step.TrainStep`` for ``model``
+    (base_experiment.py:44-77): ``optimizer.{type, learning_rate,
+    weight_decay, momentum}``, ``meta_optimizer.{look_ahead, look_ahead_k,
+    look_ahead_alpha}``, ``lr_scheduler.{active, decay_rate}`` (the
+    per-epoch ExponentialLR: ``TrainStep.end_epoch``),
+    ``data_loader.batch_size`` (eps = 1e-2 / batch_size**2) and
+    ``model.image_shape``.  The reference reads LookAhead's k and alpha from
+    ``cfg.optimizer``, where none of its yaml files defines them
+    (base_experiment.py:67-70); they are read from ``meta_optimizer`` here,
+    where config.yaml puts them.  ``kw``: further TrainStep arguments."""
+    from .train_step import TrainStep
+    opt = cfg["optimizer"]
+    kind = _OPTIMIZERS.get(opt["type"])
+    if kind is None:
+        raise ValueError(f"Unknown optimizer type {opt['type']!r}.")
+    meta = cfg.get("meta_optimizer") or {}
+    sched = cfg.get("lr_scheduler") or {}
+    shape = kw.pop("image_shape", None) or tuple(cfg["model"]["image_shape"])
+    args = dict(lr=float(opt["learning_rate"]), optimizer=kind,
+                weight_decay=float(opt.get("weight_decay", 0.0)),
+                lr_decay_rate=float(sched["decay_rate"])
+                if sched.get("active", False) else None,
+                look_ahead=bool(meta.get("look_ahead", False)),
+                look_ahead_k=int(meta.get("look_ahead_k", 5)),
+                look_ahead_alpha=float(meta.get("look_ahead_alpha", 0.5)))
+    if kind == "rmsprop":
+        args["momentum"] = float(opt["momentum"])
+    args.update(kw)
+    return TrainStep(model, int(cfg["data_loader"]["batch_size"]), shape, **args)

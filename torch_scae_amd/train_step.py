@@ -12,8 +12,9 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .data_parallel import (FlatParameters, RMSpropFlat, all_reduce_gradients,
-                            broadcast_parameters, world)
+from .data_parallel import (FlatParameters, all_reduce_gradients,
+                            broadcast_parameters, load_optimizer_state_dict,
+                            make_optimizer, optimizer_state_dict, world)
 
 
 # parameters whose gradients are final once backward has come down through
@@ -75,6 +76,13 @@ class TrainStep:
     collective even with ranks: measurements only -- the ranks' parameters
     drift apart) or None (two buckets where possible).  ``bench.py`` measures
     all three on the ranks it is given and takes the fastest.
+
+    ``optimizer``: the reference's choice (base_experiment.py:44-77) --
+    ``"rmsprop"`` (RMSpropFlat, also ``True``), ``"adam"`` (AdamFlat),
+    ``"radam"`` (RAdamFlat), or ``False`` / ``None`` for none; each optionally
+    wrapped in LookAhead(``look_ahead_k``, ``look_ahead_alpha``) (optimizers.py:105-190),
+    fused into the same pass.  eps = 1e-2 / batch_size**2 for all three
+    (:46).  Every optimiser runs in every replay and collective mode.
     """
 
     MODES = ("2 buckets", "1 bucket", "in graph")
@@ -84,7 +92,8 @@ class TrainStep:
                  lr_decay_rate=0.997, autocast_dtype=None,
                  force_collective=False, overlap=True, lazy_render=True,
                  prologue=True, fuse_kernels=True, collective_mode=None,
-                 replay="graph", two_lanes=False):
+                 replay="graph", two_lanes=False, betas=(0.9, 0.999),
+                 look_ahead=False, look_ahead_k=5, look_ahead_alpha=0.5):
         self.model = model
         self.device = next(model.parameters()).device
         self.world = world()[1]
@@ -135,11 +144,16 @@ class TrainStep:
             "2 buckets, the first overlapping the encoder backward" \
             if self.split else "1 bucket after the backward"
         broadcast_parameters(self.flat)
-        # eps = 1e-2 / bs**2 as in configs/optimizer/rmsprop.yaml
-        self.opt = RMSpropFlat(self.flat, lr=lr, momentum=momentum,
-                               eps=1e-2 / float(batch_size) ** 2,
-                               weight_decay=weight_decay) \
-            if optimizer else None
+        # eps = 1e-2 / bs**2 for every optimiser (base_experiment.py:46)
+        if optimizer is True:
+            optimizer = "rmsprop"
+        self.opt = make_optimizer(
+            optimizer, self.flat, lr=lr, eps=1e-2 / float(batch_size) ** 2,
+            betas=betas, momentum=momentum, weight_decay=weight_decay,
+            look_ahead=look_ahead, look_ahead_k=look_ahead_k,
+            look_ahead_alpha=look_ahead_alpha) \
+            if optimizer not in (None, False) else None
+        self.steps = 0           # steps taken (host count; the optimisers keep their own)
         self.lr_decay_rate = lr_decay_rate
         # the backward's last column sums (parameter gradients only) ride in the optimiser's
         # launch: one launch less on the step's dependent chain.  Not with a collective (the
@@ -450,26 +464,56 @@ class TrainStep:
 
     def snapshot(self):
         """The training state this step advances -- parameters, the
-        optimiser's two moment buffers and its learning rate -- as clones (a
-        few device copies; not for use inside a timed region).  ``restore``
+        optimiser's two moment buffers, its step count, LookAhead's slow weights
+        and its learning rate -- as clones (a few device copies; not for use
+        inside a timed region).  ``restore``
         puts it back, under an already captured graph too: the graph reads
         and writes the same flat buffers, and everything derived from the
         parameters (folding products, filter re-layouts) is recomputed by
         every step's own prologue / graph."""
-        snap = {"param": self.flat.flat_param.clone()}
+        snap = {"param": self.flat.flat_param.clone(), "steps": self.steps}
         if self.opt is not None:
-            snap.update(square_avg=self.opt.square_avg.clone(),
-                        buf=self.opt.buf.clone(), lr=self.opt.lr)
+            snap.update({k: b.clone() for k, b in self.opt.state_buffers()},
+                        lr=self.opt.lr)
+            if self.opt.counts_steps:
+                snap["step_state"] = self.opt.step_state.clone()
+            if self.opt.slow is not None:
+                snap["slow"] = self.opt.slow.clone()
         return snap
 
     @torch.no_grad()
     def restore(self, snap):
         self.flat.flat_param.copy_(snap["param"])
+        self.steps = snap.get("steps", self.steps)
         if self.opt is not None:
-            self.opt.square_avg.copy_(snap["square_avg"])
-            self.opt.buf.copy_(snap["buf"])
+            for k, b in self.opt.state_buffers():
+                b.copy_(snap[k])
+            if "step_state" in snap:
+                self.opt.step_state.copy_(snap["step_state"])
+            if "slow" in snap:
+                self.opt.slow.copy_(snap["slow"])
             if self.opt.lr != snap["lr"]:
                 self.opt.set_lr(snap["lr"])
+
+    def optimizer_state_dict(self):
+        """The optimiser's state in ``torch.optim``'s schema (state keyed by the
+        parameter's index in ``model.parameters()``): loads into the matching
+        stock optimiser over the model's parameters
+        (data_parallel.optimizer_state_dict; with LookAhead a ``slow_state``
+        keyed the same way)."""
+        if self.opt is None:
+            raise ValueError("this step has no optimiser")
+        return optimizer_state_dict(self.opt, list(self.model.parameters()),
+                                    steps=self.steps)
+
+    def load_optimizer_state_dict(self, sd):
+        """Load a ``torch.optim``-schema state (``optimizer_state_dict``, or a
+        stock optimiser's over ``model.parameters()``); a captured graph
+        replays from it."""
+        if self.opt is None:
+            raise ValueError("this step has no optimiser")
+        self.steps = load_optimizer_state_dict(
+            self.opt, list(self.model.parameters()), sd)
 
     def _refresh_prologue(self):
         """Noise + folding products for the next forward (no batch)."""
@@ -516,6 +560,7 @@ class TrainStep:
     def __call__(self, image, label):
         """image / label may be device tensors; copied into the static inputs."""
         self._stage(image, label)
+        self.steps += 1
         if self.use_graph:
             self.capture()
             if self.split:
