@@ -1109,6 +1109,40 @@ int scae_loss_tail_bwd_f32(const float *lpp, const float *posterior,
                            const float *weights5, float within_const, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Evaluation epilogue (csrc/eval_tail.hip): the last launch of an evaluation batch.
+ *   replaces SCAE.calculate_accuracy (stacked_capsule_auto_encoder.py:289-297) and the
+ *   per-batch outputs plus epoch means of BaseExperiment.validation_step /
+ *   validation_epoch_end / test_step / test_epoch_end (base_experiment.py:128-202)
+ * ------------------------------------------------------------------------ */
+/* The fp64 accumulator (zero it to start an epoch):
+ *   [0] batches  [1] sum loss  [2] sum accuracy (max of the heads)  [3] sum prior accuracy
+ *   [4] sum posterior accuracy  [5 + i] sum of out12[i], i < 12 (scae_loss_tail_fwd_f32's
+ *   12-vector; zero when out12 is not given).  ONE thread adds a batch, in stream order:
+ * the sums are reproducible bit for bit.  batch3 (nullable) receives the batch's {accuracy,
+ * prior accuracy, posterior accuracy}.  Accuracy of a head: argmax over its class
+ * probabilities (torch.argmax: first maximal index, NaN maximal) == label, count / B in fp32;
+ * zero without a label. */
+#define SCAE_EVAL_ACC_DOUBLES 17
+/* The loss tail's batch combine -- the same bits as scae_loss_tail_combine_f32 for the same
+ * arguments (extras->defer_combine ignored) -- plus the accuracies from prior_prob / post_prob
+ * (B, ncls), which scae_loss_tail_fwd_class_probs_f32 wrote in the same batch, plus the
+ * accumulation.  One workgroup.  Follows a forward launched with defer_combine. */
+int scae_eval_tail_f32(const float *lpp, const float *posterior, const float *caps_presence,
+                       const float *cls_w, const float *cls_b, const int64_t *label,
+                       const scae_loss_extras *extras, float *out12, float *workspace, int B,
+                       int O, int M, int ncls, int n_classes_cfg, int prior_type,
+                       int post_type, int sparsity_on, const float *weights5,
+                       float within_const, const float *prior_prob, const float *post_prob,
+                       double *acc, float *batch3, void *stream);
+/* Accuracies + accumulation only, for a loss other launches computed (a model outside the
+ * fused tail: recon_mse_weight > 0, part_caps_sparsity_weight > 0, more than 32 classes):
+ * loss (1), out12 (12, nullable), prior_prob / post_prob (B, ncls) and label (nullable
+ * together: n_classes=None; any ncls > 0). */
+int scae_eval_accumulate_f32(const float *loss, const float *out12, const float *prior_prob,
+                             const float *post_prob, const int64_t *label, int B, int ncls,
+                             double *acc, float *batch3, void *stream);
+
+/* ------------------------------------------------------------------------
  * K1  template render + Gaussian-mixture image likelihood
  *     replaces part_decoder.py:174-237 (affine_grid + 2x grid_sample +
  *     background + presence), distributions.py:34-47 (mixture log_prob) and

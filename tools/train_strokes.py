@@ -9,6 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 from torch_scae_amd.data import stroke_batches
+from torch_scae_amd.eval_step import EvalStep
 from torch_scae_amd.train_step import TrainStep
 
 out, steps = sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 20000
@@ -22,21 +23,17 @@ train = stroke_batches(256, B, shape, seed=1, device=dev, glyph_seed=7)
 held = stroke_batches(16, B, shape, seed=2, device=dev, glyph_seed=7)   # same glyphs, fresh warps
 
 
+# held-out batches through the replayed evaluation step: its epoch means, one read per call
+ev = EvalStep(model, B, shape)
+
+
 def evaluate():
-    model.eval()
-    accs, losses = [], []
-    with torch.no_grad():
-        for i in range(held[0].shape[0]):
-            res = model(held[0][i])
-            loss, _ = model.loss(res, held[0][i], held[1][i])
-            losses.append(float(loss))
-            prior = (res.prior_cls_prob.argmax(-1) == held[1][i]).float().mean()
-            post = (res.posterior_cls_prob.argmax(-1) == held[1][i]).float().mean()
-            accs.append((float(prior), float(post)))
-    model.train()
-    return dict(loss=sum(losses) / len(losses),
-                prior_acc=sum(a for a, _ in accs) / len(accs),
-                posterior_acc=sum(b for _, b in accs) / len(accs))
+    for i in range(held[0].shape[0]):
+        ev(held[0][i], held[1][i])
+    m = ev.epoch_means()
+    ev.reset()
+    return dict(loss=float(m["loss"]), prior_acc=float(m["prior_accuracy"]),
+                posterior_acc=float(m["posterior_accuracy"]))
 
 
 log = [dict(step=0, **evaluate(), capsules=bench.capsule_state(model, held[0][0]))]

@@ -300,6 +300,9 @@ SIGNATURES = {
     + [POINTER(ScaledSum), c_int, P],
     "scae_loss_tail_bwd_f32": [P] * 6 + [POINTER(LossExtras)] + [P] * 7
     + [c_int] * 8 + [POINTER(c_float), c_float, P],
+    "scae_eval_tail_f32": [P] * 6 + [POINTER(LossExtras), P, P] + [c_int] * 8
+    + [POINTER(c_float), c_float] + [P] * 5,
+    "scae_eval_accumulate_f32": [P] * 5 + [c_int] * 2 + [P] * 3,
     "scae_template_render_fwd_f32": [POINTER(DecoderDesc), P, P, P],
     "scae_render_gmm_logprob_fwd_f32": [POINTER(DecoderDesc), P, P, P, P, P],
     "scae_render_gmm_bwd_f32": [POINTER(DecoderDesc)] + [P] * 12 + [P],
@@ -318,6 +321,7 @@ _RESTYPES = {"scae_error_string": c_char_p,
              "scae_conv3x3_wf_floats": c_int64,
              "scae_launch_list_begin": P,
              "scae_launch_list_free": None}
+EVAL_ACC_DOUBLES = 17        # SCAE_EVAL_ACC_DOUBLES: the accumulator of scae_eval_*
 FLAT_OPT_STATE_INTS = 2112   # SCAE_FLAT_OPT_STATE_INTS: the step_state of scae_flat_opt_*
 ABI_VERSION = 2     # SCAE_ABI_VERSION of the include/scae_hip.h this binding mirrors
 

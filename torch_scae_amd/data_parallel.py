@@ -186,6 +186,21 @@ def world():
     return 0, 1
 
 
+def all_reduce_sums(buf, group=None):
+    """``buf`` <- its sum over the ranks, in place: one all-reduce of a small buffer (an
+    evaluation step's fp64 accumulator, eval_step.EvalStep) outside any graph.  A no-op
+    with one rank.  gloo reduces a host copy."""
+    if world()[1] <= 1:
+        return buf
+    if buf.is_cuda and dist.get_backend(group) == "gloo":
+        host = buf.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        buf.copy_(host)
+    else:
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    return buf
+
+
 def broadcast_parameters(flat: FlatParameters, src=0):
     """Make every rank start from rank ``src``'s weights."""
     if world()[1] > 1:

@@ -1,0 +1,426 @@
+"""One SCAE evaluation batch = forward + SCAE.loss + SCAE.calculate_accuracy under
+``model.eval()`` and ``no_grad``, optionally captured once into a HIP graph and replayed,
+with the epoch's means kept in a device-resident fp64 accumulator: a whole epoch is N
+replays and one read at its end.
+
+Mirrors the semantics of the reference's BaseExperiment.validation_step /
+validation_epoch_end / test_step / test_epoch_end
+(torch_scae_experiments/base_experiment.py:128-202)."""
+import contextlib
+
+import torch
+
+from . import ops
+from .data_parallel import all_reduce_sums, world
+
+# the accumulator (include/scae_hip.h, SCAE_EVAL_ACC_DOUBLES): [0] batches, then the sums
+# of these keys ([5] is the 12-vector's loss entry, the same value as [1]: not a key)
+ACC_KEYS = {"loss": 1, "accuracy": 2, "prior_accuracy": 3, "posterior_accuracy": 4,
+            "log_prob": 6, "prior_within_sparsity_loss": 7,
+            "prior_between_sparsity_loss": 8, "posterior_within_sparsity_loss": 9,
+            "posterior_between_sparsity_loss": 10, "prior_cls_xe": 11,
+            "posterior_cls_xe": 12, "rec_ll": 13, "rec_ll_loss": 14, "log_prob_loss": 15,
+            "cpr_dynamic_reg_loss": 16}
+ACC_DOUBLES = 17
+
+
+def means(sums):
+    """{key: fp32 mean} of an accumulator (fp64, any device): sum / number of batches --
+    the reference's unweighted mean over batches.  Empty (no batch) -> NaN means."""
+    s = sums.detach().to("cpu", torch.float64)
+    n = float(s[0])
+    out = {k: (s[i] / n if n else torch.tensor(float("nan"), dtype=torch.float64))
+           .to(torch.float32) for k, i in ACC_KEYS.items()}
+    out["batches"] = int(n)
+    return out
+
+
+def out12_from_log(loss, log):
+    """The loss tail's 12-vector (ops.loss_tail_scalar) from SCAE.loss's log dict, for a
+    loss the fused tail did not complete; entries the model does not log are zero."""
+    z = torch.zeros((), device=loss.device, dtype=loss.dtype)
+
+    def get(k):
+        v = log.get(k)
+        return z if v is None else v.detach().reshape(()).to(loss.dtype)
+    rec_loss, lp_loss = get("rec_ll_loss"), get("log_prob_loss")
+    return torch.stack([loss.detach().reshape(()), -lp_loss,
+                        get("prior_within_sparsity_loss"), get("prior_between_sparsity_loss"),
+                        get("posterior_within_sparsity_loss"),
+                        get("posterior_between_sparsity_loss"), get("prior_cls_xe"),
+                        get("posterior_cls_xe"), -rec_loss, rec_loss, lp_loss,
+                        get("cpr_dynamic_reg_loss")])
+
+
+def accumulate_host(acc, loss, out12, prior, post, label):
+    """The epilogue's accumulation (csrc/eval_tail.hip) for a model on the CPU: the same
+    sums, in torch.  Returns the batch's (accuracy, prior, posterior) accuracies."""
+    pa = qa = torch.zeros((), dtype=torch.float32)
+    if label is not None:
+        B = label.shape[0]
+        pa = (prior.argmax(-1) == label).sum().to(torch.float32) / B
+        qa = (post.argmax(-1) == label).sum().to(torch.float32) / B
+    best = torch.maximum(pa, qa)
+    acc[0] += 1.0
+    acc[1] += loss.detach().double().reshape(())
+    acc[2] += best.double()
+    acc[3] += pa.double()
+    acc[4] += qa.double()
+    acc[5:17] += out12.detach().double().cpu()
+    return torch.stack([best, pa, qa])
+
+
+class EvalStep:
+    """``EvalStep(model, batch_size, image_shape)``: ``step(image, label)`` runs one
+    evaluation batch and returns its loss (a device tensor the next call overwrites); the
+    batch is added to the step's fp64 accumulator, ``epoch_means()`` reads it.
+
+    Inside the step's plan the forward takes the training step's fused launches under
+    ``no_grad`` (image layer and folding products in the prologue, coloured templates in
+    the part-capsule head, the reconstruction likelihood in the object encoder's trunk,
+    the class probabilities in the loss tail's per-image launch), and the loss tail ends
+    in the evaluation epilogue (csrc/eval_tail.hip) instead of its batch combine.  A model
+    the fused tail does not complete (``recon_mse_weight`` > 0,
+    ``part_caps_sparsity_weight`` > 0, more than 32 classes, ``fuse_kernels=False``) takes
+    its own loss launches and then the epilogue's accumulation alone.
+
+    The step runs its warm-ups, capture and eager calls with ``model.eval()`` (the part
+    encoder draws no noise; the object decoder's uniform noise comes from the step's own
+    device generator) and restores ``model.training``.  It has its own plan, prologue and
+    noise generator and writes no gradients and no optimiser state.  Parameters re-homed
+    after the capture (a ``TrainStep`` built later moves them into flat buffers) are
+    detected by a pointer check and the step recaptures; in-place updates need nothing.
+    With a process group of world > 1 ``*_epoch_end`` / ``epoch_means`` sum the
+    accumulators of all ranks first (data_parallel.all_reduce_sums).
+
+    ``replay``: "graph" (hipGraphLaunch) or "launches" (the recorded launch list, when the
+    captured graph holds only library launches; else the graph).  ``autocast_dtype``:
+    torch.bfloat16 takes the training step's bf16 operand paths."""
+
+    def __init__(self, model, batch_size, image_shape, use_graph=True, replay="graph",
+                 autocast_dtype=None, lazy_render=True, prologue=True, fuse_kernels=True):
+        if not isinstance(batch_size, int) or isinstance(batch_size, bool) \
+                or batch_size <= 0:
+            raise ValueError(f"batch_size must be a positive int, got {batch_size!r}")
+        image_shape = tuple(image_shape)
+        if len(image_shape) != 3 or not all(isinstance(d, int) and d > 0
+                                            for d in image_shape):
+            raise ValueError(f"image_shape must be (C, H, W), got {image_shape!r}")
+        if replay not in ("graph", "launches"):
+            raise ValueError("replay must be 'graph' or 'launches'")
+        if autocast_dtype not in (None, torch.bfloat16):
+            raise ValueError("autocast_dtype must be None or torch.bfloat16")
+        self.model = model
+        self._params = [p for p in model.parameters()]
+        if not self._params:
+            raise ValueError("model has no parameters")
+        self.device = self._params[0].device
+        self.batch_size, self.image_shape = batch_size, image_shape
+        self.cuda = self.device.type == "cuda"
+        self.use_graph = use_graph and self.cuda
+        self.replay, self.autocast_dtype = replay, autocast_dtype
+        self.lazy_render, self.prologue, self.fuse_kernels = lazy_render, prologue, \
+            fuse_kernels
+        dec = getattr(model, "part_decoder", None)
+        self._lazy_dec = dec if lazy_render and hasattr(dec, "lazy_render") else None
+        self._pro = ops.StepPrologue() if prologue and self.cuda else None
+        # this step's plan: its prologue, parked launches and noise generator
+        self.plan = ops.StepPlan("eval step", prologue=self._pro)
+        self.epi = ops.EvalEpilogue(self.device) if self.cuda else None
+        self.acc = self.epi.acc if self.cuda else \
+            torch.zeros(ACC_DOUBLES, dtype=torch.float64)
+        self.batch_acc = self.epi.batch3 if self.cuda else torch.zeros(3)
+        self.image = torch.zeros(batch_size, *image_shape, device=self.device)
+        self.label = torch.zeros(batch_size, dtype=torch.long, device=self.device)
+        self.loss = torch.zeros((), device=self.device)
+        self.graph = None
+        self.graph_nodes = None  # (graph nodes, kernel nodes, recorded launches) of a capture
+        self.fused = None        # the captured batch ends in the fused epilogue
+        self._klist = None
+        self._launches = None
+        self._stream = None
+        self._home = None        # parameter storage the capture read
+        self._tail_step = None   # evaluate()'s remainder batch
+
+    # -- the batch ----------------------------------------------------------
+    def _storage(self):
+        ps = self._params
+        return (ps[0].data_ptr(), ps[-1].data_ptr())
+
+    @contextlib.contextmanager
+    def _eval_mode(self):
+        was = self.model.training
+        self.model.eval()
+        prev = None
+        if self._lazy_dec is not None:
+            prev, self._lazy_dec.lazy_render = self._lazy_dec.lazy_render, True
+        try:
+            with torch.no_grad():
+                yield
+        finally:
+            if self._lazy_dec is not None:
+                self._lazy_dec.lazy_render = prev
+            self.model.train(was)
+
+    def _label_arg(self):
+        return self.label if getattr(self.model, "n_classes", None) is not None else None
+
+    def _batch(self):
+        """forward + loss + epilogue on the resident buffers (eval mode, no_grad)."""
+        model, label = self.model, self._label_arg()
+        if not self.cuda:
+            res = model(self.image)
+            loss, log = model.loss(res, self.image, label)
+            probs = (res.prior_cls_prob, res.posterior_cls_prob) if label is not None \
+                else (None, None)
+            self.batch_acc.copy_(accumulate_host(self.acc, loss, out12_from_log(loss, log),
+                                                 *probs, label))
+            self.loss.copy_(loss.detach())
+            return
+        plan, epi = self.plan, self.epi
+        epi.fused = False
+        with plan.active(), plan.precision(self.autocast_dtype is not None), \
+                plan.fusing(self.image if self.fuse_kernels else None), \
+                plan.evaluating(epi):
+            res = model(self.image)
+            loss, log = model.loss(res, self.image, label)
+        self.fused = epi.fused
+        if not epi.fused:
+            with plan.active():
+                probs = (res.prior_cls_prob, res.posterior_cls_prob) \
+                    if label is not None else (None, None)
+                epi.accumulate(loss.detach(), out12_from_log(loss, log), *probs, label)
+        if torch.cuda.is_current_stream_capturing():
+            # the captured loss lives in the graph's pool at a fixed address
+            self.loss = loss.detach()
+        else:
+            self.loss.copy_(loss.detach())
+
+    def _refresh_prologue(self):
+        if self._pro is not None:
+            with self.plan.active():
+                self._pro.launch(stream_ref=self.image)
+
+    def _stage(self, image, label):
+        """The batch into the resident buffers: the prologue's hand-over launch when both
+        tensors already live on the device in the buffers' layout."""
+        if tuple(image.shape) != tuple(self.image.shape) or \
+                tuple(label.shape) != tuple(self.label.shape):
+            raise ValueError(f"batch of shape {tuple(image.shape)} / {tuple(label.shape)}; "
+                             f"this step takes {tuple(self.image.shape)} / "
+                             f"{tuple(self.label.shape)}")
+        direct = image.is_cuda and label.is_cuda and image.dtype == self.image.dtype \
+            and label.dtype == self.label.dtype and image.is_contiguous() \
+            and label.is_contiguous() and image.device == self.device == label.device
+        if self._pro is not None and direct:
+            with self.plan.active():
+                self._pro.launch(self.image, image, self.label, label)
+            return
+        self.image.copy_(image, non_blocking=True)
+        self.label.copy_(label, non_blocking=True)
+        self._refresh_prologue()
+
+    # -- capture / replay ---------------------------------------------------
+    def _capture(self):
+        import ctypes
+        import torch.distributed as dist
+        from . import _lib
+        # parameters re-homed since the last capture: the prologue's registered layer
+        # inputs point at the old storage -- a fresh prologue (the generator state lives
+        # in the plan and continues)
+        if self._home is not None and self._pro is not None:
+            self._pro = ops.StepPrologue()
+            self.plan.prologue = self._pro
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(self.device)
+        s = self._stream
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with self._eval_mode():
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    self._refresh_prologue()
+                    self._batch()
+                self._refresh_prologue()    # what the capture below consumes
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            # the warm-ups' batches are not the epoch's
+            self.acc.zero_()
+            try:
+                # (keep_graph: the captured graph stays readable -- graph_nodes)
+                graph = torch.cuda.CUDAGraph(keep_graph=True)
+            except TypeError:        # (a torch without keep_graph: graph replay only)
+                graph = torch.cuda.CUDAGraph()
+            mode = "thread_local" if dist.is_available() and dist.is_initialized() \
+                else "global"
+            lib = _lib.load()
+            self._free_list()
+            klist = lib.scae_launch_list_begin(ctypes.c_void_p(s.cuda_stream))
+            try:
+                with torch.cuda.graph(graph, stream=s, capture_error_mode=mode), \
+                        _lib.recorder() as launches:
+                    self._batch()
+                if klist:
+                    lib.scae_launch_list_end(klist)
+                self.graph, self._launches = graph, launches
+                if klist and self.replay == "launches" and \
+                        self._graph_is_only_launches(lib.scae_launch_list_size(klist)):
+                    self._klist, klist = klist, None
+                elif self._klist is None:
+                    self._graph_is_only_launches(
+                        lib.scae_launch_list_size(klist) if klist else -1)
+            finally:
+                if klist:
+                    lib.scae_launch_list_free(klist)
+        self._home = self._storage()
+        self._refresh_prologue()
+
+    def _graph_is_only_launches(self, n_launches):
+        """True when the captured graph's nodes are exactly ``n_launches`` kernel nodes (the
+        library's record); sets ``graph_nodes``."""
+        import ctypes
+        try:
+            raw = self.graph.raw_cuda_graph()
+            hip = ctypes.CDLL("libamdhip64.so")
+            n = ctypes.c_size_t(0)
+            if hip.hipGraphGetNodes(ctypes.c_void_p(raw), None, ctypes.byref(n)) != 0:
+                return False
+            nodes = (ctypes.c_void_p * max(1, n.value))()
+            if hip.hipGraphGetNodes(ctypes.c_void_p(raw), nodes, ctypes.byref(n)) != 0:
+                return False
+            kernels = other = 0
+            for i in range(n.value):
+                t = ctypes.c_int(-1)
+                if hip.hipGraphNodeGetType(ctypes.c_void_p(nodes[i]), ctypes.byref(t)) != 0:
+                    return False
+                kernels += t.value == 0          # hipGraphNodeTypeKernel
+                other += t.value not in (0, 5, 6, 7)
+            self.graph_nodes = (n.value, kernels, n_launches)
+            return other == 0 and kernels == n_launches
+        except Exception:       # (no raw graph in this torch build)
+            return False
+
+    def _free_list(self):
+        if getattr(self, "_klist", None):
+            from . import _lib
+            _lib.load().scae_launch_list_free(self._klist)
+        self._klist = None
+
+    def __del__(self):
+        try:
+            self._free_list()
+        except Exception:      # (interpreter shutdown)
+            pass
+
+    def capture(self):
+        """Build the step's graph now (or again, when the parameters have been re-homed
+        since the last capture).  The accumulator is left cleared."""
+        if self.use_graph and (self.graph is None or self._home != self._storage()):
+            self.graph = None
+            self._capture()
+
+    def __call__(self, image, label):
+        """One evaluation batch: stage, run (replay), accumulate.  -> the batch loss."""
+        self._stage(image, label)
+        if self.use_graph:
+            if self.graph is None or self._home != self._storage():
+                # (a capture runs warm-up batches: keep what the epoch has so far)
+                kept = self.acc.clone()
+                self.capture()
+                self.acc.copy_(kept)
+                self._stage(image, label)
+            if self._klist:
+                import ctypes
+                from . import _lib
+                _lib.call("scae_launch_list_run2", self._klist, ctypes.c_void_p(
+                    torch.cuda.current_stream(self.device).cuda_stream), None)
+            else:
+                self.graph.replay()
+        else:
+            with self._eval_mode():
+                self._batch()
+        return self.loss
+
+    # -- the reference's hooks ----------------------------------------------
+    def _eager_result(self):
+        """One eager no_grad forward of the staged batch (not replayed): the ``result``
+        for image logging (validation_epoch_end, base_experiment.py:145-184)."""
+        with self._eval_mode():
+            return self.model(self.image.clone())
+
+    def validation_step(self, image, label, batch_idx=None):
+        """-> {'val_loss', 'accuracy'} as device tensors the next call overwrites
+        (base_experiment.py:128-143); with ``batch_idx == 0`` also 'result'."""
+        loss = self(image, label)
+        out = {"val_loss": loss, "accuracy": self.batch_acc[0]}
+        if batch_idx == 0:
+            out["result"] = self._eager_result()
+        return out
+
+    def test_step(self, image, label, batch_idx=None):
+        """-> {'test_loss', 'accuracy'} (base_experiment.py:186-195).  The reference's
+        test_step stores the ``(loss, info)`` tuple of SCAE.loss as 'test_loss', which its
+        test_epoch_end's ``torch.stack`` cannot take; this returns the loss tensor."""
+        loss = self(image, label)
+        out = {"test_loss": loss, "accuracy": self.batch_acc[0]}
+        if batch_idx == 0:
+            out["result"] = self._eager_result()
+        return out
+
+    def _global_sums(self):
+        sums = self.acc.clone()
+        if world()[1] > 1:
+            all_reduce_sums(sums)
+        return sums
+
+    def epoch_means(self):
+        """{key: fp32 mean over the batches so far} (one read; across ranks when a process
+        group of world > 1 is up), plus 'batches'."""
+        return means(self._global_sums())
+
+    def reset(self):
+        self.acc.zero_()
+
+    def _epoch_end(self, prefix):
+        m = self.epoch_means()
+        self.reset()
+        return {f"{prefix}_loss": m["loss"],
+                "log": {f"{prefix}_loss": m["loss"], f"{prefix}_accuracy": m["accuracy"]}}
+
+    def validation_epoch_end(self, outputs=None):
+        """-> {'val_loss', 'log': {'val_loss', 'val_accuracy'}} (base_experiment.py:145-184:
+        the unweighted means over the epoch's batches); clears the accumulator."""
+        return self._epoch_end("val")
+
+    def test_epoch_end(self, outputs=None):
+        """-> {'test_loss', 'log': {'test_loss', 'test_accuracy'}} (:197-202)."""
+        return self._epoch_end("test")
+
+    def evaluate(self, images, labels):
+        """A whole split: every full batch replayed, the remainder through a second step of
+        the remainder's size (captured once, cached; not padded -- the between-example
+        terms depend on the batch size).  -> ``epoch_means()`` of the split: the unweighted
+        mean over its batches, as the reference's loop (and a ``drop_last=False`` loader)
+        gives.  Starts from a cleared accumulator and leaves it cleared."""
+        N, B = images.shape[0], self.batch_size
+        if labels.shape[0] != N or N == 0:
+            raise ValueError("images and labels must hold the same number (> 0) of examples")
+        full, rem = divmod(N, B)
+        tail = None
+        if rem:
+            tail = self._tail_step
+            if tail is None or tail.batch_size != rem:
+                tail = self._tail_step = EvalStep(
+                    self.model, rem, self.image_shape, use_graph=self.use_graph,
+                    replay=self.replay, autocast_dtype=self.autocast_dtype,
+                    lazy_render=self.lazy_render, prologue=self.prologue,
+                    fuse_kernels=self.fuse_kernels)
+            tail.reset()
+        self.reset()
+        for i in range(full):
+            self(images[i * B:(i + 1) * B], labels[i * B:(i + 1) * B])
+        sums = self._global_sums()
+        if tail is not None:
+            tail(images[full * B:], labels[full * B:])
+            sums = sums + tail._global_sums()
+            tail.reset()
+        self.reset()
+        return means(sums)

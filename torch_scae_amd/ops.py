@@ -617,6 +617,12 @@ def offer_log_prob_rider(inputs, x):
     return plan.rider
 
 
+def evaluating():
+    """Inside an evaluation step's forward + loss (eval_step.EvalStep): the fused launches
+    of a training step's forward are taken under ``no_grad`` too."""
+    return _plan().evaluation is not None
+
+
 def withdraw_log_prob_rider():
     """After the object encoder: a rider nobody launched is dropped."""
     plan = _plan()
@@ -1861,7 +1867,8 @@ def offer_colored_templates(template_logits, w1, b1, w2, b2, template_nonlin,
     coloured-template kernel that the next ``colored_templates`` call with
     these parameters (and that encoder's ``feature``) would launch."""
     plan = _plan()
-    if plan.fused and torch.is_grad_enabled() and template_logits.is_cuda:
+    if plan.fused and (torch.is_grad_enabled() or plan.evaluation is not None) \
+            and template_logits.is_cuda:
         plan.offer("tc_fwd", _TcOffer(template_logits, w1, b1, w2, b2,
                                       _NONLIN_CODE[template_nonlin],
                                       _NONLIN_CODE[color_nonlin]))
@@ -2866,7 +2873,14 @@ class _LossTail(torch.autograd.Function):
         defer = ctx.plan.fused and rec_sums is not None and \
             any(ctx.needs_input_grad) and \
             bool(_lib.load().scae_loss_tail_defer_preferred(B, O))
-        ex.defer_combine = int(defer)
+        # an evaluation step's loss, when this launch pair forms the whole scalar (rec_sums):
+        # the per-image launch, then the evaluation epilogue (combine + accuracies +
+        # accumulation) in place of the combine
+        ev = ctx.plan.evaluation if ctx.plan.fused and rec_sums is not None else None
+        if ev is not None and label is not None and not ctx.plan.holds("class_probs"):
+            ev = None               # (no class probabilities to read: the plain tail)
+        defer = defer and ev is None
+        ex.defer_combine = int(defer or ev is not None)
         # per-image / per-column statistics the backward kernel reads back
         ws = torch.empty(_lib.load().scae_loss_tail_workspace_floats(
             ints[0], ints[1], ints[3]), device=lpp.device, dtype=lpp.dtype)
@@ -2878,6 +2892,9 @@ class _LossTail(torch.autograd.Function):
                       _stream(lpp))
         else:
             _lib.call("scae_loss_tail_fwd_f32", *tail, _stream(lpp))
+        if ev is not None:
+            probs = (None, None) if label is None else parked.keep[4:6]
+            ev.fused_launch(tail, *probs, keep=(ws, both, ex, w5), stream_ref=lpp)
         ctx.save_for_backward(lpp, posterior, caps_presence, ws,
                               *([cls_w, cls_b, label] if label is not None
                                 else []),
@@ -2958,6 +2975,38 @@ def loss_tail_scalar(lpp, posterior, caps_presence, cls_w, cls_b, label,
            float(w_reg))
     return _LossTail.apply(lpp, posterior, caps_presence, cls_w, cls_b, label,
                            rec_sums, reg, cfg)
+
+
+class EvalEpilogue:
+    """Buffers of an evaluation step's epilogue (csrc/eval_tail.hip): the fp64 epoch
+    accumulator (include/scae_hip.h, SCAE_EVAL_ACC_DOUBLES) and the batch's three accuracies.
+    ``fused_launch``: the loss tail's combine + accuracies + accumulation, called by
+    ``_LossTail.forward`` inside an evaluation plan; ``accumulate``: accuracies +
+    accumulation alone, for a loss the tail did not complete."""
+
+    def __init__(self, device):
+        self.acc = torch.zeros(_lib.EVAL_ACC_DOUBLES, device=device, dtype=torch.float64)
+        self.batch3 = torch.zeros(3, device=device, dtype=torch.float32)
+        self.fused = False      # the last forward ended in the fused epilogue
+        self._keep = None       # what the last launch points into
+
+    def fused_launch(self, tail, prior, post, keep, stream_ref):
+        _need_hip(prior, post)
+        _lib.call("scae_eval_tail_f32", *tail, _p(prior), _p(post), _p(self.acc),
+                  _p(self.batch3), _stream(stream_ref))
+        self.fused, self._keep = True, (keep, prior, post)
+
+    def accumulate(self, loss, out12, prior, post, label):
+        """loss (), out12 (12) or None, class probabilities (B, ncls) and label (B) int64, or
+        three Nones (no classes)."""
+        _need_hip(loss, out12, prior, post)
+        B = 1 if label is None else label.shape[0]
+        ncls = 0 if prior is None else prior.shape[-1]
+        loss, out12, prior, post = _c(loss), _c(out12), _c(prior), _c(post)
+        lab = None if label is None else ctypes.c_void_p(_c(label).data_ptr())
+        _lib.call("scae_eval_accumulate_f32", _p(loss), _p(out12), _p(prior), _p(post), lab,
+                  B, ncls, _p(self.acc), _p(self.batch3), _stream(loss))
+        self._keep = (loss, out12, prior, post, label)
 
 
 def loss_tail(*args, **kwargs):

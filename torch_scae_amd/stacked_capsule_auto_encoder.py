@@ -251,7 +251,8 @@ class SCAE(nn.Module):
         target = ops.fusion_target()
         dec = self.part_decoder
         if target is None or target.data_ptr() != image.data_ptr() or \
-                target.shape != image.shape or not torch.is_grad_enabled() \
+                target.shape != image.shape \
+                or not (torch.is_grad_enabled() or ops.evaluating()) \
                 or self.vote_type != 'enc' or self.presence_type != 'enc' \
                 or not self.fuse_loss_tail or self.recon_mse_weight > 0 \
                 or self.part_caps_sparsity_weight > 0 \

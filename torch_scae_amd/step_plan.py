@@ -154,6 +154,10 @@ class StepPlan:
         # 0: one workgroup per (component, image) pair, which floods the chip)
         self.side_resident = int(_os.environ.get("SCAE_SIDE_RESIDENT", "512"))
         self._main = None         # the stream the side lane forked from, while it is open
+        # eval_step.EvalStep's epilogue buffers (ops.EvalEpilogue) while its forward + loss
+        # run: a no-grad forward then takes the training step's fused launches, and the loss
+        # tail ends in the evaluation epilogue instead of its batch combine
+        self.evaluation = None
 
     # -- the second lane ----------------------------------------------------
     @contextlib.contextmanager
@@ -333,6 +337,14 @@ class StepPlan:
             yield pro
         finally:
             self.prologue = prev
+
+    @contextlib.contextmanager
+    def evaluating(self, epilogue):
+        prev, self.evaluation = self.evaluation, epilogue
+        try:
+            yield self
+        finally:
+            self.evaluation = prev
 
     @contextlib.contextmanager
     def precision(self, bf16):
