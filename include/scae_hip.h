@@ -847,6 +847,51 @@ int scae_step_prologue_first_f32(float *dst_image, const float *src_image, int64
                                  uint64_t *noise_state, const scae_seed_fold_desc *fold,
                                  const scae_first_layer_desc *first, void *stream);
 
+/* A batch source: a dataset held in device memory, read through the epoch's order with the
+ * reference's MNIST transform applied on the way in (Pad + RandomAffine(translate):
+ * mnist/experiment.py:23-40; base_experiment.py:79-93 for the loaders).  Device code:
+ * csrc/batch_source_dev.h; torch_scae_amd/data.py holds the CPU form of every draw.
+ *   Slot b of rank `rank`'s batch of B is epoch position p = position + rank*B + b (a step's
+ *   global batch is world*B positions from `position`); p -> view row perm(p) -> dataset
+ *   row index[perm(p)] (index NULL: the view row itself).
+ *   shuffle 0: perm = identity (the reference's loaders do not shuffle); 1: a keyed
+ *   pseudo-random permutation of [0, n) (4-round Feistel network, Philox round keys of
+ *   (seed, epoch, round), cycle-walked) -- not a uniform draw over all n! orders.
+ *   translate 1: per-example shifts (dy, dx) = round-half-even(U(-pad, pad)) per axis,
+ *   pad = (H - h) / 2, drawn by Philox from (seed; p, epoch); 0: centred padding.
+ *   out[b, c, i, j] = x[row, c, i - top, j - left] where that pixel exists, else 0,
+ *   top = (H - h)/2 + dy, left = (W - w)/2 + dx; uint8 pixels / 255.0f (correctly rounded).
+ *   Labels (uint8 or int64) are written as int64.  C <= 4 (else SCAE_ERR_UNSUPPORTED),
+ *   h <= H, w <= W, n < 2^31, position + (rank + 1) * B <= n. */
+typedef struct scae_batch_source_desc {
+  const void *images;     /* (rows, C, h, w) uint8 (image_u8 = 1) or fp32 in [0, 1] */
+  const void *labels;     /* (rows) uint8 (label_u8 = 1) or int64; nullable without labels out */
+  const int32_t *index;   /* (n) dataset rows of the view, nullable: rows 0 .. n-1 */
+  int64_t rows;           /* examples in the dataset (rows outside it read as zeros) */
+  int64_t n;              /* examples in the view */
+  int image_u8, label_u8;
+  int C, h, w, H, W;
+  int shuffle, translate;
+  uint64_t seed;
+  int64_t epoch, position;
+  int rank, world;
+} scae_batch_source_desc;
+/* The rank's batch of B from `src` into dst_image (B, C, H, W) fp32 and dst_label (B) int64
+ * (nullable), one launch. */
+int scae_gather_batch_f32(float *dst_image, int64_t *dst_label, int B,
+                          const scae_batch_source_desc *src, void *stream);
+/* scae_step_prologue_first_f32 with the batch hand-over taken from `src`: its staging
+ * workgroups gather the rank's batch of B into dst_image / dst_label (as
+ * scae_gather_batch_f32), and the image layer's workgroups (first, nullable) build their LDS
+ * copy of each image from `src` through the same device code -- first->img is not read; first
+ * must describe B images of src's (C, H, W).  Noise, folding products and re-layouts as
+ * there. */
+int scae_step_prologue_source_f32(float *dst_image, int64_t *dst_label, int B,
+                                  const scae_batch_source_desc *src, float *noise,
+                                  int64_t n_noise, uint64_t *noise_state,
+                                  const scae_seed_fold_desc *fold,
+                                  const scae_first_layer_desc *first, void *stream);
+
 /* ------------------------------------------------------------------------
  * K10  coloured templates      replaces TemplateGenerator.forward,
  *      part_decoder.py:78-110 (colorize_templates = True):

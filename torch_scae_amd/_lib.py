@@ -7,7 +7,7 @@ tensor is not on a HIP device, the ops raise.
 import ctypes
 import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int,
-                    c_int64, c_void_p)
+                    c_int64, c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SCAE_HIP_LIB: another build of the same library, for A/B measurements)
@@ -124,6 +124,16 @@ class FirstLayerDesc(Structure):
         [("rw", P * 8), ("rwf", P * 8), ("rwd", P * 8),
          ("rCout", c_int * 8), ("rCin", c_int * 8),
          ("out_h", P), ("rwfh", P * 8), ("rwdh", P * 8)]
+
+
+class BatchSourceDesc(Structure):
+    """struct scae_batch_source_desc"""
+    _fields_ = [("images", P), ("labels", P), ("index", P), ("rows", c_int64),
+                ("n", c_int64)] + \
+        [(n, c_int) for n in ("image_u8", "label_u8", "C", "h", "w", "H", "W",
+                              "shuffle", "translate")] + \
+        [("seed", c_uint64), ("epoch", c_int64), ("position", c_int64),
+         ("rank", c_int), ("world", c_int)]
 
 
 class SeedFoldGrads(Structure):
@@ -255,6 +265,9 @@ SIGNATURES = {
     "scae_step_prologue_first_f32": [P, P, c_int64, P, P, c_int64, P, c_int64,
                                      P, POINTER(SeedFoldDesc),
                                      POINTER(FirstLayerDesc), P],
+    "scae_gather_batch_f32": [P, P, c_int, POINTER(BatchSourceDesc), P],
+    "scae_step_prologue_source_f32": [P, P, c_int, POINTER(BatchSourceDesc), P, c_int64, P,
+                                      POINTER(SeedFoldDesc), POINTER(FirstLayerDesc), P],
     "scae_rmsprop_step_f32": [P, P, P, P, c_int64, c_float, P, c_float, c_float,
                               c_float, c_float, c_float, P],
     "scae_rmsprop_sums_step_f32": [P, P, P, P, c_int64, c_float, P, c_float, c_float,

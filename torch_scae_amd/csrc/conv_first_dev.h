@@ -118,19 +118,21 @@ __device__ __forceinline__ void stage_image(float *s_img, const float *img, int 
 
 // workgroup `blk` (256 threads) of the forward: image NCHW (B,Cin,IH,IW),
 // w [Cout][Cin][3][3] -> out NHWC, ReLU; s_img: Cin * IH * IW floats of LDS
-template <int CIN>
-__device__ __forceinline__ void fwd_block(const float *__restrict__ img,
-                                          const float *__restrict__ w,
-                                          const float *__restrict__ bias,
-                                          float *__restrict__ out, const ConvGeom &g, int blk,
-                                          float *s_img,
-                                          unsigned short *__restrict__ out_h = nullptr) {
+// fwd_block_from: the same with image n staged into s_img by stage(s_img, n) (all threads,
+// ending in a barrier) -- the step prologue's batch source builds it from a dataset
+template <int CIN, typename Stage>
+__device__ __forceinline__ void fwd_block_from(const Stage &stage,
+                                               const float *__restrict__ w,
+                                               const float *__restrict__ bias,
+                                               float *__restrict__ out, const ConvGeom &g,
+                                               int blk, float *s_img,
+                                               unsigned short *__restrict__ out_h = nullptr) {
   // out_h (nullable): the same values as bf16 INSTEAD of the fp32 tensor (the bf16-resident
   // layers behind it read nothing else)
   const FirstSplit f = first_split(g.B, g.Cout);
   const int n = blk / f.slices, slice = blk % f.slices;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  stage_image(s_img, img, n, CIN * g.IH * g.IW);
+  stage(s_img, n);
   const int P = g.OH * g.OW, per = (P + f.slices - 1) / f.slices;
   const int pbeg = slice * per, pend = min(P, pbeg + per);
   if (first_vec(g.Cout)) {
@@ -202,5 +204,17 @@ __device__ __forceinline__ void fwd_block(const float *__restrict__ img,
       while (ow >= g.OW) ow -= g.OW, ++oh;
     }
   }
+}
+
+template <int CIN>
+__device__ __forceinline__ void fwd_block(const float *__restrict__ img,
+                                          const float *__restrict__ w,
+                                          const float *__restrict__ bias,
+                                          float *__restrict__ out, const ConvGeom &g, int blk,
+                                          float *s_img,
+                                          unsigned short *__restrict__ out_h = nullptr) {
+  const int count = CIN * g.IH * g.IW;
+  fwd_block_from<CIN>([&](float *s, int n) { stage_image(s, img, n, count); }, w, bias, out, g,
+                      blk, s_img, out_h);
 }
 }  // namespace scae_first

@@ -12,7 +12,11 @@
 // They have no dependencies between them and are each a few workgroups to a few hundred: as
 // separate launches they cost a dependent-dispatch floor each (~5 + 5 + 15 + 11 us at
 // cfg-2); here they are block ranges of one grid.  Any part may be absent.
+// With a batch source (scae_step_prologue_source_f32) the hand-over is a gather from a
+// device-resident dataset (batch_source_dev.h): one staging workgroup per image, and the image
+// layer's workgroups build their LDS image from the dataset through the same device code.
 #include "common.h"
+#include "batch_source_dev.h"
 #include "noise_dev.h"
 #include "seed_fold_dev.h"
 #include "conv_first_dev.h"
@@ -41,10 +45,12 @@ struct Prologue {
   scae_first::RelayoutBatch rl;
   int n_first, rb;
   int nb_stage, nb_noise, nb_fold, nb_first;
+  scae_batch_source_desc src;   // (SRC: the hand-over's source; nb_stage = its batch)
 };
 
-// CIN: input channels of the image layer (0: no image layer in this launch)
-template <int CIN>
+// CIN: input channels of the image layer (0: no image layer in this launch); SRC: the batch
+// comes from p.src instead of src_image / src_label
+template <int CIN, bool SRC>
 __global__ __launch_bounds__(NT) void step_prologue_kernel(Prologue p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int blk = blockIdx.x;
@@ -55,8 +61,20 @@ __global__ __launch_bounds__(NT) void step_prologue_kernel(Prologue p) {
   blk -= p.nb_fold;
   if (CIN > 0) {
     if (blk < p.n_first) {
-      scae_first::fwd_block<(CIN > 0 ? CIN : 1)>(p.first_img, p.first_w, p.first_bias, p.first_out,
-                                               p.first_g, blk, lds, p.first_out_h);
+      if (SRC) {
+        const int B = p.nb_stage;
+        const auto stage = [&](float *s, int n) {
+          scae_src::gather_image(p.src, p.src.position + (int64_t)p.src.rank * B + n, s);
+          __syncthreads();
+        };
+        scae_first::fwd_block_from<(CIN > 0 ? CIN : 1)>(stage, p.first_w, p.first_bias,
+                                                        p.first_out, p.first_g, blk, lds,
+                                                        p.first_out_h);
+      } else {
+        scae_first::fwd_block<(CIN > 0 ? CIN : 1)>(p.first_img, p.first_w, p.first_bias,
+                                                   p.first_out, p.first_g, blk, lds,
+                                                   p.first_out_h);
+      }
       return;
     }
     if (blk < p.nb_first) {
@@ -71,6 +89,14 @@ __global__ __launch_bounds__(NT) void step_prologue_kernel(Prologue p) {
     return;
   }
   blk -= p.nb_noise;
+  if (SRC) {   // one workgroup per image of the rank's batch
+    const int B = p.nb_stage;
+    const scae_src::Draw d = scae_src::gather_image(
+        p.src, p.src.position + (int64_t)p.src.rank * B + blk,
+        p.dst_image + (size_t)blk * p.src.C * p.src.H * p.src.W);
+    if (p.dst_label && threadIdx.x == 0) p.dst_label[blk] = scae_src::label_of(p.src, d);
+    return;
+  }
   const long tid = (long)blk * NT + threadIdx.x, stride = (long)p.nb_stage * NT;
   const bool vec = (((size_t)p.dst_image | (size_t)p.src_image) & 15) == 0;
   const long n4 = vec ? p.n_image >> 2 : 0;
@@ -81,15 +107,27 @@ __global__ __launch_bounds__(NT) void step_prologue_kernel(Prologue p) {
 }
 }  // namespace
 
-extern "C" int scae_step_prologue_first_f32(float *dst_image, const float *src_image,
-                                            int64_t n_image, int64_t *dst_label,
-                                            const int64_t *src_label, int64_t n_label,
-                                            float *noise, int64_t n_noise, uint64_t *noise_state,
-                                            const scae_seed_fold_desc *fold,
-                                            const scae_first_layer_desc *first, void *stream) {
+namespace {
+// the launch of scae_step_prologue_first_f32 (src == NULL) / scae_step_prologue_source_f32
+int prologue_launch(float *dst_image, const float *src_image, int64_t n_image,
+                    int64_t *dst_label, const int64_t *src_label, int64_t n_label,
+                    const scae_batch_source_desc *src, int src_B, float *noise,
+                    int64_t n_noise, uint64_t *noise_state, const scae_seed_fold_desc *fold,
+                    const scae_first_layer_desc *first, void *stream) {
   Prologue p{};
   size_t lds = 0;
-  if (n_image > 0) {
+  if (src) {
+    SCAE_REQUIRE(dst_image);
+    const int rc = scae_src::check(src, src_B);
+    if (rc) return rc;
+    SCAE_REQUIRE(!dst_label || src->labels);
+    p.src = *src;
+    p.nb_stage = src_B;
+    p.dst_image = dst_image, p.dst_label = dst_label;
+    if (first && (first->B != src_B || first->Cin != src->C || first->IH != src->H ||
+                  first->IW != src->W))
+      return SCAE_ERR_BAD_ARG;
+  } else if (n_image > 0) {
     SCAE_REQUIRE(dst_image && src_image && n_label >= 0 &&
                  (n_label == 0 || (dst_label && src_label)));
     long blocks = (n_image / 4 + NT - 1) / NT;
@@ -119,7 +157,7 @@ extern "C" int scae_step_prologue_first_f32(float *dst_image, const float *src_i
   int cin = 0;
   if (first) {
     const scae_first_layer_desc &f = *first;
-    SCAE_REQUIRE(f.img && f.w && f.bias && f.out && f.B > 0 && f.IH >= 3 && f.IW >= 3 &&
+    SCAE_REQUIRE((f.img || src) && f.w && f.bias && f.out && f.B > 0 && f.IH >= 3 && f.IW >= 3 &&
                  f.Cout > 0 && f.stride > 0 && f.n_layers >= 0 && f.n_layers <= 8);
     if (f.Cin < 1 || f.Cin > 4 || f.Cout % 64) return SCAE_ERR_UNSUPPORTED;
     const size_t img_lds = (size_t)f.Cin * f.IH * f.IW * sizeof(float);
@@ -140,20 +178,45 @@ extern "C" int scae_step_prologue_first_f32(float *dst_image, const float *src_i
   }
   const int grid = p.nb_stage + p.nb_noise + p.nb_fold + p.nb_first;
   SCAE_REQUIRE(grid > 0);
-#define SCAE_PROLOGUE(CI)                                                                     \
-  case CI: {                                                                                  \
+#define SCAE_PROLOGUE(CI, SRC)                                                                \
+  case CI + 8 * SRC: {                                                                        \
+    const void *k = reinterpret_cast<const void *>(step_prologue_kernel<CI, SRC>);            \
     if (lds > 48 * 1024) {                                                                    \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(step_prologue_kernel<CI>), \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
       if (e != hipSuccess) return (int)e;                                                     \
     }                                                                                         \
-    scae::launch(step_prologue_kernel<CI>, dim3(grid), dim3(NT), lds, (hipStream_t)stream, p); \
+    scae::launch(step_prologue_kernel<CI, SRC>, dim3(grid), dim3(NT), lds,                    \
+                 (hipStream_t)stream, p);                                                     \
   } break;
-  switch (cin) {
-    SCAE_PROLOGUE(0) SCAE_PROLOGUE(1) SCAE_PROLOGUE(2) SCAE_PROLOGUE(3) SCAE_PROLOGUE(4)
+  switch (cin + (src ? 8 : 0)) {
+    SCAE_PROLOGUE(0, false) SCAE_PROLOGUE(1, false) SCAE_PROLOGUE(2, false)
+    SCAE_PROLOGUE(3, false) SCAE_PROLOGUE(4, false)
+    SCAE_PROLOGUE(0, true) SCAE_PROLOGUE(1, true) SCAE_PROLOGUE(2, true)
+    SCAE_PROLOGUE(3, true) SCAE_PROLOGUE(4, true)
   }
 #undef SCAE_PROLOGUE
   return scae_launch_status();
+}
+}  // namespace
+
+extern "C" int scae_step_prologue_first_f32(float *dst_image, const float *src_image,
+                                            int64_t n_image, int64_t *dst_label,
+                                            const int64_t *src_label, int64_t n_label,
+                                            float *noise, int64_t n_noise, uint64_t *noise_state,
+                                            const scae_seed_fold_desc *fold,
+                                            const scae_first_layer_desc *first, void *stream) {
+  return prologue_launch(dst_image, src_image, n_image, dst_label, src_label, n_label, nullptr,
+                         0, noise, n_noise, noise_state, fold, first, stream);
+}
+
+extern "C" int scae_step_prologue_source_f32(float *dst_image, int64_t *dst_label, int B,
+                                             const scae_batch_source_desc *src, float *noise,
+                                             int64_t n_noise, uint64_t *noise_state,
+                                             const scae_seed_fold_desc *fold,
+                                             const scae_first_layer_desc *first, void *stream) {
+  SCAE_REQUIRE(src);
+  return prologue_launch(dst_image, nullptr, 0, dst_label, nullptr, 0, src, B, noise, n_noise,
+                         noise_state, fold, first, stream);
 }
 
 extern "C" int scae_step_prologue_f32(float *dst_image, const float *src_image, int64_t n_image,

@@ -13,7 +13,16 @@ dataset can be fetched: ten glyph classes, each a fixed set of pen strokes,
 rendered under a random affine warp per sample -- images with parts that recur
 under pose changes, which is what the part capsules model.  (U[0,1) noise
 images have no such structure: trained on them the capsules switch off within
-a few hundred steps)"""
+a few hundred steps)
+
+``ResidentDataset`` holds a dataset in device memory once; its views
+(``split`` / ``view``) are the reference's loaders and ``random_split``
+(torch_scae_experiments/base_experiment.py:79-93, mnist/experiment.py:23-55)
+with the transform applied on the device: a training step gathers its batch
+in its prologue launch (csrc/batch_source_dev.h, ``TrainStep.step_from``).
+Every view also has a CPU path that computes the same order and shifts in
+integer torch ops."""
+import gzip
 import math
 
 import torch
@@ -88,3 +97,317 @@ def stroke_batches(n_batches, batch, image_shape, seed=0, device="cpu",
     images = (ink * colour.view(N, C, 1, 1)).clamp(0, 1)
     return (images.view(n_batches, batch, C, H, W).contiguous(),
             labels.view(n_batches, batch).to(device))
+
+
+# -- device-resident datasets ---------------------------------------------------------------
+# The draws of csrc/batch_source_dev.h in integer torch ops (int64 tensors holding uint32
+# values): Philox4x32 with the device generator's constants and key schedule (noise_dev.h).
+_M32 = 0xFFFFFFFF
+_TAG_PERM, _TAG_SHIFT = 0x5045524D, 0x53484654
+_FEISTEL_ROUNDS, _F_PHILOX_ROUNDS, _KEY_PHILOX_ROUNDS = 4, 3, 10
+
+
+def _mulhilo(a, m):
+    """(hi, lo) 32-bit words of a * m (a: uint32 values, m: a uint32 constant), in 16-bit
+    limbs so that no int64 product overflows."""
+    pl, ph = a * (m & 0xFFFF), a * (m >> 16)
+    s = (pl & _M32) + ((ph & 0xFFFF) << 16)
+    return ((pl >> 32) + (ph >> 16) + (s >> 32)) & _M32, s & _M32
+
+
+def _philox(c, k0, k1, rounds):
+    c = list(c)
+    for _ in range(rounds):
+        hi0, lo0 = _mulhilo(c[0], 0xD2511F53)
+        hi1, lo1 = _mulhilo(c[2], 0xCD9E8D57)
+        c = [hi1 ^ c[1] ^ k0, lo1, hi0 ^ c[3] ^ k1, lo0]
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c
+
+
+def _word(v, like):
+    return torch.full_like(like, v & _M32)
+
+
+def _round_keys(seed, epoch):
+    r = torch.arange(_FEISTEL_ROUNDS, dtype=torch.int64)
+    c = _philox([r, _word(epoch, r), _word(epoch >> 32, r), _word(_TAG_PERM, r)],
+                seed & _M32, (seed >> 32) & _M32, _KEY_PHILOX_ROUNDS)
+    return list(zip(c[0].tolist(), c[1].tolist()))
+
+
+def feistel_order(positions, n, seed, epoch):
+    """View rows of epoch positions (int64 tensor, values in [0, n)) under the shuffled
+    order: a keyed pseudo-random permutation of [0, n) -- a 4-round Feistel network over the
+    smallest even bit width k with 2^k >= n, round keys drawn by Philox from (seed, epoch,
+    round), cycle-walked into [0, n).  Not a uniform draw over all n! orders."""
+    x = positions.to(torch.int64).clone()
+    if n <= 1:
+        return x
+    k = 0
+    while (1 << k) < n:
+        k += 2
+    h, m = k // 2, (1 << (k // 2)) - 1
+    keys = _round_keys(seed, epoch)
+    todo = torch.ones_like(x, dtype=torch.bool)
+    while bool(todo.any()):
+        v = x[todo]
+        L, R = v >> h, v & m
+        zero = torch.zeros_like(R)
+        for k0, k1 in keys:
+            f = _philox([R, zero, zero, zero], k0, k1, _F_PHILOX_ROUNDS)[0]
+            L, R = R, L ^ (f & m)
+        x[todo] = (L << h) | R
+        todo = x >= n
+    return x
+
+
+def shift_rule(r24, pad):
+    """round-half-to-even(2 pad r / 2^24 - pad) of 24-bit uniforms r, exactly in integers
+    (torchvision's RandomAffine translation: round(U(-pad, pad)))."""
+    num = 2 * pad * r24.to(torch.int64)
+    f, rem = (num >> 24) - pad, num & 0xFFFFFF
+    half = 0x800000
+    return torch.where(rem > half, f + 1, torch.where(rem < half, f, f + (f & 1)))
+
+
+def translate_shifts(positions, epoch, seed, pads):
+    """(len, 2) int64 (dy, dx) of epoch positions: two 24-bit uniforms of one Philox draw
+    keyed by ``seed`` at counter (position, epoch, tag); ``pads`` = (pad_h, pad_w)."""
+    p = positions.to(torch.int64)
+    c = _philox([p & _M32, _word(epoch, p), _word(epoch >> 32, p), _word(_TAG_SHIFT, p)],
+                seed & _M32, (seed >> 32) & _M32, _KEY_PHILOX_ROUNDS)
+    return torch.stack([shift_rule(c[0] >> 8, pads[0]), shift_rule(c[1] >> 8, pads[1])], 1)
+
+
+class ResidentDataset:
+    """A dataset held in device memory once: ``images`` (N, C, h, w) or (N, h, w), uint8
+    (pixels / 255, as ToTensor) or floating in [0, 1] (kept as fp32); ``labels`` (N,) uint8 or
+    any integer type (kept as int64).  Batches come out as (B, C, H, W) fp32 with ``out_size``
+    = (H, W) >= (h, w): zero padding of (H - h) // 2 per side, plus the training transform's
+    random translation where a view asks for it.  C <= 4."""
+
+    def __init__(self, images, labels, out_size=(40, 40), device="cuda"):
+        images, labels = torch.as_tensor(images), torch.as_tensor(labels)
+        if images.dim() == 3:
+            images = images.unsqueeze(1)
+        if images.dim() != 4 or labels.dim() != 1 or labels.shape[0] != images.shape[0]:
+            raise ValueError("images (N, C, h, w) or (N, h, w) and labels (N,) expected")
+        if images.shape[0] == 0 or images.shape[0] >= 2 ** 31:
+            raise ValueError("a dataset holds 1 .. 2^31 - 1 examples")
+        if images.dtype != torch.uint8:
+            if not images.dtype.is_floating_point:
+                raise ValueError("images must be uint8 or floating point")
+            images = images.to(torch.float32)
+        if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+            raise ValueError("labels must be integers")
+        if labels.dtype != torch.uint8:
+            labels = labels.to(torch.int64)
+        self.n, self.C, self.h, self.w = images.shape
+        self.H, self.W = (int(v) for v in out_size)
+        if not (1 <= self.C <= 4 and self.h <= self.H and self.w <= self.W):
+            raise ValueError(f"C <= 4 and out_size >= (h, w) needed, got C={self.C}, "
+                             f"(h, w)=({self.h}, {self.w}), out_size={tuple(out_size)}")
+        self.device = torch.device(device)
+        self.images = images.to(self.device).contiguous()
+        self.labels = labels.to(self.device).contiguous()
+
+    @property
+    def pads(self):
+        return (self.H - self.h) // 2, (self.W - self.w) // 2
+
+    def __len__(self):
+        return self.n
+
+    def view(self, shuffle=False, translate=True, seed=0, rank=0, world=1):
+        """The whole dataset as one view (``DatasetView``)."""
+        return DatasetView(self, None, shuffle, translate, seed, rank, world)
+
+    def split(self, lengths, generator=None, **view_args):
+        """Views over the rows ``torch.utils.data.random_split(range(N), lengths,
+        generator)`` gives (``torch.randperm(N, generator=generator)`` cut in turn); lengths
+        are integers summing to N.  ``view_args`` (shuffle, translate, seed, rank, world)
+        apply to every view; a view's attributes can be changed afterwards."""
+        lengths = [int(v) for v in lengths]
+        if sum(lengths) != self.n or any(v <= 0 for v in lengths):
+            raise ValueError("lengths must be positive and sum to the dataset's size")
+        perm = torch.randperm(self.n, generator=generator)
+        views, off = [], 0
+        for v in lengths:
+            views.append(DatasetView(self, perm[off:off + v], **view_args))
+            off += v
+        return views
+
+
+class DatasetView:
+    """A view of a ``ResidentDataset``: ``index`` (its dataset rows, None: all), read in the
+    epoch's order (``shuffle``: a keyed pseudo-random permutation per epoch, ``feistel_order``;
+    else the identity -- the reference's loaders do not shuffle) with per-example shifts
+    (``translate``; else centred padding).  The reference's validation split inherits the
+    training transform (``random_split`` shares the dataset object), so translate it too for
+    parity; its test set is not padded at all, which does not fit a 40 x 40 model: give the
+    test view ``translate=False`` for centred padding.
+
+    Rank sharding: step s of an epoch takes the global batch of world*B positions from
+    s*world*B; rank r takes slots [r*B, (r+1)*B).  An epoch has n // (world*B) steps and
+    training drops the remainder (a captured step has a fixed batch; the reference keeps it,
+    ``drop_last=False``) -- without shuffling the same last examples are skipped every epoch.
+    ``epoch`` / ``cursor`` (steps taken in the epoch) advance with ``TrainStep.step_from``;
+    ``state_dict`` carries them so that a resumed run continues in the same order."""
+
+    def __init__(self, dataset, index=None, shuffle=False, translate=True, seed=0, rank=0,
+                 world=1):
+        self.dataset = dataset
+        if index is not None:
+            index = torch.as_tensor(index).to("cpu", torch.int64).contiguous()
+            if index.dim() != 1 or index.numel() == 0 or \
+                    int(index.min()) < 0 or int(index.max()) >= dataset.n:
+                raise ValueError("index must hold dataset rows")
+        self.index = index
+        self.n = dataset.n if index is None else index.numel()
+        self.index_dev = None if index is None else \
+            index.to(torch.int32).to(dataset.device)
+        if not (isinstance(world, int) and world >= 1 and 0 <= rank < world):
+            raise ValueError(f"rank {rank} of world {world}")
+        self.shuffle, self.translate = bool(shuffle), bool(translate)
+        self.seed = int(seed) & ((1 << 64) - 1)
+        self.rank, self.world = int(rank), int(world)
+        self.epoch = self.cursor = 0
+
+    def __len__(self):
+        return self.n
+
+    # -- the order ------------------------------------------------------------------------
+    def steps_per_epoch(self, batch):
+        return self.n // (self.world * batch)
+
+    def positions(self, step, batch):
+        """Epoch positions of this rank's slots in step ``step``."""
+        return step * self.world * batch + self.rank * batch + torch.arange(batch)
+
+    def rows_and_shifts(self, epoch, positions):
+        """(dataset rows, (len, 2) shifts) of epoch positions -- the CPU path."""
+        p = torch.as_tensor(positions, dtype=torch.int64)
+        vr = feistel_order(p, self.n, self.seed, epoch) if self.shuffle else p
+        rows = vr if self.index is None else self.index[vr]
+        ds = self.dataset
+        shifts = translate_shifts(p, epoch, self.seed, ds.pads) if self.translate \
+            else torch.zeros(p.numel(), 2, dtype=torch.int64)
+        return rows, shifts
+
+    def indices_and_shifts(self, epoch, step, batch):
+        return self.rows_and_shifts(epoch, self.positions(step, batch))
+
+    def _cpu_batch(self, epoch, positions):
+        rows, shifts = self.rows_and_shifts(epoch, positions)
+        ds = self.dataset
+        src = ds.images[rows.to(ds.device)].cpu()
+        image = pad_and_translate(src, (ds.H, ds.W), shifts=shifts)
+        return image, ds.labels[rows.to(ds.device)].cpu().to(torch.int64)
+
+    def batch(self, epoch, step, batch):
+        """This rank's batch of step ``step`` of ``epoch`` on the CPU: (image (B, C, H, W)
+        fp32, label (B,) int64) -- what the device gather writes, bit for bit."""
+        return self._cpu_batch(epoch, self.positions(step, batch))
+
+    def materialise(self, epoch=None):
+        """Every example of the view in epoch position order (CPU): what an evaluation of
+        the view reads."""
+        return self._cpu_batch(self.epoch if epoch is None else epoch, torch.arange(self.n))
+
+    # -- the device side --------------------------------------------------------------------
+    def desc(self, epoch, position, rank=None):
+        """struct scae_batch_source_desc of this rank's batch at epoch position
+        ``position`` (of the step's global batch)."""
+        from . import _lib
+        ds = self.dataset
+        d = _lib.BatchSourceDesc()
+        d.images, d.labels = ds.images.data_ptr(), ds.labels.data_ptr()
+        d.index = None if self.index_dev is None else self.index_dev.data_ptr()
+        d.rows, d.n = ds.n, self.n
+        d.image_u8, d.label_u8 = int(ds.images.dtype == torch.uint8), \
+            int(ds.labels.dtype == torch.uint8)
+        d.C, d.h, d.w, d.H, d.W = ds.C, ds.h, ds.w, ds.H, ds.W
+        d.shuffle, d.translate = int(self.shuffle), int(self.translate)
+        d.seed, d.epoch, d.position = self.seed, int(epoch), int(position)
+        d.rank, d.world = self.rank if rank is None else rank, self.world
+        return d
+
+    def check(self, batch, image_shape):
+        ds = self.dataset
+        if tuple(image_shape) != (ds.C, ds.H, ds.W):
+            raise ValueError(f"the view gives ({ds.C}, {ds.H}, {ds.W}) images, the step "
+                             f"takes {tuple(image_shape)}")
+        if ds.device.type != "cuda":
+            raise ValueError("a step reads a dataset held on the device")
+        if self.steps_per_epoch(batch) == 0:
+            raise ValueError(f"{self.n} examples make no batch of {batch} x {self.world} ranks")
+
+    def gather(self, batch, epoch=None, step=None, image=None, label=None, rank=None,
+               position=None):
+        """This rank's batch on the device in one launch (scae_gather_batch_f32) -- by default
+        the batch the next ``TrainStep.step_from`` takes; into ``image`` / ``label`` when
+        given.  -> (image, label)."""
+        import ctypes
+        from . import _lib
+        ds = self.dataset
+        epoch = self.epoch if epoch is None else epoch
+        if position is None:
+            position = (self.cursor if step is None else step) * self.world * batch
+        if image is None:
+            image = torch.empty(batch, ds.C, ds.H, ds.W, device=ds.device)
+        if label is None:
+            label = torch.empty(batch, dtype=torch.int64, device=ds.device)
+        _lib.call("scae_gather_batch_f32", ctypes.c_void_p(image.data_ptr()),
+                  ctypes.c_void_p(label.data_ptr()), batch,
+                  ctypes.byref(self.desc(epoch, position, rank)),
+                  ctypes.c_void_p(torch.cuda.current_stream(ds.device).cuda_stream))
+        return image, label
+
+    def take_step(self, batch):
+        """(epoch, position) of the next step's global batch; advances the cursor, wrapping
+        to the next epoch after ``steps_per_epoch(batch)`` steps."""
+        spe = self.steps_per_epoch(batch)
+        if self.cursor >= spe:          # (a state loaded for another batch size)
+            self.epoch, self.cursor = self.epoch + 1, 0
+        out = (self.epoch, self.cursor * self.world * batch)
+        self.cursor += 1
+        if self.cursor == spe:
+            self.epoch, self.cursor = self.epoch + 1, 0
+        return out
+
+    def state_dict(self):
+        return {"epoch": self.epoch, "cursor": self.cursor, "seed": self.seed,
+                "shuffle": self.shuffle, "translate": self.translate, "n": self.n,
+                "rank": self.rank, "world": self.world}
+
+    def load_state_dict(self, sd):
+        if sd.get("n", self.n) != self.n or sd.get("world", self.world) != self.world:
+            raise ValueError("state of a view of another size / world")
+        self.seed = int(sd.get("seed", self.seed))
+        self.shuffle = bool(sd.get("shuffle", self.shuffle))
+        self.translate = bool(sd.get("translate", self.translate))
+        self.epoch, self.cursor = int(sd["epoch"]), int(sd["cursor"])
+
+
+_IDX_TYPES = {0x08: torch.uint8, 0x09: torch.int8, 0x0B: torch.int16, 0x0C: torch.int32,
+              0x0D: torch.float32, 0x0E: torch.float64}
+
+
+def read_idx(path):
+    """An IDX file (MNIST's format: train-images-idx3-ubyte, ...), plain or gzip-compressed
+    (``.gz``), from local disk -> a CPU tensor of its type and shape."""
+    import numpy as np
+    opener = gzip.open if str(path).endswith(".gz") else open
+    with opener(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 4 or raw[0] != 0 or raw[1] != 0 or raw[2] not in _IDX_TYPES:
+        raise ValueError(f"{path}: not an IDX file")
+    nd = raw[3]
+    dims = [int.from_bytes(raw[4 + 4 * i:8 + 4 * i], "big") for i in range(nd)]
+    dtype = _IDX_TYPES[raw[2]]
+    np_t = {torch.uint8: ">u1", torch.int8: ">i1", torch.int16: ">i2", torch.int32: ">i4",
+            torch.float32: ">f4", torch.float64: ">f8"}[dtype]
+    count = math.prod(dims)
+    data = np.frombuffer(raw, dtype=np_t, count=count, offset=4 + 4 * nd)
+    return torch.from_numpy(data.astype(np_t[1:]).reshape(dims).copy())

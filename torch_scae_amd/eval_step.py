@@ -220,6 +220,24 @@ class EvalStep:
         self.label.copy_(label, non_blocking=True)
         self._refresh_prologue()
 
+    def _stage_source(self, view, epoch, position, rank=None, standalone=False):
+        """The batch at ``position`` of ``epoch`` gathered from a device-resident dataset
+        (data.DatasetView) into the resident buffers: the prologue's source mode, or
+        (``standalone``, or no prologue) the standalone gather and a refresh of the
+        prologue."""
+        src = view.desc(epoch, position, rank)
+        if self._pro is not None and not standalone:
+            with self.plan.active():
+                self._pro.launch(self.image, None, self.label, source=src)
+            return
+        import ctypes
+        from . import _lib
+        P = ctypes.c_void_p
+        _lib.call("scae_gather_batch_f32", P(self.image.data_ptr()),
+                  P(self.label.data_ptr()), self.batch_size, ctypes.byref(src),
+                  P(torch.cuda.current_stream(self.device).cuda_stream))
+        self._refresh_prologue()
+
     # -- capture / replay ---------------------------------------------------
     def _capture(self):
         import ctypes
@@ -319,14 +337,17 @@ class EvalStep:
 
     def __call__(self, image, label):
         """One evaluation batch: stage, run (replay), accumulate.  -> the batch loss."""
-        self._stage(image, label)
+        return self._run(lambda: self._stage(image, label))
+
+    def _run(self, stage):
+        stage()
         if self.use_graph:
             if self.graph is None or self._home != self._storage():
                 # (a capture runs warm-up batches: keep what the epoch has so far)
                 kept = self.acc.clone()
                 self.capture()
                 self.acc.copy_(kept)
-                self._stage(image, label)
+                stage()
             if self._klist:
                 import ctypes
                 from . import _lib
@@ -394,26 +415,38 @@ class EvalStep:
         """-> {'test_loss', 'log': {'test_loss', 'test_accuracy'}} (:197-202)."""
         return self._epoch_end("test")
 
-    def evaluate(self, images, labels):
+    def _tail(self, rem):
+        tail = self._tail_step
+        if tail is None or tail.batch_size != rem:
+            tail = self._tail_step = EvalStep(
+                self.model, rem, self.image_shape, use_graph=self.use_graph,
+                replay=self.replay, autocast_dtype=self.autocast_dtype,
+                lazy_render=self.lazy_render, prologue=self.prologue,
+                fuse_kernels=self.fuse_kernels)
+        tail.reset()
+        return tail
+
+    def evaluate(self, images, labels=None):
         """A whole split: every full batch replayed, the remainder through a second step of
         the remainder's size (captured once, cached; not padded -- the between-example
         terms depend on the batch size).  -> ``epoch_means()`` of the split: the unweighted
         mean over its batches, as the reference's loop (and a ``drop_last=False`` loader)
-        gives.  Starts from a cleared accumulator and leaves it cleared."""
+        gives.  Starts from a cleared accumulator and leaves it cleared.
+
+        ``images`` may be a data.DatasetView instead of (images, labels): its examples in
+        the order and with the shifts of its current epoch (``view.materialise()``), the
+        full batches gathered in the step's prologue launch, the remainder by the
+        standalone gather into the tail step; the view then moves on to its next epoch.
+        With world > 1 rank r takes slots [r*B, (r+1)*B) of each global batch of world*B
+        and rank 0 alone the remainder of the view."""
+        from .data import DatasetView
+        if isinstance(images, DatasetView):
+            return self._evaluate_view(images)
         N, B = images.shape[0], self.batch_size
-        if labels.shape[0] != N or N == 0:
+        if labels is None or labels.shape[0] != N or N == 0:
             raise ValueError("images and labels must hold the same number (> 0) of examples")
         full, rem = divmod(N, B)
-        tail = None
-        if rem:
-            tail = self._tail_step
-            if tail is None or tail.batch_size != rem:
-                tail = self._tail_step = EvalStep(
-                    self.model, rem, self.image_shape, use_graph=self.use_graph,
-                    replay=self.replay, autocast_dtype=self.autocast_dtype,
-                    lazy_render=self.lazy_render, prologue=self.prologue,
-                    fuse_kernels=self.fuse_kernels)
-            tail.reset()
+        tail = self._tail(rem) if rem else None
         self.reset()
         for i in range(full):
             self(images[i * B:(i + 1) * B], labels[i * B:(i + 1) * B])
@@ -423,4 +456,32 @@ class EvalStep:
             sums = sums + tail._global_sums()
             tail.reset()
         self.reset()
+        return means(sums)
+
+    def _evaluate_view(self, view):
+        if not self.cuda:
+            raise ValueError("evaluating a device-resident dataset needs a device step")
+        B, W = self.batch_size, view.world
+        ds = view.dataset
+        if (ds.C, ds.H, ds.W) != self.image_shape:
+            raise ValueError(f"the view gives ({ds.C}, {ds.H}, {ds.W}) images, the step "
+                             f"takes {self.image_shape}")
+        full = view.steps_per_epoch(B)
+        done = full * W * B
+        rem = view.n - done if view.rank == 0 else 0
+        tail = self._tail(rem) if rem else None
+        epoch = view.epoch
+        self.reset()
+        for i in range(full):
+            self._run(lambda: self._stage_source(view, epoch, i * W * B))
+        sums = self.acc.clone()
+        if tail is not None:
+            tail._run(lambda: tail._stage_source(view, epoch, done, rank=0,
+                                                 standalone=True))
+            sums += tail.acc
+            tail.reset()
+        if world()[1] > 1:
+            all_reduce_sums(sums)
+        self.reset()
+        view.epoch, view.cursor = epoch + 1, 0
         return means(sums)

@@ -207,9 +207,13 @@ class StepPrologue:
         return d
 
     def launch(self, dst_image=None, src_image=None, dst_label=None,
-               src_label=None, stream_ref=None):
+               src_label=None, stream_ref=None, source=None):
         """One launch: batch hand-over (when the four tensors are given) +
-        whatever of noise / folding this prologue has buffers for."""
+        whatever of noise / folding this prologue has buffers for.  With
+        ``source`` (a scae_batch_source_desc, data.DatasetView.desc) the
+        hand-over gathers the batch of ``dst_image``'s size from a
+        device-resident dataset instead (src_image / src_label unused) and the
+        image layer reads the dataset too (scae_step_prologue_source_f32)."""
         stage = dst_image is not None
         n_noise = 0 if self.noise is None else self.noise.numel()
         # the image layer runs here when the batch it will be asked for is the
@@ -231,15 +235,22 @@ class StepPrologue:
                                            *self.fold_dims))
         if first:
             fdesc = ctypes.byref(self._first_desc(
-                src_image if stage else self.first_inputs[0]))
-        _lib.call("scae_step_prologue_first_f32",
-                  _p(dst_image), _p(src_image),
-                  dst_image.numel() if stage else 0,
-                  P(dst_label.data_ptr()) if stage else None,
-                  P(src_label.data_ptr()) if stage else None,
-                  dst_label.numel() if stage else 0,
-                  _p(self.noise), n_noise, _p(self.noise_state), desc, fdesc,
-                  _stream(ref))
+                src_image if stage and source is None else
+                dst_image if stage else self.first_inputs[0]))
+        if source is not None:
+            _lib.call("scae_step_prologue_source_f32", _p(dst_image),
+                      _p(dst_label), dst_image.shape[0], ctypes.byref(source),
+                      _p(self.noise), n_noise, _p(self.noise_state), desc, fdesc,
+                      _stream(ref))
+        else:
+            _lib.call("scae_step_prologue_first_f32",
+                      _p(dst_image), _p(src_image),
+                      dst_image.numel() if stage else 0,
+                      P(dst_label.data_ptr()) if stage else None,
+                      P(src_label.data_ptr()) if stage else None,
+                      dst_label.numel() if stage else 0,
+                      _p(self.noise), n_noise, _p(self.noise_state), desc, fdesc,
+                      _stream(ref))
         self.noise_fresh = self.noise is not None
         self.fold_fresh = fold_here
         self.first_fresh = first

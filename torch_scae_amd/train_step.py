@@ -557,9 +557,55 @@ class TrainStep:
         self.image.copy_(image, non_blocking=True)
         self.label.copy_(label, non_blocking=True)
 
+    def _stage_source(self, view, epoch, position):
+        """The batch at ``position`` of ``epoch`` gathered from a device-resident dataset
+        into the resident input buffers: the step's prologue launch, or the standalone
+        gather without a prologue."""
+        src = view.desc(epoch, position)
+        if self._pro is not None:
+            with self.plan.active():
+                self._pro.launch(self.image, None, self.label, source=src)
+            return
+        import ctypes
+        from . import _lib
+        P = ctypes.c_void_p
+        _lib.call("scae_gather_batch_f32", P(self.image.data_ptr()),
+                  P(self.label.data_ptr()), self.image.shape[0], ctypes.byref(src),
+                  P(torch.cuda.current_stream(self.device).cuda_stream))
+
+    def step_from(self, view):
+        """One step on the next batch of ``view`` (data.DatasetView of a
+        ResidentDataset on this step's device): the batch is gathered -- order, padding
+        and shifts applied -- in the step's prologue launch, with no torch operator and no
+        host-to-device copy.  Advances the view's cursor and wraps to its next epoch after
+        ``view.steps_per_epoch(batch)`` steps (the LR decays in ``end_epoch``).  -> the
+        loss (a device tensor the next step overwrites)."""
+        B = self.image.shape[0]
+        view.check(B, self.image.shape[1:])
+        if self.world > 1 and (view.rank, view.world) != world():
+            raise ValueError(f"view of rank {view.rank} / world {view.world} in a step "
+                             f"of rank {world()[0]} / world {self.world}")
+        epoch, position = view.take_step(B)
+        self._stage_source(view, epoch, position)
+        return self._step_staged()
+
+    def train_epoch(self, view):
+        """The view's remaining steps of its current epoch (``step_from``), then
+        ``end_epoch()``.  -> the last step's loss (a device tensor)."""
+        B = self.image.shape[0]
+        view.check(B, self.image.shape[1:])
+        epoch, loss = view.epoch, None
+        while view.epoch == epoch:
+            loss = self.step_from(view)
+        self.end_epoch()
+        return loss
+
     def __call__(self, image, label):
         """image / label may be device tensors; copied into the static inputs."""
         self._stage(image, label)
+        return self._step_staged()
+
+    def _step_staged(self):
         self.steps += 1
         if self.use_graph:
             self.capture()
