@@ -33,8 +33,7 @@ done
 # the rank-launcher + RCCL path on one GPU (1-rank nccl group)
 timeout 600 python bench.py --gpus 1 --force-spawn --steps 100 --no-cpu-baseline --no-roofline 2> /dev/null | grep '^{' > $O/bench_force_spawn.json
 rm -f $O/*_domain_stats.csv
-# upper bound of a multi-layer K8 launch and the image-resident forward (variant library built here)
-[ -f tools/ablibs/libscae_multi.so ] && timeout 300 python tools/conv_multi_probe.py tools/ablibs/libscae_multi.so > $O/conv_multi_probe.txt 2>&1
+# phase stamps of the K8 forward tiles (variant library built here)
 [ -f tools/ablibs/libfwd_prof.so ] && timeout 300 python tools/fwd_prof.py tools/ablibs/libfwd_prof.so > $O/fwd_tile_timeline.txt 2>&1
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O -o gap -- python3 $R/tools/graph_gap_probe.py > /dev/null 2>&1)
 python3 tools/graph_gap_report.py $O/gap_kernel_trace.csv > $O/graph_gap.txt 2>&1; rm -f $O/gap_*.csv

@@ -27,8 +27,6 @@
 //     tap falls outside the output read zeros through the buffer descriptor's range check.
 // Accumulation order over K is (tap, channel) ascending in 16-wide MFMA steps -- the order of
 // the first form, whose results these kernels reproduce to round-off of the fp32 accumulators.
-#include <cstdlib>
-
 #include "mfma_pipe.h"
 #include "conv_first_dev.h"
 
@@ -569,12 +567,6 @@ int raise_lds(K kernel, int bytes) {
                                      hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   return e == hipSuccess ? SCAE_OK : (int)e;
 }
-// ring depth of the DMA-staged passes (tuning aid: SCAE_BF16R_NS=1..4)
-int ring_depth(const char *env, int dflt) {
-  const char *e = getenv(env);
-  const int v = e && *e ? atoi(e) : dflt;
-  return v < 1 ? 1 : (v > 4 ? 4 : v);
-}
 }  // namespace
 
 extern "C" int scae_conv3x3_bf16r_supported(int B, int IH, int IW, int Cin, int Cout, int stride) {
@@ -610,15 +602,15 @@ extern "C" int scae_conv3x3_fwd_bf16r(const uint16_t *in, const uint16_t *wf, co
   const int M = B * g.OH * g.OW;
   const dim3 grid(Cout / TN, (M + TM - 1) / TM);
 #define SCAE_FWD_NS(N)                                                                          \
-  case N:                                                                                       \
-    if ((rc = raise_lds(conv_fwd_bf16r_kernel<N>, N * STAGE_B))) return rc;                     \
-    scae::launch(conv_fwd_bf16r_kernel<N>, grid, dim3(NT), N * STAGE_B, (hipStream_t)stream, in, \
-                 wf, bias, out_h, out_f, post_bias, out_post, g);                                \
-    break;
-  // many tiles: one stage, five workgroups per CU covering each other; few: two stages
-  // (measured at B = 1024: 648 tiles 37.5 us against 41.6, 392 tiles 27.1 against 23.3)
-  switch (ring_depth("SCAE_BF16R_FWD_NS", (long)grid.x * grid.y > 512 ? 1 : 2)) {
-    SCAE_FWD_NS(1) SCAE_FWD_NS(2) SCAE_FWD_NS(3) SCAE_FWD_NS(4)
+  if ((rc = raise_lds(conv_fwd_bf16r_kernel<N>, N * STAGE_B))) return rc;                       \
+  scae::launch(conv_fwd_bf16r_kernel<N>, grid, dim3(NT), N * STAGE_B, (hipStream_t)stream, in,   \
+               wf, bias, out_h, out_f, post_bias, out_post, g);
+  // ring depth: many tiles, one stage, five workgroups per CU covering each other; few, two
+  // stages (measured at B = 1024: 648 tiles 37.5 us against 41.6, 392 tiles 27.1 against 23.3)
+  if ((long)grid.x * grid.y > 512) {
+    SCAE_FWD_NS(1)
+  } else {
+    SCAE_FWD_NS(2)
   }
 #undef SCAE_FWD_NS
   return scae_launch_status();
@@ -648,19 +640,20 @@ extern "C" int scae_conv3x3_dgrad_bf16r(const uint16_t *dpre, const uint16_t *wd
   if (covered != IH * IW) return SCAE_ERR_UNSUPPORTED;   // (every pixel is in one class pair)
   const dim3 grid(Cin / TN, tiles);
 #define SCAE_DG_NS(N)                                                                           \
-  case N:                                                                                       \
-    if (stride == 2) {                                                                          \
-      if ((rc = raise_lds(conv_dgrad_bf16r_kernel<N, true>, N * STAGE_B))) return rc;           \
-      scae::launch((conv_dgrad_bf16r_kernel<N, true>), grid, dim3(NT), N * STAGE_B,             \
-                   (hipStream_t)stream, dpre, wd, gate, din_h, din_f, g, pl);                    \
-    } else {                                                                                    \
-      if ((rc = raise_lds(conv_dgrad_bf16r_kernel<N, false>, N * STAGE_B))) return rc;          \
-      scae::launch((conv_dgrad_bf16r_kernel<N, false>), grid, dim3(NT), N * STAGE_B,            \
-                   (hipStream_t)stream, dpre, wd, gate, din_h, din_f, g, pl);                    \
-    }                                                                                           \
-    break;
-  switch (ring_depth("SCAE_BF16R_DGRAD_NS", (long)grid.x * grid.y > 512 ? 1 : 2)) {
-    SCAE_DG_NS(1) SCAE_DG_NS(2) SCAE_DG_NS(3) SCAE_DG_NS(4)
+  if (stride == 2) {                                                                            \
+    if ((rc = raise_lds(conv_dgrad_bf16r_kernel<N, true>, N * STAGE_B))) return rc;             \
+    scae::launch((conv_dgrad_bf16r_kernel<N, true>), grid, dim3(NT), N * STAGE_B,               \
+                 (hipStream_t)stream, dpre, wd, gate, din_h, din_f, g, pl);                      \
+  } else {                                                                                      \
+    if ((rc = raise_lds(conv_dgrad_bf16r_kernel<N, false>, N * STAGE_B))) return rc;            \
+    scae::launch((conv_dgrad_bf16r_kernel<N, false>), grid, dim3(NT), N * STAGE_B,              \
+                 (hipStream_t)stream, dpre, wd, gate, din_h, din_f, g, pl);                      \
+  }
+  // ring depth as the forward's
+  if ((long)grid.x * grid.y > 512) {
+    SCAE_DG_NS(1)
+  } else {
+    SCAE_DG_NS(2)
   }
 #undef SCAE_DG_NS
   return scae_launch_status();
@@ -687,15 +680,8 @@ extern "C" int scae_conv3x3_wgrad_bf16r(const uint16_t *dpre, const uint16_t *x,
   if (rc) return rc;
   const int splits = scae_conv3x3_wgrad_bf16r_splits(B, g.OH, g.OW, Cin, Cout);
   const dim3 grid(Cin / TN, Cout / TM, 9 * splits);
-#define SCAE_WG_NS(N)                                                                           \
-  case N:                                                                                       \
-    if ((rc = raise_lds(conv_wgrad_bf16r_tr_kernel<N>, N * STAGE_B))) return rc;                \
-    scae::launch(conv_wgrad_bf16r_tr_kernel<N>, grid, dim3(NT), N * STAGE_B,                    \
-                 (hipStream_t)stream, dpre, x, partial, g, splits);                             \
-    break;
-  switch (ring_depth("SCAE_BF16R_WGRAD_NS", 1)) {
-    SCAE_WG_NS(1) SCAE_WG_NS(2) SCAE_WG_NS(3) SCAE_WG_NS(4)
-  }
-#undef SCAE_WG_NS
+  // one ring stage (32 KiB: no LDS limit to raise)
+  scae::launch(conv_wgrad_bf16r_tr_kernel<1>, grid, dim3(NT), STAGE_B, (hipStream_t)stream, dpre,
+               x, partial, g, splits);
   return scae_launch_status();
 }

@@ -263,9 +263,9 @@ __global__ __launch_bounds__(NT) void conv_dgrad_kernel(const float *__restrict_
   dgrad_tile<MODE>(smem, blockIdx.x, blockIdx.y, dpre, wd, gate, din, g, pl);
 }
 
-// ---- weight gradient: grid (Cin/T, Cout/T, 9 taps * S splits) --------------------
+// ---- weight gradient: tile (bx, by) of tap / split bz (bf16 fallback of the pair launch) ----
 // partial[(split*9 + tap)][co][ci], then bias partials [split][co] after 9*S slabs
-template <int SK>   // workgroup shape (mfma_tile.h MODE 0, 1 or 3)
+template <int SK>   // workgroup shape (mfma_tile.h MODE 3)
 __device__ __forceinline__ void wgrad_tile(float *smem, int bx, int by, int bz,
                                            const float *__restrict__ dpre,
                                            const float *__restrict__ in,
@@ -337,15 +337,6 @@ __device__ __forceinline__ void wgrad_tile(float *smem, int bx, int by, int bz,
       partial[(size_t)splits * 9 * g.Cout * g.Cin + (size_t)split * g.Cout + co0 + tid] = sum;
     }
   }
-}
-
-template <int SK>
-__global__ __launch_bounds__(NT) void conv_wgrad_kernel(const float *__restrict__ dpre,
-                                                        const float *__restrict__ in,
-                                                        float *__restrict__ partial, ConvGeom g,
-                                                        int splits) {
-  __shared__ __attribute__((aligned(16))) float smem[Tile<SK>::SMEM];
-  wgrad_tile<SK>(smem, blockIdx.x, blockIdx.y, blockIdx.z, dpre, in, partial, g, splits);
 }
 
 // Data and weight gradient of one layer in ONE launch: both only wait for dpre, and
@@ -513,100 +504,6 @@ __global__ __launch_bounds__(pipe::NT, 4) void conv_fwd_pipe_fold_kernel(
     scae_fold::forward_block_any<16>(fold, plan, blk - n_conv, smem);
 }
 
-// ---- data gradient (tap classes as in dgrad_tile) -----------------------------------
-template <class T>
-__device__ __forceinline__ void dgrad_pipe_tile(float *smem, int bx, int by,
-                                                const float *__restrict__ dpre,
-                                                const float *__restrict__ wd,
-                                                const float *__restrict__ gate,
-                                                float *__restrict__ din, const ConvGeom &g,
-                                                const DgradPlan &pl) {
-  SCAE_PIPE_IDS
-  const int nz = pl.nrc * pl.ncc;
-  const int z = __popcll(__ballot(lane + 1 < nz && by >= pl.tile_start[min(lane + 1, 64)]));
-  const int rc = z / pl.ncc, cc = z - rc * pl.ncc;
-  const int AH = pl.rcount[rc], AW = pl.ccount[cc], M = g.B * AH * AW, KT = 9 * g.Cout;
-  const int m0 = (by - pl.tile_start[z]) * T::TA, n0 = bx * T::TB;
-  const int sh = g.stride - 1;
-  const int rm = pl.rmask[rc], cm = pl.cmask[cc];
-  const int nkh = __popc(rm), nkw = __popc(cm);
-  auto nth_bit = [](int mask, int n) {
-    const int k0 = (mask & 1) ? 0 : ((mask & 2) ? 1 : 2);
-    if (n == 0) return k0;
-    const int rest = mask & ~(1 << k0);
-    return (n == 1 && (rest & 2)) ? 1 : 2;
-  };
-  const int cpt = g.Cout / pipe::BK, nchunk = nkh * nkw * cpt;
-  const pipe::DmaLane da = pipe::dma_lane<T::TA>(wid, lane), db = pipe::dma_lane<T::TB>(wid, lane);
-  const pipe::rsrc_t ra =
-      pipe::make_rsrc(dpre, (unsigned)((size_t)g.B * g.OH * g.OW * g.Cout * 4));
-  const pipe::rsrc_t rb = pipe::make_rsrc(wd, (unsigned)((size_t)g.Cin * KT * 4));
-  int pn[T::RA], pih[T::RA], piw[T::RA], bvo[T::RB];
-#pragma unroll
-  for (int j = 0; j < T::RA; ++j) {
-    const int m = min(m0 + da.row0 + pipe::DMA_ROWS * j, M - 1);
-    const int n = m / (AH * AW), rem = m - n * AH * AW, a = rem / AW, b = rem - a * AW;
-    pn[j] = n * g.OH * g.OW;
-    pih[j] = pl.rlist[pl.rstart[rc] + a], piw[j] = pl.clist[pl.cstart[cc] + b];
-  }
-#pragma unroll
-  for (int j = 0; j < T::RB; ++j)
-    bvo[j] = ((n0 + db.row0 + pipe::DMA_ROWS * j) * KT + db.koff) * 4;
-  struct Ctx {
-    int kh, kw, soa, sob;
-  };
-  int c_co = 0, c_ti = 0, c_tj = 0;   // chunk -> (tap (ti, tj) of the class, channel block)
-  auto chunk = [&](int) {
-    const int kh = nth_bit(rm, c_ti), kw = nth_bit(cm, c_tj);
-    const Ctx x{kh, kw, c_co * 4, ((kh * 3 + kw) * g.Cout + c_co) * 4};
-    c_co += pipe::BK;
-    if (c_co == g.Cout) {
-      c_co = 0;
-      if (++c_tj == nkw) c_tj = 0, ++c_ti;
-    }
-    return x;
-  };
-  auto issue = [&](const Ctx &x, float *st, int j) {
-    if (j < T::RA) {
-      // the range check only ever fails on the merged classes of stride 2: such a
-      // lane reads zeros (an offset outside the descriptor)
-      const int dh = pih[j] - x.kh, dw = piw[j] - x.kw, oh = dh >> sh, ow = dw >> sh;
-      const bool ok = dh >= 0 && dw >= 0 && oh < g.OH && ow < g.OW;
-      const int vo = ok ? ((pn[j] + oh * g.OW + ow) * g.Cout + da.koff) * 4 : pipe::DMA_ZERO;
-      pipe::dma16(ra, st + da.loff + j * pipe::DMA_ROWS * pipe::BKH, vo, x.soa);
-    } else {
-      pipe::dma16(rb, st + T::TA * pipe::BK + db.loff + (j - T::RA) * pipe::DMA_ROWS * pipe::BKH,
-                  bvo[j - T::RA], x.sob);
-    }
-  };
-  pipe::f32x16 acc[T::MI][T::NI];
-  pipe::kk_zero<T>(acc);
-  pipe::kk_mainloop<T>(nchunk, smem, acc, wn, ks, li, lk, chunk, issue);
-  // the rows this lane finishes (16 per 32-row block), their pixels and gates: every load in
-  // flight before the first store, stores through a range-checked descriptor (no branches)
-  int ooff[T::MI][16];
-  float gt[T::MI][T::NI][16];
-#pragma unroll
-  for (int mi = 0; mi < T::MI; ++mi)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int m = m0 + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * lk, mc = min(m, M - 1);
-      const int nb = mc / (AH * AW), rem = mc - nb * AH * AW, a = rem / AW, b = rem - a * AW;
-      const int ih = pl.rlist[pl.rstart[rc] + a], iw = pl.clist[pl.cstart[cc] + b];
-      const int o = (((nb * g.IH + ih) * g.IW + iw) * g.Cin + n0) * 4;
-      ooff[mi][e] = m < M ? o : pipe::DMA_ZERO;
-#pragma unroll
-      for (int ni = 0; ni < T::NI; ++ni)
-        gt[mi][ni][e] = gate ? gate[o / 4 + (wn * T::NI + ni) * 32 + li] : 1.f;
-    }
-  const pipe::rsrc_t rdin = pipe::make_rsrc(din, (unsigned)((size_t)g.B * g.IH * g.IW * g.Cin * 4));
-  pipe::kk_epilogue_idx<T>(smem, acc, wid, wn, ks, li, lk,
-                           [&](int mi, int ni, int e, int, int col, float v) {
-    v = gt[mi][ni][e] > 0.f ? v : 0.f;
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), rdin, ooff[mi][e] + col * 4, 0, 0);
-  });
-}
-
 // ---- weight gradient: tile (bx, by) of tap / split bz ------------------------------------
 template <class T>
 __device__ __forceinline__ void wgrad_pipe_tile(float *smem, int bx, int by, int bz,
@@ -697,34 +594,11 @@ __device__ __forceinline__ void wgrad_pipe_tile(float *smem, int bx, int by, int
 }
 
 template <class T>
-__global__ __launch_bounds__(pipe::NT) void conv_dgrad_pipe_kernel(
-    const float *__restrict__ dpre, const float *__restrict__ wd, const float *__restrict__ gate,
-    float *__restrict__ din, ConvGeom g, DgradPlan pl) {
-  __shared__ __attribute__((aligned(1024))) float smem[T::SMEM];
-  dgrad_pipe_tile<T>(smem, blockIdx.x, blockIdx.y, dpre, wd, gate, din, g, pl);
-}
-template <class T>
 __global__ __launch_bounds__(pipe::NT) void conv_wgrad_pipe_kernel(
     const float *__restrict__ dpre, const float *__restrict__ in, float *__restrict__ partial,
     ConvGeom g, int splits) {
   __shared__ __attribute__((aligned(1024))) float smem[T::SMEM];
   wgrad_pipe_tile<T>(smem, blockIdx.x, blockIdx.y, blockIdx.z, dpre, in, partial, g, splits);
-}
-// data- and weight-gradient tiles of a layer in one launch (see conv_bwd_pair_kernel)
-template <class TD, class TW>
-__global__ __launch_bounds__(pipe::NT) void conv_bwd_pair_pipe_kernel(
-    const float *__restrict__ dpre, const float *__restrict__ wd, const float *__restrict__ gate,
-    float *__restrict__ din, const float *__restrict__ in, float *__restrict__ partial,
-    ConvGeom g, DgradPlan pl, int splits, PairGrid pg) {
-  constexpr int SM = TD::SMEM > TW::SMEM ? TD::SMEM : TW::SMEM;
-  __shared__ __attribute__((aligned(1024))) float smem[SM];
-  const int bid = blockIdx.x;
-  if (bid < pg.nd) {   // workgroup-uniform
-    dgrad_pipe_tile<TD>(smem, bid % pg.gx, bid / pg.gx, dpre, wd, gate, din, g, pl);
-  } else {
-    const int w = bid - pg.nd, bx = w % pg.wx, t = w / pg.wx;
-    wgrad_pipe_tile<TW>(smem, bx, t % pg.wy, t / pg.wy, dpre, in, partial, g, splits);
-  }
 }
 
 // ---- data-gradient tile, third form (DMODE 4) ------------------------------------------------
@@ -1104,92 +978,6 @@ __device__ __forceinline__ void dgrad_x6k_tile(float *smemf, int bx, int by,
   *reinterpret_cast<float4 *>(din + o + 4) = v.hi;
 }
 
-// The forward of a layer in the same form: 32 output pixels x 64 output channels, the 9 x C_in / 32
-// chunks dealt to the four waves.  A = input rows (a lane's source row is fixed, the tap moves the
-// wave-uniform offset), B = wf (C_out, 9, C_in).
-__device__ __forceinline__ void fwd_x6k_tile(float *smemf, int bx, int by,
-                                             const float *__restrict__ in,
-                                             const float *__restrict__ wf,
-                                             const float *__restrict__ bias,
-                                             float *__restrict__ out,
-                                             const float *__restrict__ post_bias,
-                                             float *__restrict__ out_post, const ConvGeom &g) {
-  using namespace dgk;
-  using dgx::swz;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int M = g.B * g.OH * g.OW, hw = g.OH * g.OW;
-  const int m0 = by * TM, n0 = bx * TN;
-  const pipe::rsrc_t ra = pipe::make_rsrc(in, (unsigned)((size_t)g.B * g.IH * g.IW * g.Cin * 4));
-  const pipe::rsrc_t rb = pipe::make_rsrc(wf, (unsigned)((size_t)g.Cout * 9 * g.Cin * 4));
-  int va[4], vb[8];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int row = 8 * j + (lane >> 3), m = m0 + row;
-    va[j] = pipe::DMA_ZERO;
-    if (m < M) {
-      const int n = m / hw, rem = m - n * hw, oh = rem / g.OW, ow = rem - oh * g.OW;
-      va[j] = (((n * g.IH + oh * g.stride) * g.IW + ow * g.stride) * g.Cin) * 4 +
-              swz(row, lane & 7) * 16;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int row = 8 * j + (lane >> 3);
-    vb[j] = ((n0 + row) * 9 * g.Cin) * 4 + swz(row, lane & 7) * 16;
-  }
-  const int cpt = g.Cin / BKF;
-  const Out8 v = pipeline(smemf, 9 * cpt, [&](int c, unsigned char *stage) {
-    const int tap = c / cpt, h = c - tap * cpt, kh = tap / 3, kw = tap - kh * 3;
-    const int sa = ((kh * g.IW + kw) * g.Cin + h * BKF) * 4, sb = (tap * g.Cin + h * BKF) * 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      pipe::dma16(ra, reinterpret_cast<float *>(stage + 8 * j * ROWB), va[j], sa);
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      pipe::dma16(rb, reinterpret_cast<float *>(stage + A_B + 8 * j * ROWB), vb[j], sb);
-  });
-  const int row = tid >> 3, c8 = 8 * (tid & 7), m = m0 + row, n = n0 + c8;
-  if (m >= M) return;
-  const float4 b0 = ld4(bias + n), b1 = ld4(bias + n + 4);
-  const float o[8] = {fmaxf(v.lo.x + b0.x, 0.f), fmaxf(v.lo.y + b0.y, 0.f), fmaxf(v.lo.z + b0.z, 0.f),
-                      fmaxf(v.lo.w + b0.w, 0.f), fmaxf(v.hi.x + b1.x, 0.f), fmaxf(v.hi.y + b1.y, 0.f),
-                      fmaxf(v.hi.z + b1.z, 0.f), fmaxf(v.hi.w + b1.w, 0.f)};
-  const size_t at = (size_t)m * g.Cout + n;
-  *reinterpret_cast<float4 *>(out + at) = make_float4(o[0], o[1], o[2], o[3]);
-  *reinterpret_cast<float4 *>(out + at + 4) = make_float4(o[4], o[5], o[6], o[7]);
-  if (out_post) {   // + the per-(channel, pixel) embedding bias, (Cout, OH, OW)
-    const float *pb = post_bias + (size_t)n * hw + m % hw;
-    float q[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) q[e] = o[e] + pb[(size_t)e * hw];
-    *reinterpret_cast<float4 *>(out_post + at) = make_float4(q[0], q[1], q[2], q[3]);
-    *reinterpret_cast<float4 *>(out_post + at + 4) = make_float4(q[4], q[5], q[6], q[7]);
-  }
-}
-__global__ __launch_bounds__(NT) void conv_fwd_x6k_kernel(
-    const float *__restrict__ in, const float *__restrict__ wf, const float *__restrict__ bias,
-    float *__restrict__ out, const float *__restrict__ post_bias, float *__restrict__ out_post,
-    ConvGeom g) {
-  __shared__ __attribute__((aligned(1024))) float smem[dgk::SMEM];
-  fwd_x6k_tile(smem, blockIdx.x, blockIdx.y, in, wf, bias, out, post_bias, out_post, g);
-}
-// ... with the folding products of the output attention as the tail of its grid
-// (conv_fwd_pipe_fold_kernel's riders).  Beside the ring tiles (four workgroups per CU: tiles
-// and riders all resident at once) the riders cost 0.8 us, beside these (three per CU) 8 - 10 us:
-// worth it for the large layers only (fwd_ksplit).
-__global__ __launch_bounds__(NT) void conv_fwd_x6k_fold_kernel(
-    const float *__restrict__ in, const float *__restrict__ wf, const float *__restrict__ bias,
-    float *__restrict__ out, const float *__restrict__ post_bias, float *__restrict__ out_post,
-    ConvGeom g, int gx, int n_conv, scae_seed_fold_desc fold, scae_fold::Plan plan) {
-  static_assert(dgk::SMEM >= FOLD_SMEM, "the riders' LDS");
-  __shared__ __attribute__((aligned(1024))) float smem[dgk::SMEM];
-  const int blk = blockIdx.x;
-  if (blk < n_conv)   // workgroup-uniform
-    fwd_x6k_tile(smem, blk % gx, blk / gx, in, wf, bias, out, post_bias, out_post, g);
-  else
-    scae_fold::forward_block_any<16>(fold, plan, blk - n_conv, smem);
-}
-
 // data-gradient tile by DMODE: 0 - 2 the first-generation shapes of mfma_tile.h, 4 / 5 the forms above
 template <int DMODE>
 struct DgradShape {
@@ -1515,25 +1303,18 @@ inline int tile_mode(long tiles64, long tiles_wide, long wide_min) {
   return !small_tiles(tiles64) ? 0 : (tiles_wide >= wide_min ? 2 : 1);
 }
 
-struct WgradPlan {
-  bool small;
-  int splits;
-};
-WgradPlan wgrad_plan(int M, int Cin, int Cout) {
-  // 64x64 tiles (half the L2 traffic per flop of the 32x32 shape); the grid is
-  // filled by splitting the pixel (K) dimension instead: >= 768 workgroups of
-  // >= 8 K chunks each, measured best on the encoder's 128-channel layers
-  WgradPlan p;
+// the weight gradient's 64x64 tiles (half the L2 traffic per flop of the 32x32 shape)
+// fill the grid by splitting the pixel (K) dimension: >= 768 workgroups of >= 8 K
+// chunks each, measured best on the encoder's 128-channel layers
+int wgrad_splits(int M, int Cin, int Cout) {
   const long tiles64 = (long)(Cin / 64) * (Cout / 64) * 9;
-  p.small = false;
 #ifndef SCAE_WGRAD_BLOCKS
 #define SCAE_WGRAD_BLOCKS 768
 #endif
   long s = (SCAE_WGRAD_BLOCKS + tiles64 - 1) / tiles64;
   const long cap = (M / BK) / 8;
   s = s > cap ? cap : s;
-  p.splits = (int)(s < 1 ? 1 : (s > 32 ? 32 : s));
-  return p;
+  return (int)(s < 1 ? 1 : (s > 32 ? 32 : s));
 }
 
 // second-generation tile shapes (mfma_pipe.h).  Ring depth: 3 stages; 4 / 5 / 6 measured at
@@ -1546,37 +1327,23 @@ WgradPlan wgrad_plan(int M, int Cin, int Cout) {
 #ifndef SCAE_PIPE_WBK
 #define SCAE_PIPE_WBK 32
 #endif
-using PipeC0 = pipe::KK<64, 128, 4, SCAE_PIPE_NS>;   // 4 waves x (64 x 32); 24 KiB / stage
-using PipeC1 = pipe::KK<32, 128, 4, SCAE_PIPE_NS>;   // 4 waves x (32 x 32); 20 KiB / stage
-using PipeC2 = pipe::KK<32, 64, 2, SCAE_PIPE_NS>;    // 2 x 2 (columns x k halves); 12 KiB
-using PipeC3 = pipe::KK<64, 64, 2, SCAE_PIPE_NS>;    // 2 x 2, 64 rows; 16 KiB
+// the forward: 2 x 2 waves (columns x k halves), 12 KiB per stage.  Measured on the
+// encoder's 128-channel layers at B = 128 and B = 1024, this 32 x 64 shape (4 workgroups
+// per CU, in-workgroup k split) wins or ties against 64 x 128, 32 x 128 and 64 x 64 --
+// with few tiles because it quantises best over 256 CUs, with many because four
+// workgroups per CU cover each other's barrier and DMA waits
+using PipeC2 = pipe::KK<32, 64, 2, SCAE_PIPE_NS>;
 // weight gradient: 2 x 2 waves x (32 x 32)
 using PipeW = pipe::SS<64, 64, SCAE_PIPE_WBK, SCAE_PIPE_NS>;
 // ... with 16-pixel chunks: a 24 KiB ring instead of 48, so that the pair launches of the small
 // layers hold more than three workgroups per CU (their data-gradient tiles need 18 KiB and
 // 60-114 registers).  B = 128: layer 4 31.7 -> 28.9 us, layer 3 47.4 -> 46.1, layer 2 +0.4;
-// at B = 1024 the 32-pixel chunks win by 7 % (tools/conv_multi_probe.py, round 5).
+// at B = 1024 the 32-pixel chunks win by 7 % (round 5).
 using PipeW16 = pipe::SS<64, 64, 16, SCAE_PIPE_NS>;
 #ifndef SCAE_WGRAD_SHORT_CHUNK_PIXELS
 #define SCAE_WGRAD_SHORT_CHUNK_PIXELS 8192   // layers with fewer output pixels take PipeW16
 #endif
 
-// shape for an (M rows) x (N columns) k-contiguous problem; an environment variable
-// (read per call; tuning aid) overrides: -1 = first-generation kernels
-inline int pipe_cfg(const char *env, long M, int N) {
-  const char *e = getenv(env);
-  if (e && *e) {
-    const int v = atoi(e);
-    if (v < 0) return -1;
-    if (N % 128 == 0 || v >= 2) return v > 3 ? 3 : v;
-  }
-  // measured on the encoder's 128-channel layers at B = 128 and B = 1024: the 32 x 64
-  // shape (4 workgroups per CU, in-workgroup k split) wins or ties everywhere -- with
-  // few tiles because it quantises best over 256 CUs, with many because four
-  // workgroups per CU cover each other's barrier and DMA waits
-  (void)M;
-  return 2;
-}
 }  // namespace
 
 extern "C" int64_t scae_conv3x3_wf_floats(int Cout, int Cin) {
@@ -1737,28 +1504,6 @@ static bool conv_bf16_shape(long rows, int Cin, int Cout) {
   return Cin % 128 == 0 && Cout % 128 == 0 && rows * (Cout / 128) >= 128 * 128;
 }
 
-// the forward form with the K loop dealt to the waves (fwd_x6k_tile) against the ring-pipelined
-// tiles, each ALONE: 34 -> 27 us at cfg-2's second layer, 42 -> 35 at CIFAR's, 210 / 121 / 68 ->
-// 184 / 102 / 57 at B = 1024.  In a training step the second layer's launch carries the folding
-// products, and beside these tiles (three workgroups per CU instead of four: tiles and riders no
-// longer fit one round) the riders cost 8 - 10 us instead of 0.8: cfg-2 35 -> 42 - 44 us, the step
-// 0.4966 -> 0.505 ms (0.498 with the riders back in the prologue); the B = 1024 step 4.61 -> 4.66
-// ms.  So it is an OPTION (SCAE_K8_FWDK = 1, or a tile-count threshold at build time), and ONE rule
-// serves the plain and the carrying launch: an eager step and a replayed one stay bit-identical.
-#ifndef SCAE_FWDK_MIN_TILES
-#define SCAE_FWDK_MIN_TILES 0   // 0: never by default
-#endif
-static bool fwd_ksplit(const ConvGeom &g) {
-  if (g.Cin % dgk::BKF || g.Cout % dgk::TN ||
-      (size_t)g.B * g.IH * g.IW * g.Cin * 4 >= (1u << 31))
-    return false;
-  const char *e = getenv("SCAE_K8_FWDK"), *f = getenv("SCAE_K8_FWD");
-  if (e && *e) return atoi(e) != 0;
-  if (f && *f) return false;
-  const long tiles = (long)(g.Cout / dgk::TN) * (((long)g.B * g.OH * g.OW + dgk::TM - 1) / dgk::TM);
-  return SCAE_FWDK_MIN_TILES > 0 && tiles >= SCAE_FWDK_MIN_TILES;
-}
-
 static int conv_fwd_impl(const float *in, const float *wf, const float *bias, float *out,
                          const float *post_bias, float *out_post, int B, int IH, int IW, int Cin,
                          int Cout, int stride, bool bf16, void *stream) {
@@ -1773,45 +1518,8 @@ static int conv_fwd_impl(const float *in, const float *wf, const float *bias, fl
                        wf, bias, out, post_bias, out_post, g);
     return scae_launch_status();
   }
-  if (fwd_ksplit(g)) {   // the K loop dealt to the waves (fwd_x6k_tile)
-    scae::launch(conv_fwd_x6k_kernel, dim3(Cout / dgk::TN, (M + dgk::TM - 1) / dgk::TM), dim3(NT),
-                 0, st, in, wf, bias, out, post_bias, out_post, g);
-    return scae_launch_status();
-  }
-  const int cfg = pipe_cfg("SCAE_K8_FWD", M, Cout);
-  if (cfg >= 0) {
-#define SCAE_FWD_PIPE(TT)                                                                    \
-  scae::launch(conv_fwd_pipe_kernel<TT>, dim3(Cout / TT::TB, (M + TT::TA - 1) / TT::TA), \
-                     dim3(pipe::NT), 0, st, in, wf, bias, out, post_bias, out_post, g)
-    switch (cfg) {
-      case 0: SCAE_FWD_PIPE(PipeC0); break;
-      case 1: SCAE_FWD_PIPE(PipeC1); break;
-      case 2: SCAE_FWD_PIPE(PipeC2); break;
-      default: SCAE_FWD_PIPE(PipeC3);
-    }
-#undef SCAE_FWD_PIPE
-    return scae_launch_status();
-  }
-#ifndef SCAE_FWD_WIDE_MIN
-#define SCAE_FWD_WIDE_MIN 300
-#endif
-#ifndef SCAE_FWD_SMALL_TILES
-#define SCAE_FWD_SMALL_TILES SCAE_SMALL_TILES
-#endif
-  const long f64 = (long)(Cout / 64) * ((M + 63) / 64), f32 = (long)(Cout / 64) * ((M + 31) / 32);
-  switch (f64 >= SCAE_FWD_SMALL_TILES ? 0 : (f32 >= SCAE_FWD_WIDE_MIN ? 2 : 1)) {
-    case 0:
-      scae::launch(conv_fwd_kernel<0>, dim3(Cout / 64, (M + 63) / 64), dim3(NT), 0, st, in,
-                         wf, bias, out, post_bias, out_post, g);
-      break;
-    case 2:
-      scae::launch(conv_fwd_kernel<2>, dim3(Cout / 64, (M + 31) / 32), dim3(NT), 0, st, in,
-                         wf, bias, out, post_bias, out_post, g);
-      break;
-    default:
-      scae::launch(conv_fwd_kernel<1>, dim3(Cout / 32, (M + 31) / 32), dim3(NT), 0, st, in,
-                         wf, bias, out, post_bias, out_post, g);
-  }
+  scae::launch(conv_fwd_pipe_kernel<PipeC2>, dim3(Cout / PipeC2::TB, (M + PipeC2::TA - 1) / PipeC2::TA),
+               dim3(pipe::NT), 0, st, in, wf, bias, out, post_bias, out_post, g);
   return scae_launch_status();
 }
 
@@ -1838,12 +1546,6 @@ extern "C" int scae_conv3x3_fwd_fold_f32(const float *in, const float *wf, const
     return SCAE_ERR_UNSUPPORTED;
   ConvGeom g{B, IH, IW, (IH - 3) / stride + 1, (IW - 3) / stride + 1, Cin, Cout, stride};
   const scae_fold::Plan plan = scae_fold::plan(a.C, a.D);
-  if (fwd_ksplit(g)) {
-    const int M = B * g.OH * g.OW, gx = Cout / dgk::TN, n_conv = gx * ((M + dgk::TM - 1) / dgk::TM);
-    scae::launch(conv_fwd_x6k_fold_kernel, dim3(n_conv + plan.blocks()), dim3(NT), 0,
-                 (hipStream_t)stream, in, wf, bias, out, post_bias, out_post, g, gx, n_conv, a, plan);
-    return scae_launch_status();
-  }
   const int M = B * g.OH * g.OW, gx = Cout / PipeC2::TB,
             n_conv = gx * ((M + PipeC2::TA - 1) / PipeC2::TA);
   scae::launch(conv_fwd_pipe_fold_kernel<PipeC2>, dim3(n_conv + plan.blocks()),
@@ -1864,7 +1566,6 @@ extern "C" int scae_conv3x3_fwd_bf16(const float *in, const float *wf, const flo
 struct DgradLaunch {
   DgradPlan pl;
   int mode, gx, ny;
-  int cfg;   // >= 0: second-generation tile shape (mode / gx / ny then refer to it)
 };
 // (pair = true: the launch also carries the weight-gradient tiles, so the data
 // gradient does not have to fill the chip on its own)
@@ -1896,27 +1597,14 @@ static DgradLaunch plan_dgrad(const ConvGeom &g, bool pair = false, bool bf16 = 
   };
   // rows of the problem: input pixels (class tiles are ragged; close enough to choose)
   if (bf16) {   // mfma_tile.h MODE 3: 128 input pixels x 128 channels
-    d.cfg = -1;
     d.mode = 3;
     d.ny = tiles(128);
     d.gx = g.Cin / 128;
     return d;
   }
-  // (default: first-generation data-gradient tiles, see conv_bwd_pair_mixed_kernel)
-  const char *env = getenv(pair ? "SCAE_K8_PAIR" : "SCAE_K8_DG");
-  d.cfg = env && *env ? pipe_cfg(pair ? "SCAE_K8_PAIR" : "SCAE_K8_DG", (long)g.B * g.IH * g.IW,
-                                 g.Cin)
-                      : -1;
-  if (d.cfg >= 0) {
-    const int ta = (d.cfg == 0 || d.cfg == 3) ? 64 : 32, tb = d.cfg <= 1 ? 128 : 64;
-    d.mode = 0;
-    d.ny = tiles(ta);
-    d.gx = g.Cin / tb;
-    return d;
-  }
   // the DMA-fed exact-split tile (DMODE 4): SCAE_K8_DGX = minimal number of its 64 x 128 tiles
   // for a layer to take it (0 = never)
-  if (!(env && *env) && g.Cin % dgx::TN == 0 && g.Cout % dgx::BKF == 0 &&
+  if (g.Cin % dgx::TN == 0 && g.Cout % dgx::BKF == 0 &&
       (size_t)g.B * g.IH * g.IW * g.Cin * 4 < (1u << 31)) {
     const char *xe = getenv("SCAE_K8_DGX");
     const long min_tiles = xe && *xe ? atol(xe) : SCAE_DGX_MIN_TILES;
@@ -1928,7 +1616,7 @@ static DgradLaunch plan_dgrad(const ConvGeom &g, bool pair = false, bool bf16 = 
   }
   // ... and for the layers below that, the form with the K loop split over the waves (DMODE 5):
   // SCAE_K8_DGK = 1 / 0
-  if (!(env && *env) && g.Cin % dgk::TN == 0 && g.Cout % dgk::BKF == 0 &&
+  if (g.Cin % dgk::TN == 0 && g.Cout % dgk::BKF == 0 &&
       (size_t)g.B * g.IH * g.IW * g.Cin * 4 < (1u << 31)) {
     const char *ke = getenv("SCAE_K8_DGK");
     if (ke && *ke ? atoi(ke) != 0 : SCAE_DGK_DEFAULT != 0) {
@@ -1936,6 +1624,7 @@ static DgradLaunch plan_dgrad(const ConvGeom &g, bool pair = false, bool bf16 = 
       return d;
     }
   }
+  // otherwise the first-generation tiles (DMODE 0 - 2; see conv_bwd_pair_mixed_kernel)
   const long t64 = (long)(g.Cin / 64) * tiles(64), t32 = (long)(g.Cin / 64) * tiles(32);
   d.mode = pair ? (t64 >= SCAE_PAIR_SMALL_TILES ? 0 : (t32 >= SCAE_PAIR_WIDE_MIN ? 2 : 1))
                 : tile_mode(t64, t32, 600);
@@ -1955,29 +1644,9 @@ extern "C" int scae_conv3x3_dgrad_f32(const float *dpre, const float *wd, const 
   const DgradLaunch d = plan_dgrad(g);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(d.gx, d.ny);
-  if (d.cfg >= 0) {
-#define SCAE_DG_PIPE(TT)                                                                   \
-  scae::launch(conv_dgrad_pipe_kernel<TT>, grid, dim3(pipe::NT), 0, st, dpre, wd, gate, \
-                     din, g, d.pl)
-    switch (d.cfg) {
-      case 0: SCAE_DG_PIPE(PipeC0); break;
-      case 1: SCAE_DG_PIPE(PipeC1); break;
-      case 2: SCAE_DG_PIPE(PipeC2); break;
-      default: SCAE_DG_PIPE(PipeC3);
-    }
-#undef SCAE_DG_PIPE
-    return scae_launch_status();
-  }
-  if (d.mode == 4) {
-    const char *ne = getenv("SCAE_K8_DGX_NS");   // (tuning aid: ring depth)
-    const int ns = ne && *ne ? atoi(ne) : 2;
-    if (ns == 1)
-      scae::launch(conv_dgrad_x6_kernel<1>, grid, dim3(NT), 0, st, dpre, wd, gate, din, g, d.pl);
-    else if (ns == 3)
-      scae::launch(conv_dgrad_x6_kernel<3>, grid, dim3(NT), 0, st, dpre, wd, gate, din, g, d.pl);
-    else
-      scae::launch(conv_dgrad_x6_kernel<2>, grid, dim3(NT), 0, st, dpre, wd, gate, din, g, d.pl);
-  } else if (d.mode == 5)
+  if (d.mode == 4)
+    scae::launch(conv_dgrad_x6_kernel<2>, grid, dim3(NT), 0, st, dpre, wd, gate, din, g, d.pl);
+  else if (d.mode == 5)
     scae::launch(conv_dgrad_x6k_kernel, grid, dim3(NT), 0, st, dpre, wd, gate, din, g, d.pl);
   else if (d.mode == 0)
     scae::launch(conv_dgrad_kernel<0>, grid, dim3(NT), 0, st, dpre, wd, gate, din, g, d.pl);
@@ -1999,81 +1668,40 @@ static int conv_bwd_pair_impl(const float *dpre, const float *wd, const float *i
   if (IH > DG_MAXDIM || IW > DG_MAXDIM) return SCAE_ERR_UNSUPPORTED;
   bf16 = bf16 && conv_bf16_shape((long)B * IH * IW, Cin, Cout);
   const DgradLaunch d = plan_dgrad(g, true, bf16);
-  const WgradPlan p = wgrad_plan(B * g.OH * g.OW, Cin, Cout);
-  if (rider) {   // only the mixed form below carries one
-    const char *pe = getenv("SCAE_K8_PAIR");
-    if (bf16 || d.cfg >= 0 || (pe && atoi(pe) < 0)) return SCAE_ERR_UNSUPPORTED;
-  }
+  const int splits = wgrad_splits(B * g.OH * g.OW, Cin, Cout);
+  if (rider && bf16) return SCAE_ERR_UNSUPPORTED;   // only the mixed form below carries one
+  hipStream_t st = (hipStream_t)stream;
   if (bf16) {   // both gradients on bf16 operands, 128 x 128 tiles
     const PairGrid bg{d.gx * d.ny, d.gx, Cin / 128, Cout / 128};
-    scae::launch((conv_bwd_pair_kernel<3, 3>), dim3(bg.nd + bg.wx * bg.wy * 9 * p.splits),
-                       dim3(NT), 0, (hipStream_t)stream, dpre, wd, in, din, in, partial, g, d.pl,
-                       p.splits, bg);
+    scae::launch((conv_bwd_pair_kernel<3, 3>), dim3(bg.nd + bg.wx * bg.wy * 9 * splits), dim3(NT),
+                 0, st, dpre, wd, in, din, in, partial, g, d.pl, splits, bg);
     return scae_launch_status();
   }
-  const int wt = p.small && d.cfg < 0 ? 32 : 64;
-  const PairGrid pg{d.gx * d.ny, d.gx, Cin / wt, Cout / wt};
-  const dim3 grid(pg.nd + pg.wx * pg.wy * 9 * p.splits);
-  hipStream_t st = (hipStream_t)stream;
-  if (d.cfg >= 0) {
-#define SCAE_PAIR_PIPE(TT)                                                                  \
-  scae::launch((conv_bwd_pair_pipe_kernel<TT, PipeW>), grid, dim3(pipe::NT), 0, st,   \
-                     dpre, wd, in, din, in, partial, g, d.pl, p.splits, pg)
-    switch (d.cfg) {
-      case 0: SCAE_PAIR_PIPE(PipeC0); break;
-      case 1: SCAE_PAIR_PIPE(PipeC1); break;
-      case 2: SCAE_PAIR_PIPE(PipeC2); break;
-      default: SCAE_PAIR_PIPE(PipeC3);
-    }
-#undef SCAE_PAIR_PIPE
-    return scae_launch_status();
+  // the data-gradient tiles of d.mode beside second-generation weight-gradient tiles (64 x 64),
+  // whose ring holds 16-pixel chunks for the layers with few output pixels (the K-split
+  // data-gradient tile brings 48 KiB of LDS to the launch anyway: the short ring would buy no
+  // workgroup)
+  const PairGrid pg{d.gx * d.ny, d.gx, Cin / 64, Cout / 64};
+  const dim3 grid(pg.nd + pg.wx * pg.wy * 9 * splits);
+  const bool w16 = d.mode != 5 && (long)B * g.OH * g.OW < SCAE_WGRAD_SHORT_CHUNK_PIXELS;
+#define SCAE_PAIR_MIXED(DM, TW)                                                                  \
+  if (rider)                                                                                    \
+    scae::launch((conv_bwd_pair_mixed_rider_kernel<DM, TW>), dim3(grid.x + rider->n), dim3(NT), \
+                 0, st, dpre, wd, in, din, in, partial, g, d.pl, splits, pg, *rider);           \
+  else                                                                                          \
+    scae::launch((conv_bwd_pair_mixed_kernel<DM, TW>), grid, dim3(NT), 0, st, dpre, wd, in,     \
+                 din, in, partial, g, d.pl, splits, pg)
+#define SCAE_PAIR_RING(DM) \
+  if (w16) { SCAE_PAIR_MIXED(DM, PipeW16); } else { SCAE_PAIR_MIXED(DM, PipeW); }
+  switch (d.mode) {
+    case 0: SCAE_PAIR_RING(0) break;
+    case 2: SCAE_PAIR_RING(2) break;
+    case 4: SCAE_PAIR_RING(4) break;
+    case 5: SCAE_PAIR_MIXED(5, PipeW); break;
+    default: SCAE_PAIR_RING(1)
   }
-  const char *pe = getenv("SCAE_K8_PAIR");
-  if (!(pe && atoi(pe) < 0)) {   // second-generation weight-gradient tiles (64 x 64)
-    const PairGrid mg{d.gx * d.ny, d.gx, Cin / 64, Cout / 64};
-    const dim3 mgrid(mg.nd + mg.wx * mg.wy * 9 * p.splits);
-    const char *we = getenv("SCAE_K8_W16");   // (tuning aid: 0 / 1 forces the ring)
-    // (the K-split data-gradient tile brings 48 KiB of LDS to the launch anyway: the short ring
-    // would buy no workgroup)
-    const bool w16 = we && *we ? atoi(we) != 0
-                               : d.mode != 5 &&
-                                     (long)B * g.OH * g.OW < SCAE_WGRAD_SHORT_CHUNK_PIXELS;
-#define SCAE_PAIR_MIXED(DM, TW)                                                              \
-  scae::launch((conv_bwd_pair_mixed_kernel<DM, TW>), mgrid, dim3(NT), 0, st, dpre, wd, in, \
-                     din, in, partial, g, d.pl, p.splits, mg)
-#define SCAE_PAIR_MIXED_FOLD(DM, TW)                                                          \
-  scae::launch((conv_bwd_pair_mixed_rider_kernel<DM, TW>), rgrid, dim3(NT), 0, st, dpre, wd, \
-                     in, din, in, partial, g, d.pl, p.splits, mg, *rider)
-#define SCAE_PAIR_BY_MODE(LAUNCH, TW) \
-  if (d.mode == 0) LAUNCH(0, TW);     \
-  else if (d.mode == 2) LAUNCH(2, TW); \
-  else if (d.mode == 4) LAUNCH(4, TW); \
-  else if (d.mode == 5) LAUNCH(5, TW); \
-  else LAUNCH(1, TW)
-    if (rider) {
-      const dim3 rgrid(mgrid.x + rider->n);
-      if (w16) { SCAE_PAIR_BY_MODE(SCAE_PAIR_MIXED_FOLD, PipeW16); }
-      else { SCAE_PAIR_BY_MODE(SCAE_PAIR_MIXED_FOLD, PipeW); }
-      return scae_launch_status();
-    }
-    if (w16) { SCAE_PAIR_BY_MODE(SCAE_PAIR_MIXED, PipeW16); }
-    else { SCAE_PAIR_BY_MODE(SCAE_PAIR_MIXED, PipeW); }
-#undef SCAE_PAIR_BY_MODE
-#undef SCAE_PAIR_MIXED_FOLD
+#undef SCAE_PAIR_RING
 #undef SCAE_PAIR_MIXED
-    return scae_launch_status();
-  }
-#define SCAE_PAIR(DM, WS)                                                                     \
-  scae::launch((conv_bwd_pair_kernel<DM, WS>), grid, dim3(NT), 0, st, dpre, wd, in, din, \
-                     in, partial, g, d.pl, p.splits, pg)
-  if (d.mode == 0) {
-    if (p.small) SCAE_PAIR(0, true); else SCAE_PAIR(0, false);
-  } else if (d.mode == 2) {
-    if (p.small) SCAE_PAIR(2, true); else SCAE_PAIR(2, false);
-  } else {
-    if (p.small) SCAE_PAIR(1, true); else SCAE_PAIR(1, false);
-  }
-#undef SCAE_PAIR
   return scae_launch_status();
 }
 
@@ -2136,119 +1764,10 @@ extern "C" int scae_debug_fwd_prof(unsigned long long *out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fwd_prof), sizeof(g_fwd_prof));
 }
 #endif
-#ifdef SCAE_CONV_MULTI_PROBE
-// Upper-bound probe (tools/conv_multi_probe.py): the tiles of up to 3 layers in ONE launch
-// WITHOUT dependencies between them (every layer reads buffers that already exist) -- what a
-// dependency-tracking multi-layer launch could gain at most over one launch per layer.
-namespace {
-struct MultiFwd {
-  const float *in[3], *wf[3], *bias[3];
-  float *out[3];
-  ConvGeom g[3];
-  int start[4], gx[3];
-};
-template <class T>
-__global__ __launch_bounds__(pipe::NT) void conv_fwd_multi_probe_kernel(MultiFwd a) {
-  __shared__ __attribute__((aligned(1024))) float smem[T::SMEM];
-  const int b = blockIdx.x;
-  const int l = b >= a.start[2] ? 2 : (b >= a.start[1] ? 1 : 0);
-  const int t = b - a.start[l];
-  fwd_pipe_tile<T>(smem, t % a.gx[l], t / a.gx[l], a.in[l], a.wf[l], a.bias[l], a.out[l], nullptr,
-                   nullptr, a.g[l]);
-}
-struct MultiBwd {
-  const float *dpre[3], *wd[3], *gate[3], *in[3];
-  float *din[3], *partial[3];
-  ConvGeom g[3];
-  DgradPlan pl[3];
-  int splits[3], mode[3];
-  PairGrid pg[3];
-  int start[4];
-};
-__global__ __launch_bounds__(NT) void conv_bwd_multi_probe_kernel(const MultiBwd *ap) {
-  constexpr int SM = Tile<0>::SMEM > PipeW::SMEM ? Tile<0>::SMEM : PipeW::SMEM;
-  __shared__ __attribute__((aligned(1024))) float smem[SM];
-  const MultiBwd &a = *ap;
-  const int b = blockIdx.x;
-  const int l = b >= a.start[2] ? 2 : (b >= a.start[1] ? 1 : 0);
-  const int bid = b - a.start[l];
-  const PairGrid pg = a.pg[l];
-  if (bid < pg.nd) {
-    if (a.mode[l] == 0)
-      dgrad_tile<0>(smem, bid % pg.gx, bid / pg.gx, a.dpre[l], a.wd[l], a.gate[l], a.din[l], a.g[l], a.pl[l]);
-    else if (a.mode[l] == 2)
-      dgrad_tile<2>(smem, bid % pg.gx, bid / pg.gx, a.dpre[l], a.wd[l], a.gate[l], a.din[l], a.g[l], a.pl[l]);
-    else if (a.mode[l] == 5)
-      dgrad_any_tile<5, SM>(smem, bid % pg.gx, bid / pg.gx, a.dpre[l], a.wd[l], a.gate[l], a.din[l], a.g[l], a.pl[l]);
-    else if (a.mode[l] == 4)
-      dgrad_any_tile<4, SM>(smem, bid % pg.gx, bid / pg.gx, a.dpre[l], a.wd[l], a.gate[l], a.din[l], a.g[l], a.pl[l]);
-    else
-      dgrad_tile<1>(smem, bid % pg.gx, bid / pg.gx, a.dpre[l], a.wd[l], a.gate[l], a.din[l], a.g[l], a.pl[l]);
-  } else {
-    const int w = bid - pg.nd, bx = w % pg.wx, t = w / pg.wx;
-    wgrad_pipe_tile<PipeW>(smem, bx, t % pg.wy, t / pg.wy, a.dpre[l], a.in[l], a.partial[l], a.g[l],
-                           a.splits[l]);
-  }
-}
-}  // namespace
-extern "C" int scae_debug_conv_fwd_multi(int n, const float *const *in, const float *const *wf,
-                                         const float *const *bias, float *const *out, const int *B,
-                                         const int *IH, const int *Cin, const int *Cout,
-                                         const int *stride, void *stream) {
-  MultiFwd a{};
-  int tot = 0;
-  for (int l = 0; l < 3; ++l) {
-    const int k = l < n ? l : n - 1;
-    a.in[l] = in[k], a.wf[l] = wf[k], a.bias[l] = bias[k], a.out[l] = out[k];
-    a.g[l] = ConvGeom{B[k], IH[k], IH[k], (IH[k] - 3) / stride[k] + 1, (IH[k] - 3) / stride[k] + 1,
-                      Cin[k], Cout[k], stride[k]};
-    a.gx[l] = Cout[k] / PipeC2::TB;
-    a.start[l] = tot;
-    if (l < n) tot += a.gx[l] * ((B[k] * a.g[l].OH * a.g[l].OW + PipeC2::TA - 1) / PipeC2::TA);
-  }
-  a.start[3] = tot;
-  for (int l = n; l < 3; ++l) a.start[l] = tot;
-  scae::launch(conv_fwd_multi_probe_kernel<PipeC2>, dim3(tot), dim3(pipe::NT), 0,
-                     (hipStream_t)stream, a);
-  return scae_launch_status();
-}
-// `scratch`: device memory for the argument block (sizeof(MultiBwd) bytes, >= 8 KiB given)
-extern "C" int scae_debug_conv_bwd_multi(int n, const float *const *dpre, const float *const *wd,
-                                         const float *const *in, float *const *din,
-                                         float *const *partial, const int *B, const int *IH,
-                                         const int *Cin, const int *Cout, const int *stride,
-                                         void *scratch, void *stream) {
-  static MultiBwd a;
-  a = MultiBwd{};
-  int tot = 0;
-  for (int l = 0; l < 3; ++l) {
-    const int k = l < n ? l : n - 1;
-    a.dpre[l] = dpre[k], a.wd[l] = wd[k], a.gate[l] = in[k], a.in[l] = in[k], a.din[l] = din[k],
-    a.partial[l] = partial[k];
-    ConvGeom g{B[k], IH[k], IH[k], (IH[k] - 3) / stride[k] + 1, (IH[k] - 3) / stride[k] + 1,
-               Cin[k], Cout[k], stride[k]};
-    a.g[l] = g;
-    const DgradLaunch d = plan_dgrad(g, true, false);
-    const WgradPlan p = wgrad_plan(B[k] * g.OH * g.OW, Cin[k], Cout[k]);
-    a.pl[l] = d.pl, a.mode[l] = d.mode, a.splits[l] = p.splits;
-    a.pg[l] = PairGrid{d.gx * d.ny, d.gx, Cin[k] / 64, Cout[k] / 64};
-    a.start[l] = tot;
-    if (l < n) tot += a.pg[l].nd + a.pg[l].wx * a.pg[l].wy * 9 * p.splits;
-  }
-  a.start[3] = tot;
-  for (int l = n; l < 3; ++l) a.start[l] = tot;
-  hipError_t e = hipMemcpyAsync(scratch, &a, sizeof(a), hipMemcpyHostToDevice, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  scae::launch(conv_bwd_multi_probe_kernel, dim3(tot), dim3(NT), 0, (hipStream_t)stream,
-                     (const MultiBwd *)scratch);
-  return scae_launch_status();
-}
-extern "C" int scae_debug_conv_bwd_multi_bytes(void) { return (int)sizeof(MultiBwd); }
-#endif
 
 extern "C" int scae_conv3x3_wgrad_splits(int B, int OH, int OW, int Cin, int Cout) {
   if (B <= 0 || OH <= 0 || OW <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  return wgrad_plan(B * OH * OW, Cin, Cout).splits;
+  return wgrad_splits(B * OH * OW, Cin, Cout);
 }
 
 extern "C" int scae_conv3x3_wgrad_f32(const float *dpre, const float *in, float *partial,
@@ -2258,21 +1777,13 @@ extern "C" int scae_conv3x3_wgrad_f32(const float *dpre, const float *in, float 
   int rc = check_geom(g, true);
   if (rc) return rc;
   SCAE_REQUIRE(dpre && in && partial);
-  const WgradPlan p = wgrad_plan(B * g.OH * g.OW, Cin, Cout);
-  const char *e = getenv("SCAE_K8_WG");
-  if (!(e && atoi(e) < 0))
-    scae::launch(conv_wgrad_pipe_kernel<PipeW>, dim3(Cin / 64, Cout / 64, 9 * p.splits),
-                       dim3(pipe::NT), 0, (hipStream_t)stream, dpre, in, partial, g, p.splits);
-  else if (p.small)
-    scae::launch(conv_wgrad_kernel<true>, dim3(Cin / 32, Cout / 32, 9 * p.splits), dim3(NT),
-                       0, (hipStream_t)stream, dpre, in, partial, g, p.splits);
-  else
-    scae::launch(conv_wgrad_kernel<false>, dim3(Cin / 64, Cout / 64, 9 * p.splits),
-                       dim3(NT), 0, (hipStream_t)stream, dpre, in, partial, g, p.splits);
+  const int splits = wgrad_splits(B * g.OH * g.OW, Cin, Cout);
+  scae::launch(conv_wgrad_pipe_kernel<PipeW>, dim3(Cin / 64, Cout / 64, 9 * splits), dim3(pipe::NT),
+               0, (hipStream_t)stream, dpre, in, partial, g, splits);
   if (dw) {  // else: the caller reduces later (scae_conv3x3_wgrad_reduce_batch_f32)
     const int n = 9 * Cout * Cin + Cout;
     scae::launch(reduce_wgrad_kernel, dim3((n + 255) / 256), dim3(256), 0,
-                       (hipStream_t)stream, partial, dw, db, Cout, Cin, p.splits);
+                       (hipStream_t)stream, partial, dw, db, Cout, Cin, splits);
   }
   return scae_launch_status();
 }

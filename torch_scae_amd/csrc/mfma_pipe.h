@@ -1,6 +1,6 @@
 // fp32 MFMA tile pipeline, second generation (K8 implicit-GEMM convolutions):
-//   * v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulate; half the LDS
-//     operand bytes per flop of the 16x16x4 form);
+//   * fp32 operands split exactly into three bf16 parts, six v_mfma_f32_32x32x16_bf16 per
+//     16 k (bf16x6.h): fp32 products at 6 / 16 of the fp32 MFMA time, fp32 accumulate;
 //   * operands go global -> LDS directly (global_load_lds_dwordx4, 1 KiB per wave
 //     instruction) into a ring of NS stages: the loads of chunks c+1 .. c+NS-1 are in
 //     flight while chunk c is multiplied; ONE s_barrier per 32-wide K chunk, counted
@@ -22,13 +22,6 @@
 
 #include "bf16x6.h"
 #include "common.h"
-
-// The products of the second-generation loops: exact three-way bf16 split, six bf16 MFMAs per
-// 16 k (bf16x6.h) -- fp32 results at 6 / 16 of the fp32 MFMA time; -DSCAE_PIPE_X6=0: the
-// fp32 MFMA chain (v_mfma_f32_32x32x2_f32), for A/B builds.
-#ifndef SCAE_PIPE_X6
-#define SCAE_PIPE_X6 1
-#endif
 
 namespace scae_pipe {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -149,15 +142,14 @@ template <class T, class Chunk, class Issue>
 __device__ __forceinline__ void kk_mainloop(int nchunk, float *smem, f32x16 (&acc)[T::MI][T::NI],
                                             int wn, int ks, int i, int kk, Chunk chunk,
                                             Issue issue) {
-#ifndef SCAE_PIPE_ABL
+#ifndef SCAE_PIPE_ABL   // ablation builds: 1 = no DMA after the ring prologue, 2 = no MFMAs
 #define SCAE_PIPE_ABL 0
 #endif
-  // X6 (where a wave has an even number of 4-k groups per chunk): a group is a PAIR of quads --
-  // the lane's eight k of one bf16 MFMA -- and its products the six exact partial products of
-  // bf16x6.h, the five small ones into an accumulator of their own
-  constexpr bool X6 = SCAE_PIPE_X6 != 0 && (4 / T::KS) % 2 == 0;
-  constexpr int NS = T::NS, QG = X6 ? 2 : 1, G = 4 / T::KS / QG;
-  constexpr int NM = (X6 ? 6 : 4) * T::MI * T::NI;
+  // a group is a PAIR of quads -- the lane's eight k of one bf16 MFMA -- and its products the six
+  // exact partial products of bf16x6.h, the five small ones into an accumulator of their own
+  static_assert((4 / T::KS) % 2 == 0, "an even number of 4-k groups per wave and chunk");
+  constexpr int NS = T::NS, QG = 2, G = 4 / T::KS / QG;
+  constexpr int NM = 6 * T::MI * T::NI;
   const int sw = (i >> 2) & 3;
   const int aoff = kk * T::TA * BKH + i * BKH;
   const int boff = T::TA * BK + (kk * T::TB + wn * 32 * T::NI + i) * BKH;
@@ -172,15 +164,13 @@ __device__ __forceinline__ void kk_mainloop(int nchunk, float *smem, f32x16 (&ac
       for (int ni = 0; ni < T::NI; ++ni) b[buf][h][ni] = lds4(st + boff + ni * 32 * BKH + qo);
     }
   };
-  f32x16 accl[X6 ? T::MI : 1][X6 ? T::NI : 1];
-  if (X6) {
+  f32x16 accl[T::MI][T::NI];
 #pragma unroll
-    for (int mi = 0; mi < T::MI; ++mi)
+  for (int mi = 0; mi < T::MI; ++mi)
 #pragma unroll
-      for (int ni = 0; ni < T::NI; ++ni)
+    for (int ni = 0; ni < T::NI; ++ni)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) accl[mi][ni][e] = 0.f;
-  }
+      for (int e = 0; e < 16; ++e) accl[mi][ni][e] = 0.f;
 #pragma unroll
   for (int c = 0; c < NS; ++c)
     if (c < nchunk) {
@@ -215,37 +205,27 @@ __device__ __forceinline__ void kk_mainloop(int nchunk, float *smem, f32x16 (&ac
         load(stn, 0, cur ^ 1);
       }
       const bool dma_here = gg + 1 == G && more;
-      scae_x6::Split3 as[X6 ? T::MI : 1], bs[X6 ? T::NI : 1];
-      if (X6) {
+      scae_x6::Split3 as[T::MI], bs[T::NI];
 #pragma unroll
-        for (int mi = 0; mi < T::MI; ++mi) as[mi] = scae_x6::split3(a[cur][0][mi], a[cur][QG - 1][mi]);
+      for (int mi = 0; mi < T::MI; ++mi) as[mi] = scae_x6::split3(a[cur][0][mi], a[cur][1][mi]);
 #pragma unroll
-        for (int ni = 0; ni < T::NI; ++ni) bs[ni] = scae_x6::split3(b[cur][0][ni], b[cur][QG - 1][ni]);
-      }
+      for (int ni = 0; ni < T::NI; ++ni) bs[ni] = scae_x6::split3(b[cur][0][ni], b[cur][1][ni]);
 #pragma unroll
       for (int m = 0; m < NM; ++m) {
-        if (X6) {
-          // product by product over the wave's tiles (m / tiles: hi lo, lo hi, mid mid, hi mid,
-          // mid hi -> the small accumulator; hi hi -> the tile's)
-          constexpr int NTL = T::MI * T::NI;
-          const int pr = m / NTL, mi = (m % NTL) / T::NI, ni = (m % NTL) % T::NI;
-          const bf16x8 av = pr == 1 ? as[mi].lo : (pr == 2 || pr == 4) ? as[mi].mid : as[mi].hi;
-          const bf16x8 bv = pr == 0 ? bs[ni].lo : (pr == 2 || pr == 3) ? bs[ni].mid : bs[ni].hi;
-          if (pr < 5)
-            accl[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, accl[mi][ni], 0, 0, 0);
-          else
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[mi][ni], 0, 0, 0);
-        } else {
-          const int mi = (m >> 2) / T::NI, ni = (m >> 2) % T::NI, e = m & 3;
+        // product by product over the wave's tiles (m / tiles: hi lo, lo hi, mid mid, hi mid,
+        // mid hi -> the small accumulator; hi hi -> the tile's)
+        constexpr int NTL = T::MI * T::NI;
+        const int pr = m / NTL, mi = (m % NTL) / T::NI, ni = (m % NTL) % T::NI;
+        const bf16x8 av = pr == 1 ? as[mi].lo : (pr == 2 || pr == 4) ? as[mi].mid : as[mi].hi;
+        const bf16x8 bv = pr == 0 ? bs[ni].lo : (pr == 2 || pr == 3) ? bs[ni].mid : bs[ni].hi;
 #if SCAE_PIPE_ABL == 2
-          acc[mi][ni][0] += a[cur][0][mi][e] * b[cur][0][ni][e];
+        acc[mi][ni][0] += (float)av[m & 7] * (float)bv[m & 7];
 #else
-          const float4 &aq = a[cur][0][mi], &bq = b[cur][0][ni];
-          const float av = e == 0 ? aq.x : e == 1 ? aq.y : e == 2 ? aq.z : aq.w;
-          const float bv = e == 0 ? bq.x : e == 1 ? bq.y : e == 2 ? bq.z : bq.w;
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[mi][ni], 0, 0, 0);
+        if (pr < 5)
+          accl[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, accl[mi][ni], 0, 0, 0);
+        else
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[mi][ni], 0, 0, 0);
 #endif
-        }
         if (dma_here && m + 1 < NM) {   // pieces spread over the NM - 1 gaps between the MFMAs
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -267,12 +247,10 @@ __device__ __forceinline__ void kk_mainloop(int nchunk, float *smem, f32x16 (&ac
   };
   for (int c = 0; c + 1 < nchunk; ++c) body(c, std::false_type{});
   body(nchunk - 1, std::true_type{});
-  if (X6) {
 #pragma unroll
-    for (int mi = 0; mi < T::MI; ++mi)
+  for (int mi = 0; mi < T::MI; ++mi)
 #pragma unroll
-      for (int ni = 0; ni < T::NI; ++ni) acc[mi][ni] += accl[mi][ni];
-  }
+    for (int ni = 0; ni < T::NI; ++ni) acc[mi][ni] += accl[mi][ni];
 }
 
 // Accumulators out: epi(row, col, value) per element (row-major C, 32 consecutive
@@ -346,9 +324,8 @@ struct SS {
 template <class T, class Issue, class Each>
 __device__ __forceinline__ void ss_mainloop(int nchunk, float *smem, f32x16 (&acc)[T::MI][T::NI],
                                             int wm, int wn, int i, int kk, Issue issue, Each each) {
-  constexpr bool X6 = SCAE_PIPE_X6 != 0;
-  // a batch = the lane's U k of each fragment: 4 fp32 MFMA steps, or (X6) the 8 k of one bf16 MFMA
-  constexpr int LA = T::NS - 1, S = T::BKW / 2, U = X6 ? 8 : 4, NB = S / U;
+  // a batch = the lane's U k of each fragment: the 8 k of one bf16 MFMA
+  constexpr int LA = T::NS - 1, S = T::BKW / 2, U = 8, NB = S / U;
   static_assert(NB >= 1 && S % U == 0 && T::PPW % NB == 0, "fragment batches per chunk");
   const int aoff = kk * T::TA + wm * 32 * T::MI + i;
   const int boff = T::TA * T::BKW + kk * T::TB + wn * 32 * T::NI + i;
@@ -363,22 +340,20 @@ __device__ __forceinline__ void ss_mainloop(int nchunk, float *smem, f32x16 (&ac
       for (int ni = 0; ni < T::NI; ++ni) b[buf][u][ni] = st[boff + 2 * s * T::TB + ni * 32];
     }
   };
-  // X6: the small products' accumulator
+  // the small products' accumulator
   // (one: in the launch these tiles share with the data gradient's, the registers of two more
   // accumulators cost a workgroup per CU -- B = 128, the three pair launches: 145 us with one,
   // 159 with two or three, 152 on the fp32 MFMA chain)
   constexpr int NSM = 1;
-  f32x16 accl[X6 ? T::MI : 1][X6 ? T::NI : 1][NSM];
-  if (X6) {
+  f32x16 accl[T::MI][T::NI][NSM];
 #pragma unroll
-    for (int mi = 0; mi < T::MI; ++mi)
+  for (int mi = 0; mi < T::MI; ++mi)
 #pragma unroll
-      for (int ni = 0; ni < T::NI; ++ni)
+    for (int ni = 0; ni < T::NI; ++ni)
 #pragma unroll
-        for (int n = 0; n < NSM; ++n)
+      for (int n = 0; n < NSM; ++n)
 #pragma unroll
-          for (int e = 0; e < 16; ++e) accl[mi][ni][n][e] = 0.f;
-  }
+        for (int e = 0; e < 16; ++e) accl[mi][ni][n][e] = 0.f;
 #pragma unroll
   for (int c = 0; c < LA; ++c)
     if (c < nchunk) {
@@ -412,46 +387,35 @@ __device__ __forceinline__ void ss_mainloop(int nchunk, float *smem, f32x16 (&ac
         wg_barrier();
         load(smem + sn * T::STAGE, 0, cur ^ 1);
       }
-      if (X6) {
-        scae_x6::Split3 as[T::MI], bs[T::NI];
+      scae_x6::Split3 as[T::MI], bs[T::NI];
 #pragma unroll
-        for (int mi = 0; mi < T::MI; ++mi) {
-          const float x[8] = {a[cur][0][mi], a[cur][1][mi], a[cur][2][mi], a[cur][3][mi],
-                              a[cur][4 % U][mi], a[cur][5 % U][mi], a[cur][6 % U][mi], a[cur][7 % U][mi]};
-          as[mi] = scae_x6::split3(x);
-        }
+      for (int mi = 0; mi < T::MI; ++mi) {
+        const float x[8] = {a[cur][0][mi], a[cur][1][mi], a[cur][2][mi], a[cur][3][mi],
+                            a[cur][4][mi], a[cur][5][mi], a[cur][6][mi], a[cur][7][mi]};
+        as[mi] = scae_x6::split3(x);
+      }
 #pragma unroll
-        for (int ni = 0; ni < T::NI; ++ni) {
-          const float x[8] = {b[cur][0][ni], b[cur][1][ni], b[cur][2][ni], b[cur][3][ni],
-                              b[cur][4 % U][ni], b[cur][5 % U][ni], b[cur][6 % U][ni], b[cur][7 % U][ni]};
-          bs[ni] = scae_x6::split3(x);
-        }
+      for (int ni = 0; ni < T::NI; ++ni) {
+        const float x[8] = {b[cur][0][ni], b[cur][1][ni], b[cur][2][ni], b[cur][3][ni],
+                            b[cur][4][ni], b[cur][5][ni], b[cur][6][ni], b[cur][7][ni]};
+        bs[ni] = scae_x6::split3(x);
+      }
 #define SCAE_SS_STEP(AP, BP, N)                                                                   \
   _Pragma("unroll") for (int mi = 0; mi < T::MI; ++mi)                                            \
   _Pragma("unroll") for (int ni = 0; ni < T::NI; ++ni) accl[mi][ni][(N) % NSM] =                  \
-      __builtin_amdgcn_mfma_f32_32x32x16_bf16(as[mi].AP, bs[ni].BP, accl[mi][ni][(N) % NSM], 0, 0, 0);
-        SCAE_SS_STEP(hi, lo, 0)
-        SCAE_SS_STEP(lo, hi, 1)
-        SCAE_SS_STEP(mid, mid, 2)
-        SCAE_SS_STEP(hi, mid, 0)
-        SCAE_SS_STEP(mid, hi, 1)
+    __builtin_amdgcn_mfma_f32_32x32x16_bf16(as[mi].AP, bs[ni].BP, accl[mi][ni][(N) % NSM], 0, 0, 0);
+      SCAE_SS_STEP(hi, lo, 0)
+      SCAE_SS_STEP(lo, hi, 1)
+      SCAE_SS_STEP(mid, mid, 2)
+      SCAE_SS_STEP(hi, mid, 0)
+      SCAE_SS_STEP(mid, hi, 1)
 #undef SCAE_SS_STEP
 #pragma unroll
-        for (int mi = 0; mi < T::MI; ++mi)
+      for (int mi = 0; mi < T::MI; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < T::NI; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as[mi].hi, bs[ni].hi, acc[mi][ni],
-                                                                  0, 0, 0);
-      } else {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-          for (int mi = 0; mi < T::MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < T::NI; ++ni)
-              acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][u][mi], b[cur][u][ni],
-                                                                acc[mi][ni], 0, 0, 0);
-      }
+        for (int ni = 0; ni < T::NI; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as[mi].hi, bs[ni].hi, acc[mi][ni],
+                                                                0, 0, 0);
       if (more) {
 #pragma unroll
         for (int j = blk * (T::PPW / NB); j < (blk + 1) * (T::PPW / NB); ++j) issue(c + LA, s2, j);
@@ -470,17 +434,15 @@ __device__ __forceinline__ void ss_mainloop(int nchunk, float *smem, f32x16 (&ac
   };
   for (int c = 0; c + 1 < nchunk; ++c) body(c, std::false_type{});
   body(nchunk - 1, std::true_type{});
-  if (X6) {
 #pragma unroll
-    for (int mi = 0; mi < T::MI; ++mi)
+  for (int mi = 0; mi < T::MI; ++mi)
 #pragma unroll
-      for (int ni = 0; ni < T::NI; ++ni) {
-        f32x16 small = accl[mi][ni][0];
+    for (int ni = 0; ni < T::NI; ++ni) {
+      f32x16 small = accl[mi][ni][0];
 #pragma unroll
-        for (int n = 1; n < NSM; ++n) small += accl[mi][ni][n];
-        acc[mi][ni] += small;
-      }
-  }
+      for (int n = 1; n < NSM; ++n) small += accl[mi][ni][n];
+      acc[mi][ni] += small;
+    }
 }
 
 }  // namespace scae_pipe
