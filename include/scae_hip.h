@@ -1097,6 +1097,35 @@ int scae_class_probs_f32(const float *caps_presence, const float *posterior, con
  *   caller; the forward leaves the per-image / per-column statistics there and
  *   the backward of the same inputs reads them.
  * ---------------------------------------------------------------------- */
+/* The training log: a nullable descriptor that makes the loss tail's batch combine (wherever
+ * it runs: the deferred workgroup of scae_loss_tail_bwd_f32 or the standalone combine) end in
+ * an epilogue -- the replayed step's `log` of BaseExperiment.training_step
+ * (base_experiment.py:109-126) with no launch of its own.  The epilogue
+ *   - forms both heads' accuracies from prior_prob / post_prob (B, ncls), which
+ *     scae_loss_tail_fwd_class_probs_f32 wrote in the same batch, as the evaluation epilogue
+ *     does (torch.argmax: first maximal index, NaN maximal; count / B in fp32; zero without a
+ *     label; the batch value is the max of the two heads);
+ *   - writes one row of SCAE_TRAIN_LOG_ROW floats at rows + (step[0] % capacity) * ROW:
+ *       [0] loss  [1] accuracy  [2] prior accuracy  [3] posterior accuracy
+ *       [4 + i] out12[i], i < 12  [16] learning rate (lr[0]; NaN when lr is NULL)
+ *       [17] mse  [18] part-capsule L1 (scae_train_log_f32's extra2 only; else zero);
+ *   - advances the device step counter step[0] by one (ONE thread, in stream order: a captured
+ *     launch follows the count, as the optimisers' step count does);
+ *   - adds the batch into acc (nullable), laid out as SCAE_EVAL_ACC_DOUBLES, in stream order
+ *     with one writer per entry and no atomics: the sums are reproducible bit for bit.
+ * The descriptor itself is host memory, read when the launch is issued; the pointers in it
+ * are device memory. */
+#define SCAE_TRAIN_LOG_ROW 19
+typedef struct scae_train_log_desc {
+  float *rows;      /* (capacity, SCAE_TRAIN_LOG_ROW) ring */
+  int64_t *step;    /* (1) rows written so far */
+  int capacity;
+  double *acc;      /* nullable: SCAE_EVAL_ACC_DOUBLES epoch accumulator */
+  const float *prior_prob, *post_prob;  /* (B, ncls); unused without a label */
+  const int64_t *label;                 /* (B) nullable: no accuracies */
+  int ncls;
+  const float *lr;  /* nullable: the learning rate the optimiser reads in this step */
+} scae_train_log_desc;
 typedef struct scae_loss_extras {
   const float *rec_sums;
   int n_rec;
@@ -1113,6 +1142,9 @@ typedef struct scae_loss_extras {
    * deferred forward that no backward followed. */
   int defer_combine;
   float *out12;
+  /* nullable: the training log's epilogue after the combine (scae_train_log_desc); ignored by
+   * the evaluation epilogue and by a forward whose combine is deferred */
+  const scae_train_log_desc *train_log;
 } scae_loss_extras;
 int scae_loss_tail_supported(int B, int O, int ncls);
 int64_t scae_loss_tail_workspace_floats(int B, int O, int ncls);
@@ -1186,6 +1218,12 @@ int scae_eval_tail_f32(const float *lpp, const float *posterior, const float *ca
 int scae_eval_accumulate_f32(const float *loss, const float *out12, const float *prior_prob,
                              const float *post_prob, const int64_t *label, int B, int ncls,
                              double *acc, float *batch3, void *stream);
+/* The training log's epilogue alone (scae_train_log_desc, B images), for a loss other launches
+ * computed (a model outside the fused tail, or a step whose plan holds no class probabilities):
+ * loss (1), out12 (12, nullable: zeros), extra2 (2, nullable: zeros) = {mse, part-capsule L1}.
+ * One workgroup. */
+int scae_train_log_f32(const float *loss, const float *out12, const float *extra2,
+                       const scae_train_log_desc *log, int B, void *stream);
 
 /* ------------------------------------------------------------------------
  * K1  template render + Gaussian-mixture image likelihood

@@ -100,12 +100,19 @@ class ScaledSum(Structure):
     _fields_ = [("src", P), ("n", c_int64), ("scale", c_float), ("dst", P)]
 
 
+class TrainLogDesc(Structure):
+    """struct scae_train_log_desc"""
+    _fields_ = [("rows", P), ("step", P), ("capacity", c_int), ("acc", P),
+                ("prior_prob", P), ("post_prob", P), ("label", P), ("ncls", c_int),
+                ("lr", P)]
+
+
 class LossExtras(Structure):
     """struct scae_loss_extras"""
     _fields_ = [("rec_sums", P), ("n_rec", c_int), ("reg", P),
                 ("w_reg", c_float), ("g_rec_sums", P), ("g_reg", P),
                 ("loss", P), ("g_loss", P), ("defer_combine", c_int),
-                ("out12", P)]
+                ("out12", P), ("train_log", POINTER(TrainLogDesc))]
 
 
 class SeedFoldDesc(Structure):
@@ -316,6 +323,7 @@ SIGNATURES = {
     "scae_eval_tail_f32": [P] * 6 + [POINTER(LossExtras), P, P] + [c_int] * 8
     + [POINTER(c_float), c_float] + [P] * 5,
     "scae_eval_accumulate_f32": [P] * 5 + [c_int] * 2 + [P] * 3,
+    "scae_train_log_f32": [P] * 3 + [POINTER(TrainLogDesc), c_int, P],
     "scae_template_render_fwd_f32": [POINTER(DecoderDesc), P, P, P],
     "scae_render_gmm_logprob_fwd_f32": [POINTER(DecoderDesc), P, P, P, P, P],
     "scae_render_gmm_bwd_f32": [POINTER(DecoderDesc)] + [P] * 12 + [P],
@@ -335,6 +343,7 @@ _RESTYPES = {"scae_error_string": c_char_p,
              "scae_launch_list_begin": P,
              "scae_launch_list_free": None}
 EVAL_ACC_DOUBLES = 17        # SCAE_EVAL_ACC_DOUBLES: the accumulator of scae_eval_*
+TRAIN_LOG_ROW = 19           # SCAE_TRAIN_LOG_ROW: one row of scae_train_log_desc's ring
 FLAT_OPT_STATE_INTS = 2112   # SCAE_FLAT_OPT_STATE_INTS: the step_state of scae_flat_opt_*
 ABI_VERSION = 2     # SCAE_ABI_VERSION of the include/scae_hip.h this binding mirrors
 

@@ -10,6 +10,9 @@
 //   (c) the batch added into a device-resident fp64 accumulator by ONE thread, in
 //       stream order: no atomics, so N replays give the same epoch sums bit for bit.
 // scae_eval_accumulate_f32 is (b) + (c) alone, for a loss computed by other launches.
+// The training log (scae_train_log_desc) shares (b) and (c) (loss_tail_dev.h); its epilogue
+// rides in the training step's combine workgroup (loss_tail.hip), and scae_train_log_f32
+// below is that epilogue alone, for a loss computed by other launches.
 #include "common.h"
 #include "loss_tail_dev.h"
 
@@ -24,57 +27,21 @@ struct EvalArgs {
   float *batch3;   // nullable: this batch's {best, prior, posterior} accuracy
 };
 
-// torch.argmax over one row: the first maximal index; the first NaN wins
-__device__ __forceinline__ int row_argmax(const float *p, int n) {
-  float v = p[0];
-  if (v != v) return 0;
-  int best = 0;
-  for (int c = 1; c < n; ++c) {
-    const float x = p[c];
-    if (x != x) return c;
-    if (x > v) v = x, best = c;
-  }
-  return best;
-}
-
 // the two heads' correct counts, complete in thread 0 (all threads must call: barrier)
 template <int NT>
 __device__ __forceinline__ void accuracy_counts(const EvalArgs &e, float &n_prior,
                                                 float &n_post) {
-  __shared__ float red[2][NT / 64];
-  float cp = 0.f, cq = 0.f;  // (integers: exact in fp32 up to 2^24 images)
-  if (e.label && e.ncls > 0) {
-    for (int b = threadIdx.x; b < e.B; b += NT) {
-      const int64_t l = e.label[b];
-      cp += row_argmax(e.prior_prob + (size_t)b * e.ncls, e.ncls) == l ? 1.f : 0.f;
-      cq += row_argmax(e.post_prob + (size_t)b * e.ncls, e.ncls) == l ? 1.f : 0.f;
-    }
-  }
-  cp = scae::wave_sum(cp);
-  cq = scae::wave_sum(cq);
-  const int w = threadIdx.x / 64;
-  if ((threadIdx.x & 63) == 0) red[0][w] = cp, red[1][w] = cq;
-  __syncthreads();
-  n_prior = n_post = 0.f;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < NT / 64; ++i) n_prior += red[0][i], n_post += red[1][i];
+  scae_tail::accuracy_counts<NT>(e.prior_prob, e.post_prob, e.label, e.B, e.ncls, n_prior,
+                                 n_post);
 }
 
 // thread 0: the batch into the accumulator
 __device__ __forceinline__ void accumulate(const EvalArgs &e, float loss, const float *out12,
                                            float n_prior, float n_post) {
-  float pa = 0.f, qa = 0.f;
-  if (e.label && e.ncls > 0) pa = n_prior / (float)e.B, qa = n_post / (float)e.B;
-  const float best = qa > pa ? qa : pa;
-  double *A = e.acc;
-  A[0] += 1.0;
-  A[1] += (double)loss;
-  A[2] += (double)best;
-  A[3] += (double)pa;
-  A[4] += (double)qa;
-  if (out12)
-    for (int i = 0; i < 12; ++i) A[5 + i] += (double)out12[i];
-  if (e.batch3) e.batch3[0] = best, e.batch3[1] = pa, e.batch3[2] = qa;
+  float acc3[3];
+  batch_accuracies(e.label && e.ncls > 0, e.B, n_prior, n_post, acc3);
+  accumulate_batch(e.acc, loss, out12, acc3);
+  if (e.batch3) e.batch3[0] = acc3[0], e.batch3[1] = acc3[1], e.batch3[2] = acc3[2];
 }
 
 template <int NTC>
@@ -95,6 +62,13 @@ __global__ __launch_bounds__(NT_ACC) void eval_accumulate_kernel(const float *lo
   accuracy_counts<NT_ACC>(e, n_prior, n_post);
   if (threadIdx.x != 0) return;
   accumulate(e, loss[0], out12, n_prior, n_post);
+}
+
+// the training log's epilogue for a loss, 12-vector and class probabilities of other launches
+__global__ __launch_bounds__(NT_ACC) void train_log_kernel(const float *loss, const float *out12,
+                                                          const float *extra2,
+                                                          TrainLogArgs g) {
+  train_log_epilogue<NT_ACC>(g, loss, out12, extra2);
 }
 
 int fill_eval(EvalArgs &e, const float *prior_prob, const float *post_prob,
@@ -150,5 +124,16 @@ extern "C" int scae_eval_accumulate_f32(const float *loss, const float *out12,
   if (rc) return rc;
   scae::launch(eval_accumulate_kernel, dim3(1), dim3(NT_ACC), 0, (hipStream_t)stream, loss,
                out12, e);
+  return scae_launch_status();
+}
+
+extern "C" int scae_train_log_f32(const float *loss, const float *out12, const float *extra2,
+                                  const scae_train_log_desc *log, int B, void *stream) {
+  SCAE_REQUIRE(loss && log);
+  TrainLogArgs g;
+  const int rc = fill_train_log(g, *log, B);
+  if (rc) return rc;
+  scae::launch(train_log_kernel, dim3(1), dim3(NT_ACC), 0, (hipStream_t)stream, loss, out12,
+               extra2, g);
   return scae_launch_status();
 }

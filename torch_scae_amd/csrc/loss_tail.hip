@@ -139,6 +139,17 @@ __global__ __launch_bounds__(NTC) void tail_combine_kernel(TailArgs a, scae_loss
   combine_body<NTC>(a, x, ws, out, smem);
 }
 
+// the combine with the training log's epilogue (scae_train_log_desc) after it
+template <int NTC>
+__global__ __launch_bounds__(NTC) void tail_combine_log_kernel(TailArgs a, scae_loss_extras x,
+                                                              Ws ws, float *out,
+                                                              TrainLogArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  combine_body<NTC>(a, x, ws, out, smem);
+  __syncthreads();
+  train_log_epilogue<NTC>(g, out, out, nullptr);
+}
+
 // d(gw * within + gb * between) / d x[b,o] for one image: x[o], col[o] in LDS
 __device__ __forceinline__ void sparsity_grad(const float *x, const float *col, float r, int B,
                                               int O, int type, float cw, float cb, float gw,
@@ -172,16 +183,11 @@ __device__ __forceinline__ void sparsity_grad(const float *x, const float *col, 
 // has run): the forward left the combine workgroup out -- it is the LAST workgroup of this
 // launch instead, and the image workgroups form the column sums they need themselves.
 template <int NT>
-__global__ __launch_bounds__(NT) void tail_bwd_kernel(TailArgs a, scae_loss_extras x, Ws ws,
-                                                      const float *gout /*[12]*/, float *g_lpp,
-                                                      float *g_post, float *g_cp, float *g_w,
-                                                      float *g_b) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
+__device__ __forceinline__ void tail_bwd_body(const TailArgs &a, const scae_loss_extras &x,
+                                              const Ws &ws, const float *gout /*[12]*/,
+                                              float *g_lpp, float *g_post, float *g_cp,
+                                              float *g_w, float *g_b, float *smem) {
   const int B = a.B, O = a.O, M = a.M, tid = threadIdx.x;
-  if (x.defer_combine && blockIdx.x + 1 == gridDim.x) {   // workgroup-uniform
-    combine_body<NT>(a, x, ws, x.out12, smem);
-    return;
-  }
   // d(total)/d(component): the loss plus whatever flowed into the individually
   // exposed log entries; d/d(loss) may arrive on the 12-vector, on the separate
   // scalar, or both
@@ -276,6 +282,37 @@ __global__ __launch_bounds__(NT) void tail_bwd_kernel(TailArgs a, scae_loss_extr
     }
   }
 }
+
+template <int NT>
+__global__ __launch_bounds__(NT) void tail_bwd_kernel(TailArgs a, scae_loss_extras x, Ws ws,
+                                                      const float *gout /*[12]*/, float *g_lpp,
+                                                      float *g_post, float *g_cp, float *g_w,
+                                                      float *g_b) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  if (x.defer_combine && blockIdx.x + 1 == gridDim.x) {   // workgroup-uniform
+    combine_body<NT>(a, x, ws, x.out12, smem);
+    return;
+  }
+  tail_bwd_body<NT>(a, x, ws, gout, g_lpp, g_post, g_cp, g_w, g_b, smem);
+}
+
+// defer_combine with the training log: the deferred combine workgroup ends in the log's
+// epilogue (no launch and no workgroup more)
+template <int NT>
+__global__ __launch_bounds__(NT) void tail_bwd_log_kernel(TailArgs a, scae_loss_extras x, Ws ws,
+                                                          const float *gout /*[12]*/,
+                                                          float *g_lpp, float *g_post,
+                                                          float *g_cp, float *g_w, float *g_b,
+                                                          TrainLogArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  if (blockIdx.x + 1 == gridDim.x) {   // workgroup-uniform
+    combine_body<NT>(a, x, ws, x.out12, smem);
+    __syncthreads();
+    train_log_epilogue<NT>(g, x.out12, x.out12, nullptr);
+    return;
+  }
+  tail_bwd_body<NT>(a, x, ws, gout, g_lpp, g_post, g_cp, g_w, g_b, smem);
+}
 }  // namespace
 
 extern "C" int scae_loss_tail_supported(int B, int O, int ncls) {
@@ -287,15 +324,38 @@ extern "C" int64_t scae_loss_tail_workspace_floats(int B, int O, int ncls) {
   return (int64_t)ws_floats(B, O, ncls);
 }
 
-// the combine workgroup on its own, in the shape this batch size takes
-static void launch_combine(const TailArgs &a, const scae_loss_extras &x, const Ws &ws, float *out12,
-                           hipStream_t st) {
-  if (scae_loss_tail_defer_preferred(a.B, a.O))
+int scae_tail::fill_train_log(TrainLogArgs &g, const scae_train_log_desc &d, int B) {
+  if (!d.rows || !d.step || d.capacity <= 0 || B <= 0 || d.ncls < 0) return SCAE_ERR_BAD_ARG;
+  if (d.label && (d.ncls <= 0 || !d.prior_prob || !d.post_prob)) return SCAE_ERR_BAD_ARG;
+  g = TrainLogArgs{d.rows, d.step, d.acc, d.prior_prob, d.post_prob, d.label, d.lr,
+                   d.capacity, B, d.ncls};
+  return SCAE_OK;
+}
+
+// the combine workgroup on its own, in the shape this batch size takes; with x.train_log its
+// training-log epilogue too
+static int launch_combine(const TailArgs &a, const scae_loss_extras &x, const Ws &ws,
+                          float *out12, hipStream_t st) {
+  const bool small = scae_loss_tail_defer_preferred(a.B, a.O);
+  if (x.train_log) {
+    TrainLogArgs g;
+    const int rc = fill_train_log(g, *x.train_log, a.B);
+    if (rc) return rc;
+    if (small)
+      scae::launch(tail_combine_log_kernel<NT_SMALL>, dim3(1), dim3(NT_SMALL), combine_lds(a.O),
+                   st, a, x, ws, out12, g);
+    else
+      scae::launch(tail_combine_log_kernel<NTC_LARGE>, dim3(1), dim3(NTC_LARGE),
+                   combine_lds(a.O), st, a, x, ws, out12, g);
+    return SCAE_OK;
+  }
+  if (small)
     scae::launch(tail_combine_kernel<NT_SMALL>, dim3(1), dim3(NT_SMALL), combine_lds(a.O), st,
                        a, x, ws, out12);
   else
     scae::launch(tail_combine_kernel<NTC_LARGE>, dim3(1), dim3(NTC_LARGE), combine_lds(a.O),
                        st, a, x, ws, out12);
+  return SCAE_OK;
 }
 
 int scae_tail::fill_tail(TailArgs &a, const float *lpp, const float *posterior, const float *cp,
@@ -340,8 +400,10 @@ static int tail_fwd(const float *lpp, const float *posterior, const float *caps_
   const int n_cp = cpa ? cpa->B + cpa->extra.n : 0;
   scae::launch(tail_image_kernel, dim3(B + n_cp), dim3(NTI), 3 * O * sizeof(float), st, a,
                      ws, cpa ? *cpa : scae_cp::Args{}, n_cp);
-  if (!x.defer_combine)   // (else: the backward launch -- or scae_loss_tail_combine_f32)
-    launch_combine(a, x, ws, out12, st);
+  if (!x.defer_combine) {  // (else: the backward launch -- or scae_loss_tail_combine_f32)
+    rc = launch_combine(a, x, ws, out12, st);
+    if (rc) return rc;
+  }
   return scae_launch_status();
 }
 
@@ -368,7 +430,8 @@ extern "C" int scae_loss_tail_combine_f32(const float *lpp, const float *posteri
   scae_loss_extras x{};
   if (extras) x = *extras;
   if (x.rec_sums && x.n_rec <= 0) return SCAE_ERR_BAD_ARG;
-  launch_combine(a, x, carve_ws(workspace, B, O, ncls), out12, (hipStream_t)stream);
+  rc = launch_combine(a, x, carve_ws(workspace, B, O, ncls), out12, (hipStream_t)stream);
+  if (rc) return rc;
   return scae_launch_status();
 }
 
@@ -425,6 +488,16 @@ extern "C" int scae_loss_tail_bwd_f32(const float *lpp, const float *posterior,
   const Ws ws = carve_ws(const_cast<float *>(workspace), B, O, ncls);
   if (x.defer_combine) SCAE_REQUIRE(x.out12);
   const size_t lds = 6 * O * sizeof(float) > combine_lds(O) ? 6 * O * sizeof(float) : combine_lds(O);
+  if (x.defer_combine && x.train_log) {   // the deferred combine with the log's epilogue
+    TrainLogArgs g;
+    rc = fill_train_log(g, *x.train_log, B);
+    if (rc) return rc;
+    const int cls_blocks = label ? (ncls * O + ncls + NT_SMALL / 4 - 1) / (NT_SMALL / 4) : 0;
+    scae::launch(tail_bwd_log_kernel<NT_SMALL>, dim3(B + cls_blocks + 1), dim3(NT_SMALL), lds,
+                 (hipStream_t)stream, a, x, ws, gout12, g_lpp, g_posterior, g_caps_presence,
+                 g_cls_w, g_cls_b, g);
+    return scae_launch_status();
+  }
 #define SCAE_TAIL_BWD(NTH)                                                                       \
   do {                                                                                           \
     const int cls_blocks = label ? (ncls * O + ncls + NTH / 4 - 1) / (NTH / 4) : 0;              \

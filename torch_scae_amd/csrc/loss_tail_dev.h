@@ -138,6 +138,117 @@ __device__ __forceinline__ void combine_body(const TailArgs &a, const scae_loss_
   if (x.loss) x.loss[0] = loss;
 }
 
+// -- accuracies and the fp64 epoch accumulator: the evaluation epilogue (eval_tail.hip) and
+// the training log (scae_train_log_desc, loss_tail.hip) ------------------------------------
+
+// torch.argmax over one row: the first maximal index; the first NaN wins.  The row is read
+// 16 classes at a time, the loads of a chunk in flight together.
+__device__ __forceinline__ int row_argmax(const float *p, int n) {
+  float v = 0.f;
+  int best = 0;
+  for (int c0 = 0; c0 < n; c0 += 16) {
+    float x[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) x[j] = c0 + j < n ? p[c0 + j] : 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int c = c0 + j;
+      if (c >= n) break;
+      if (x[j] != x[j]) return c;
+      if (c == 0 || x[j] > v) v = x[j], best = c;
+    }
+  }
+  return best;
+}
+
+// the two heads' correct counts, complete in thread 0 (all threads must call: barrier)
+template <int NT>
+__device__ __forceinline__ void accuracy_counts(const float *prior_prob, const float *post_prob,
+                                                const int64_t *label, int B, int ncls,
+                                                float &n_prior, float &n_post) {
+  __shared__ float red[2][NT / 64];
+  float cp = 0.f, cq = 0.f;  // (integers: exact in fp32 up to 2^24 images)
+  if (label && ncls > 0) {
+    for (int b = threadIdx.x; b < B; b += NT) {
+      const int64_t l = label[b];
+      cp += row_argmax(prior_prob + (size_t)b * ncls, ncls) == l ? 1.f : 0.f;
+      cq += row_argmax(post_prob + (size_t)b * ncls, ncls) == l ? 1.f : 0.f;
+    }
+  }
+  cp = scae::wave_sum(cp);
+  cq = scae::wave_sum(cq);
+  const int w = threadIdx.x / 64;
+  if ((threadIdx.x & 63) == 0) red[0][w] = cp, red[1][w] = cq;
+  __syncthreads();
+  n_prior = n_post = 0.f;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < NT / 64; ++i) n_prior += red[0][i], n_post += red[1][i];
+}
+
+// count / B per head (zero without a label) and the batch value max(prior, posterior)
+__device__ __forceinline__ void batch_accuracies(bool labelled, int B, float n_prior,
+                                                 float n_post, float acc3[3]) {
+  float pa = 0.f, qa = 0.f;
+  if (labelled) pa = n_prior / (float)B, qa = n_post / (float)B;
+  acc3[0] = qa > pa ? qa : pa, acc3[1] = pa, acc3[2] = qa;
+}
+
+// one thread: the batch into an SCAE_EVAL_ACC_DOUBLES accumulator (out12 nullable: zeros)
+__device__ __forceinline__ void accumulate_batch(double *A, float loss, const float *out12,
+                                                 const float acc3[3]) {
+  A[0] += 1.0;
+  A[1] += (double)loss;
+  A[2] += (double)acc3[0];
+  A[3] += (double)acc3[1];
+  A[4] += (double)acc3[2];
+  if (out12)
+    for (int i = 0; i < 12; ++i) A[5 + i] += (double)out12[i];
+}
+
+// The training log (include/scae_hip.h, scae_train_log_desc) as a kernel argument
+struct TrainLogArgs {
+  float *rows;                          // (capacity, SCAE_TRAIN_LOG_ROW)
+  int64_t *step;                        // device step counter
+  double *acc;                          // nullable
+  const float *prior_prob, *post_prob;  // (B, ncls)
+  const int64_t *label;                 // nullable: no accuracies
+  const float *lr;                      // nullable: NaN
+  int capacity, B, ncls;
+};
+
+// After the batch's loss and 12-vector exist (stores of this workgroup before a barrier, or
+// another launch's): the accuracies, one row of the ring at the step counter's slot, the
+// counter advanced, the batch added to the accumulator.  All threads call (barrier); the
+// first wave writes, lane i the row's entry i and the accumulator's entry i -- the same fp64
+// adds as accumulate_batch, with all of their loads in flight at once.
+template <int NT>
+__device__ __forceinline__ void train_log_epilogue(const TrainLogArgs &g, const float *loss,
+                                                   const float *out12, const float *extra) {
+  float n_prior, n_post;
+  accuracy_counts<NT>(g.prior_prob, g.post_prob, g.label, g.B, g.ncls, n_prior, n_post);
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x;
+  n_prior = __shfl(n_prior, 0), n_post = __shfl(n_post, 0);
+  float acc3[3];
+  batch_accuracies(g.label && g.ncls > 0, g.B, n_prior, n_post, acc3);
+  const int64_t s = g.step[0];
+  const float l = loss[0];
+  const float o = out12 && lane >= 4 && lane < 16 ? out12[lane - 4] : 0.f;
+  const float lr = g.lr ? g.lr[0] : __builtin_nanf("");
+  const float e = extra && lane >= 17 && lane < 19 ? extra[lane - 17] : 0.f;
+  const double a = g.acc && lane < SCAE_EVAL_ACC_DOUBLES ? g.acc[lane] : 0.0;
+  const float v = lane == 0 ? l : lane == 1 ? acc3[0] : lane == 2 ? acc3[1]
+                : lane == 3 ? acc3[2] : lane < 16 ? o : lane == 16 ? lr : e;
+  float *r = g.rows + (size_t)((uint64_t)s % (uint64_t)g.capacity) * SCAE_TRAIN_LOG_ROW;
+  if (lane < SCAE_TRAIN_LOG_ROW) r[lane] = v;
+  // the accumulator's entry i >= 1 is the row's entry i - 1: [1] loss, [2..4] accuracies,
+  // [5 + i] out12[i]; [0] counts batches
+  const float u = __shfl(v, lane > 0 ? lane - 1 : 0);
+  if (g.acc && lane < SCAE_EVAL_ACC_DOUBLES && (lane < 5 || out12))
+    g.acc[lane] = a + (lane == 0 ? 1.0 : (double)u);
+  if (lane == 0) g.step[0] = s + 1;
+}
+
 // LDS of the combine workgroup (either size)
 inline size_t combine_lds(int O) { return (2 * O + 6 * (NTC_LARGE / 64)) * sizeof(float); }
 
@@ -146,4 +257,6 @@ int fill_tail(TailArgs &a, const float *lpp, const float *posterior, const float
               const float *cls_w, const float *cls_b, const int64_t *label, int B, int O, int M,
               int ncls, int n_classes_cfg, int prior_type, int post_type, int sparsity_on,
               const float *weights /*5*/, float within_const);
+// TrainLogArgs from a descriptor (loss_tail.hip): SCAE_ERR_* on bad ones
+int fill_train_log(TrainLogArgs &g, const scae_train_log_desc &d, int B);
 }  // namespace scae_tail

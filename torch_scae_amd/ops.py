@@ -2891,6 +2891,12 @@ class _LossTail(torch.autograd.Function):
         if ev is not None and label is not None and not ctx.plan.holds("class_probs"):
             ev = None               # (no class probabilities to read: the plain tail)
         defer = defer and ev is None
+        # a logged training step's loss (rec_sums: this launch pair forms the whole scalar):
+        # the combine -- in the backward launch or on its own -- ends in the log's epilogue
+        tl = ctx.plan.train_log if ctx.plan.fused and rec_sums is not None and ev is None \
+            else None
+        if tl is not None and label is not None and not ctx.plan.holds("class_probs"):
+            tl = None               # (no class probabilities to read: the step logs alone)
         ex.defer_combine = int(defer or ev is not None)
         # per-image / per-column statistics the backward kernel reads back
         ws = torch.empty(_lib.load().scae_loss_tail_workspace_floats(
@@ -2898,6 +2904,9 @@ class _LossTail(torch.autograd.Function):
         tail = (_p(lpp), _p(posterior), _p(caps_presence), _p(cls_w), _p(cls_b),
                 lab, ctypes.byref(ex), _p(out), _p(ws), *ints, w5, wc)
         parked = ctx.plan.take("class_probs")
+        if tl is not None:
+            probs = (None, None) if label is None else parked.keep[4:6]
+            ex.train_log = ctypes.pointer(tl.fused_desc(*probs, label))
         if parked is not None:    # SCAE.forward's class probabilities ride along
             _lib.call("scae_loss_tail_fwd_class_probs_f32", *tail, *parked.args,
                       _stream(lpp))
@@ -2960,6 +2969,7 @@ class _LossTail(torch.autograd.Function):
             # the forward's combine workgroup rides in this launch
             ctx.plan.take("combine")
             ex.defer_combine, ex.loss, ex.out12 = 1, pend.loss_ptr, pend.out_ptr
+            ex.train_log = pend.keep[-1].train_log   # (the log's epilogue rides with it)
         w5 = (ctypes.c_float * 5)(*weights)
         lab = None if label is None else ctypes.c_void_p(label.data_ptr())
         _lib.call("scae_loss_tail_bwd_f32", _p(lpp), _p(posterior), _p(cp),
@@ -3018,6 +3028,82 @@ class EvalEpilogue:
         _lib.call("scae_eval_accumulate_f32", _p(loss), _p(out12), _p(prior), _p(post), lab,
                   B, ncls, _p(self.acc), _p(self.batch3), _stream(loss))
         self._keep = (loss, out12, prior, post, label)
+
+
+# The training log's row (include/scae_hip.h, SCAE_TRAIN_LOG_ROW) by SCAE.loss's log keys:
+# [4 + i] is the loss tail's 12-vector entry i (loss_tail_scalar)
+TRAIN_LOG_INDEX = {"loss": 0, "accuracy": 1, "prior_accuracy": 2, "posterior_accuracy": 3,
+                   "log_prob": 5, "prior_within_sparsity_loss": 6,
+                   "prior_between_sparsity_loss": 7, "posterior_within_sparsity_loss": 8,
+                   "posterior_between_sparsity_loss": 9, "prior_cls_xe": 10,
+                   "posterior_cls_xe": 11, "rec_ll": 12, "rec_ll_loss": 13,
+                   "log_prob_loss": 14, "cpr_dynamic_reg_loss": 15, "learning_rate": 16,
+                   "mse": 17, "part_caps_loss": 18}
+
+
+def ring_order(count, capacity):
+    """-> (slots, steps): the ring's rows holding the last min(count, capacity) of ``count``
+    logged steps, oldest first, and those steps' numbers (0-based)."""
+    k = min(count, capacity)
+    steps = list(range(count - k, count))
+    return [s % capacity for s in steps], steps
+
+
+class TrainLog:
+    """Buffers of a training step's log (include/scae_hip.h, scae_train_log_desc): a device
+    ring of ``capacity`` rows of SCAE_TRAIN_LOG_ROW floats, the int64 step counter that picks
+    the row, and an fp64 epoch accumulator laid out as the evaluation epilogue's
+    (eval_step.means reads it).  ``lr``: the optimiser's device learning rate (or None).
+    ``fused_desc``: the descriptor the loss tail's combine carries (``_LossTail.forward``
+    inside a plan that logs); ``log_alone``: the epilogue as a launch of its own, for a loss
+    the tail did not complete."""
+
+    def __init__(self, capacity, device, lr=None):
+        self.capacity = int(capacity)
+        self.rows = torch.zeros(self.capacity, _lib.TRAIN_LOG_ROW, device=device,
+                                dtype=torch.float32)
+        self.step = torch.zeros(1, device=device, dtype=torch.int64)
+        self.acc = torch.zeros(_lib.EVAL_ACC_DOUBLES, device=device, dtype=torch.float64)
+        self.lr = lr
+        self.count = 0          # host mirror of step[0]: rows written so far
+        self.fused = False      # the last forward wired the combine's epilogue
+        self._keep = None       # what the last launch points into
+
+    def _desc(self, prior, post, label):
+        d = _lib.TrainLogDesc()
+        d.rows, d.step, d.acc = self.rows.data_ptr(), self.step.data_ptr(), \
+            self.acc.data_ptr()
+        d.capacity = self.capacity
+        d.lr = None if self.lr is None else self.lr.data_ptr()
+        if label is not None:
+            d.prior_prob, d.post_prob, d.label = prior.data_ptr(), post.data_ptr(), \
+                label.data_ptr()
+            d.ncls = prior.shape[-1]
+        return d
+
+    def fused_desc(self, prior, post, label):
+        _need_hip(prior, post)
+        d = self._desc(prior, post, label)
+        self.fused, self._keep = True, (d, prior, post, label)
+        return d
+
+    def log_alone(self, loss, out12, extra2, prior, post, label):
+        """loss (), out12 (12) or None, extra2 (2: mse, part-capsule L1) or None, class
+        probabilities (B, ncls) and label (B) int64, or three Nones (no classes)."""
+        _need_hip(loss, out12, extra2, prior, post)
+        loss, out12, extra2 = _c(loss), _c(out12), _c(extra2)
+        prior, post, label = _c(prior), _c(post), _c(label)
+        B = 1 if label is None else label.shape[0]
+        d = self._desc(prior, post, label)
+        _lib.call("scae_train_log_f32", _p(loss), _p(out12), _p(extra2), ctypes.byref(d), B,
+                  _stream(loss))
+        self._keep = (d, loss, out12, extra2, prior, post, label)
+
+    def reset(self):
+        self.rows.zero_()
+        self.step.zero_()
+        self.acc.zero_()
+        self.count = 0
 
 
 def loss_tail(*args, **kwargs):

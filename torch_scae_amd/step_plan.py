@@ -158,6 +158,9 @@ class StepPlan:
         # run: a no-grad forward then takes the training step's fused launches, and the loss
         # tail ends in the evaluation epilogue instead of its batch combine
         self.evaluation = None
+        # train_step.TrainStep's training log (ops.TrainLog) while a logged step's forward +
+        # loss run: the loss tail's batch combine then ends in the log's epilogue
+        self.train_log = None
 
     # -- the second lane ----------------------------------------------------
     @contextlib.contextmanager
@@ -345,6 +348,14 @@ class StepPlan:
             yield self
         finally:
             self.evaluation = prev
+
+    @contextlib.contextmanager
+    def logging(self, train_log):
+        prev, self.train_log = self.train_log, train_log
+        try:
+            yield self
+        finally:
+            self.train_log = prev
 
     @contextlib.contextmanager
     def precision(self, bf16):

@@ -83,6 +83,15 @@ class TrainStep:
     wrapped in LookAhead(``look_ahead_k``, ``look_ahead_alpha``) (optimizers.py:105-190),
     fused into the same pass.  eps = 1e-2 / batch_size**2 for all three
     (:46).  Every optimiser runs in every replay and collective mode.
+
+    ``log_steps``: the capacity of the step's training log (0: no log).  Every step then
+    leaves the `log` of BaseExperiment.training_step (base_experiment.py:109-126) -- the
+    keys ``training_step()`` returns for this model, plus ``learning_rate`` -- as one row of
+    a device ring, and adds it into an fp64 epoch accumulator.  Where the loss tail forms
+    the whole scalar the row is written by the tail's batch combine (no launch and no torch
+    operator more: ``step_from`` / ``replay="launches"`` keep their form); other models log
+    with one launch of their own (scae_train_log_f32).  ``last_log()``,
+    ``log_history()``, ``training_epoch_end()``, ``reset_log()``.  Rows are rank-local.
     """
 
     MODES = ("2 buckets", "1 bucket", "in graph")
@@ -93,9 +102,15 @@ class TrainStep:
                  force_collective=False, overlap=True, lazy_render=True,
                  prologue=True, fuse_kernels=True, collective_mode=None,
                  replay="graph", two_lanes=False, betas=(0.9, 0.999),
-                 look_ahead=False, look_ahead_k=5, look_ahead_alpha=0.5):
+                 look_ahead=False, look_ahead_k=5, look_ahead_alpha=0.5,
+                 log_steps=0):
+        if not isinstance(log_steps, int) or isinstance(log_steps, bool) or log_steps < 0:
+            raise ValueError(f"log_steps must be an int >= 0, got {log_steps!r}")
         self.model = model
         self.device = next(model.parameters()).device
+        if log_steps and self.device.type != "cuda":
+            raise ValueError("log_steps needs a model on a HIP device (the log's epilogue "
+                             "is a device kernel)")
         self.world = world()[1]
         if collective_mode is None and \
                 os.environ.get("SCAE_GRAPH_ALLREDUCE", "0") == "1":
@@ -154,6 +169,12 @@ class TrainStep:
             look_ahead_alpha=look_ahead_alpha) \
             if optimizer not in (None, False) else None
         self.steps = 0           # steps taken (host count; the optimisers keep their own)
+        # the training log (ops.TrainLog): ring, step counter, epoch accumulator
+        self.train_log = ops.TrainLog(
+            log_steps, self.device, lr=None if self.opt is None else self.opt.lr_dev) \
+            if log_steps else None
+        self._log_keys = None    # the log's keys, from the logged step's SCAE.loss
+        self._warming = False    # a capture's warm-ups: not logged
         self.lr_decay_rate = lr_decay_rate
         # the backward's last column sums (parameter gradients only) ride in the optimiser's
         # launch: one launch less on the step's dependent chain.  Not with a collective (the
@@ -235,8 +256,11 @@ class TrainStep:
             # would become a launch of every replay)
             ops._launch_sum_units(stale)
         self.flat.clear_grads()
+        tlog = self.train_log if not self._warming else None
+        if tlog is not None:
+            tlog.fused = False
         with plan.active(), plan.precision(self.autocast_dtype is not None), \
-                self._lazy(), \
+                self._lazy(), plan.logging(tlog), \
                 plan.fusing(self.image if self.fuse_kernels else None):
             res = self.model(self.image)
             loss, info = self.model.loss(res, self.image, self.label)
@@ -244,6 +268,8 @@ class TrainStep:
             # only produce parameter gradients wait for ONE launch at the end
             with plan.deferring():
                 loss.backward(self._one)
+        if tlog is not None:
+            self._log_step(tlog, res, loss, info)
         self._cut = res.get("_phase_cut") if self.split else None
         self.flat.gather_grads(None if self._cut is None else 0)
         if self._capturing:
@@ -264,6 +290,31 @@ class TrainStep:
                 self.log = {k: torch.zeros_like(v) for k, v in fresh.items()}
             for k, v in fresh.items():
                 self.log[k].copy_(v)
+
+    def _log_step(self, tlog, res, loss, info):
+        """The log's keys from this step's SCAE.loss; a loss the tail did not complete logs
+        with the epilogue's own launch."""
+        keys = ["loss", *info.keys()]
+        if self.model.n_classes is not None:
+            keys.append("accuracy")
+        keys.append("learning_rate")
+        unknown = [k for k in keys if k not in ops.TRAIN_LOG_INDEX]
+        if unknown:
+            raise ValueError(f"log keys {unknown} have no place in the training log's row")
+        self._log_keys = keys
+        if tlog.fused:
+            return
+        from .eval_step import out12_from_log
+        labelled = self.model.n_classes is not None
+        extra = [info.get(k) for k in ("mse", "part_caps_loss")]
+        with self.plan.active():
+            extra2 = None if extra == [None, None] else torch.stack(
+                [torch.zeros((), device=self.device) if v is None
+                 else v.detach().reshape(()).float() for v in extra])
+            tlog.log_alone(loss.detach(), out12_from_log(loss, info), extra2,
+                           res.prior_cls_prob.detach() if labelled else None,
+                           res.posterior_cls_prob.detach() if labelled else None,
+                           self.label if labelled else None)
 
     def _part_b(self):
         """split only: the backward below the decoders' inputs."""
@@ -321,9 +372,13 @@ class TrainStep:
         s = self._stream
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            for _ in range(3):
-                self._refresh_prologue()
-                self._fwd_bwd()
+            self._warming = True        # (the warm-ups' batches are not the log's)
+            try:
+                for _ in range(3):
+                    self._refresh_prologue()
+                    self._fwd_bwd()
+            finally:
+                self._warming = False
             self._refresh_prologue()    # what the capture below consumes
         torch.cuda.current_stream().wait_stream(s)
         # capture on the SAME stream the warm-up ran on: autograd caches each
@@ -607,6 +662,8 @@ class TrainStep:
 
     def _step_staged(self):
         self.steps += 1
+        if self.train_log is not None:
+            self.train_log.count += 1   # (the row this step writes)
         if self.use_graph:
             self.capture()
             if self.split:
@@ -638,6 +695,54 @@ class TrainStep:
             self._with_log, self.graph, self.graph_b = True, None, None
         loss = self(image, label)
         return dict(loss=loss, log=self.log)
+
+    # -- the training log (log_steps) ---------------------------------------------
+    def _need_log(self):
+        if self.train_log is None:
+            raise ValueError("this step keeps no training log (TrainStep(log_steps=...))")
+        return self.train_log
+
+    def last_log(self):
+        """-> {'loss', 'log'} of the newest logged step, as ``training_step()`` returns them
+        for this model plus ``log['learning_rate']``: device views of the ring's row (a
+        later step overwrites it once the ring wraps), no read.  None before the first
+        step."""
+        tlog = self._need_log()
+        if tlog.count == 0:
+            return None
+        row = tlog.rows[(tlog.count - 1) % tlog.capacity]
+        return dict(loss=row[0], log={k: row[ops.TRAIN_LOG_INDEX[k]] for k in self._log_keys})
+
+    def log_history(self):
+        """-> ({key: host tensor (n,)}, steps): the last n = min(steps logged, capacity)
+        rows in step order and their step numbers (0-based since the last ``reset_log``).
+        One read of the ring."""
+        tlog = self._need_log()
+        slots, steps = ops.ring_order(tlog.count, tlog.capacity)
+        if not slots:
+            return {}, []
+        rows = tlog.rows.cpu()[slots]
+        return {k: rows[:, ops.TRAIN_LOG_INDEX[k]] for k in self._log_keys}, steps
+
+    def training_epoch_end(self, all_ranks=False):
+        """-> the means of the steps logged since the last call ({key: fp32 mean, 'batches':
+        n}, eval_step.means: the unweighted mean over steps), then clears the accumulator.
+        ``all_ranks``: summed over the ranks first (data_parallel.all_reduce_sums, outside
+        any graph); else this rank's."""
+        from .data_parallel import all_reduce_sums
+        from .eval_step import means
+        tlog = self._need_log()
+        sums = tlog.acc
+        if all_ranks:
+            sums = sums.clone()
+            all_reduce_sums(sums)
+        out = means(sums)
+        tlog.acc.zero_()
+        return out
+
+    def reset_log(self):
+        """Empty ring, step counter 0, accumulator cleared."""
+        self._need_log().reset()
 
     def end_epoch(self):
         """Per-epoch ExponentialLR step (base_experiment.py:73-76)."""
