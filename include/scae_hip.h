@@ -1115,6 +1115,20 @@ int scae_class_probs_f32(const float *caps_presence, const float *posterior, con
  *     with one writer per entry and no atomics: the sums are reproducible bit for bit.
  * The descriptor itself is host memory, read when the launch is issued; the pointers in it
  * are device memory. */
+/* The evaluation feature sink: DEVICE memory that a captured launch reaches by its address, so
+ * that pointing it at another output needs no new capture.  Batch rows [cursor, cursor + B)
+ * of an (capacity, 2, O) fp32 matrix receive each image's two classifier inputs: [.., 0, o]
+ * the prior presence caps_presence[b, o] and [.., 1, o] the posterior mass
+ * sum_m posterior[b, o, m] (summed as scae_class_probs_f32 sums it).  A row at or beyond
+ * capacity is dropped and sets overflow; the batch's last launch advances cursor by B (ONE
+ * thread, in stream order).  capacity 0: the sink is off -- nothing is written and the cursor
+ * stays. */
+typedef struct scae_eval_sink {
+  float *rows;
+  int64_t capacity;
+  int64_t cursor;
+  int64_t overflow;
+} scae_eval_sink;
 #define SCAE_TRAIN_LOG_ROW 19
 typedef struct scae_train_log_desc {
   float *rows;      /* (capacity, SCAE_TRAIN_LOG_ROW) ring */
@@ -1175,6 +1189,18 @@ int scae_loss_tail_fwd_class_probs_f32(
     const float *cp_caps_presence, const float *cp_posterior, const float *cp_w,
     const float *cp_bias, float *prior_prob, float *post_prob, int cp_B, int cp_O, int cp_M,
     int cp_ncls, const scae_scaled_sum *extra_sums, int n_extra, void *stream);
+/* The same with the evaluation feature sink (scae_eval_sink, DEVICE memory, nullable): the
+ * riding image workgroups store their classifier inputs at rows cursor + b.  The cursor is
+ * advanced by the batch's last launch (scae_eval_tail_sink_f32). */
+int scae_loss_tail_fwd_class_probs_sink_f32(
+    const float *lpp, const float *posterior, const float *caps_presence, const float *cls_w,
+    const float *cls_b, const int64_t *label, const scae_loss_extras *extras, float *out12,
+    float *workspace, int B, int O, int M, int ncls, int n_classes_cfg, int prior_type,
+    int post_type, int sparsity_on, const float *weights5, float within_const,
+    const float *cp_caps_presence, const float *cp_posterior, const float *cp_w,
+    const float *cp_bias, float *prior_prob, float *post_prob, int cp_B, int cp_O, int cp_M,
+    int cp_ncls, const scae_scaled_sum *extra_sums, int n_extra, scae_eval_sink *sink,
+    void *stream);
 int scae_loss_tail_bwd_f32(const float *lpp, const float *posterior,
                            const float *caps_presence, const float *cls_w,
                            const float *cls_b, const int64_t *label,
@@ -1211,6 +1237,15 @@ int scae_eval_tail_f32(const float *lpp, const float *posterior, const float *ca
                        int post_type, int sparsity_on, const float *weights5,
                        float within_const, const float *prior_prob, const float *post_prob,
                        double *acc, float *batch3, void *stream);
+/* The same, ending the batch of a feature sink (nullable): thread 0 advances its cursor by B
+ * after the accumulation. */
+int scae_eval_tail_sink_f32(const float *lpp, const float *posterior, const float *caps_presence,
+                            const float *cls_w, const float *cls_b, const int64_t *label,
+                            const scae_loss_extras *extras, float *out12, float *workspace,
+                            int B, int O, int M, int ncls, int n_classes_cfg, int prior_type,
+                            int post_type, int sparsity_on, const float *weights5,
+                            float within_const, const float *prior_prob, const float *post_prob,
+                            double *acc, float *batch3, scae_eval_sink *sink, void *stream);
 /* Accuracies + accumulation only, for a loss other launches computed (a model outside the
  * fused tail: recon_mse_weight > 0, part_caps_sparsity_weight > 0, more than 32 classes):
  * loss (1), out12 (12, nullable), prior_prob / post_prob (B, ncls) and label (nullable
@@ -1218,6 +1253,12 @@ int scae_eval_tail_f32(const float *lpp, const float *posterior, const float *ca
 int scae_eval_accumulate_f32(const float *loss, const float *out12, const float *prior_prob,
                              const float *post_prob, const int64_t *label, int B, int ncls,
                              double *acc, float *batch3, void *stream);
+/* The feature sink's rows of one batch and the cursor's advance as a launch of its own, for a
+ * batch whose class probabilities did not ride in the loss tail (O > 64, no classes, a model
+ * outside the fused tail): caps_presence (B, O), posterior (B, O + 1, M) -- only its first O
+ * rows are read.  One workgroup. */
+int scae_eval_features_f32(const float *caps_presence, const float *posterior, int B, int O,
+                           int M, scae_eval_sink *sink, void *stream);
 /* The training log's epilogue alone (scae_train_log_desc, B images), for a loss other launches
  * computed (a model outside the fused tail, or a step whose plan holds no class probabilities):
  * loss (1), out12 (12, nullable: zeros), extra2 (2, nullable: zeros) = {mse, part-capsule L1}.
@@ -1379,6 +1420,53 @@ int scae_gmm_mean_f32(const float *loc, const float *mixing_logits, float *out,
 int scae_gmm_mode_f32(const float *loc, const float *mixing_logits,
                       const float *sigma, float *out, int maximum, int B,
                       int K, int C, int Cm, int64_t P, void *stream);
+
+/* ------------------------------------------------------------------------
+ * k-means (csrc/kmeans.hip): Lloyd iterations of n_init restarts in one grid, no float atomics.
+ *   distance sum_f (x_f - c_f)^2 in f order, ties to the lowest cluster; update the mean of the
+ *   assigned points (an empty cluster keeps its centroid); a restart stops when no assignment
+ *   changed or after max_iter assignments -- the update of that last assignment is skipped, so
+ *   centroids, labels and inertia always belong together.
+ * ------------------------------------------------------------------------ */
+#define SCAE_KMEANS_MAX_K 256
+#define SCAE_KMEANS_MAX_F 256
+#define SCAE_KMEANS_MAX_KF 16384
+#define SCAE_KMEANS_STATE_INTS 4   /* per restart: done, iterations, converged, last changed */
+int scae_kmeans_supported(int k, int F);
+/* the workgroups per restart of an assignment launch (the partials' G) */
+int scae_kmeans_groups(int64_t N, int R);
+typedef struct scae_kmeans_desc {
+  const float *x;        /* (N, F) */
+  int64_t N;
+  int F, k, R;           /* features, clusters, restarts */
+  int G;                 /* scae_kmeans_groups(N, R) */
+  int max_iter;
+  float *centroids;      /* (R, k, F): the init in, the result out */
+  int64_t *labels;       /* (R, N): -1 before the first assignment */
+  float *part_sum;       /* (R, G, k F) */
+  int *part_count;       /* (R, G, k) */
+  int *part_changed;     /* (R, G) */
+  double *part_inertia;  /* (R, G) */
+  int *state;            /* R * SCAE_KMEANS_STATE_INTS + 1 zeros; the last int counts the
+                          * restarts that have stopped (the host's one read per chunk) */
+  double *inertia;       /* (R): of the last assignment */
+} scae_kmeans_desc;
+/* n_iters Lloyd iterations (two launches each: assignment, then a fixed-order reduction and
+ * update); launches of a stopped restart exit at once. */
+int scae_kmeans_lloyd_f32(const scae_kmeans_desc *d, int n_iters, void *stream);
+/* k-means++ (D^2 sampling) of R restarts, one workgroup each: centre j of restart r takes the
+ * uniform u of Philox4x32-10 keyed (seed, r) at counter (j, 0, 0, 0x4B4D5050), 24 bits -> [0, 1),
+ * and picks the first point whose running D^2 sum exceeds u * total (centre 0: every weight 1).
+ * centroids (R, k, F), d2 (R, N) workspace, chosen (R, k) the picked rows. */
+int scae_kmeans_pp_f32(const float *x, int64_t N, int F, int k, int R, uint32_t seed,
+                       float *centroids, float *d2, int64_t *chosen, void *stream);
+/* nearest-centroid labels (N) of x (N, F) under centroids (k, F) */
+int scae_kmeans_assign_f32(const float *x, int64_t N, int F, int k, const float *centroids,
+                           int64_t *labels, void *stream);
+/* table (k, ncls) += counts of (cluster_ids[n], labels[n]) pairs; pairs outside the table
+ * count into *outside.  Integer atomics: any order gives the same counts. */
+int scae_kmeans_contingency(const int64_t *cluster_ids, const int64_t *labels, int64_t N, int k,
+                            int ncls, int *table, int *outside, void *stream);
 
 #ifdef __cplusplus
 }

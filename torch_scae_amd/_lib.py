@@ -7,7 +7,7 @@ tensor is not on a HIP device, the ops raise.
 import ctypes
 import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int,
-                    c_int64, c_uint64, c_void_p)
+                    c_int64, c_uint32, c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SCAE_HIP_LIB: another build of the same library, for A/B measurements)
@@ -113,6 +113,14 @@ class LossExtras(Structure):
                 ("w_reg", c_float), ("g_rec_sums", P), ("g_reg", P),
                 ("loss", P), ("g_loss", P), ("defer_combine", c_int),
                 ("out12", P), ("train_log", POINTER(TrainLogDesc))]
+
+
+class KMeansDesc(Structure):
+    """struct scae_kmeans_desc"""
+    _fields_ = [("x", P), ("N", c_int64), ("F", c_int), ("k", c_int), ("R", c_int),
+                ("G", c_int), ("max_iter", c_int), ("centroids", P), ("labels", P),
+                ("part_sum", P), ("part_count", P), ("part_changed", P),
+                ("part_inertia", P), ("state", P), ("inertia", P)]
 
 
 class SeedFoldDesc(Structure):
@@ -322,8 +330,20 @@ SIGNATURES = {
     + [c_int] * 8 + [POINTER(c_float), c_float, P],
     "scae_eval_tail_f32": [P] * 6 + [POINTER(LossExtras), P, P] + [c_int] * 8
     + [POINTER(c_float), c_float] + [P] * 5,
+    "scae_loss_tail_fwd_class_probs_sink_f32": [P] * 6 + [POINTER(LossExtras), P, P]
+    + [c_int] * 8 + [POINTER(c_float), c_float] + [P] * 6 + [c_int] * 4
+    + [POINTER(ScaledSum), c_int, P, P],
+    "scae_eval_tail_sink_f32": [P] * 6 + [POINTER(LossExtras), P, P] + [c_int] * 8
+    + [POINTER(c_float), c_float] + [P] * 6,
     "scae_eval_accumulate_f32": [P] * 5 + [c_int] * 2 + [P] * 3,
     "scae_train_log_f32": [P] * 3 + [POINTER(TrainLogDesc), c_int, P],
+    "scae_eval_features_f32": [P, P, c_int, c_int, c_int, P, P],
+    "scae_kmeans_supported": [c_int] * 2,
+    "scae_kmeans_groups": [c_int64, c_int],
+    "scae_kmeans_lloyd_f32": [POINTER(KMeansDesc), c_int, P],
+    "scae_kmeans_pp_f32": [P, c_int64, c_int, c_int, c_int, c_uint32, P, P, P, P],
+    "scae_kmeans_assign_f32": [P, c_int64, c_int, c_int, P, P, P],
+    "scae_kmeans_contingency": [P, P, c_int64, c_int, c_int, P, P, P],
     "scae_template_render_fwd_f32": [POINTER(DecoderDesc), P, P, P],
     "scae_render_gmm_logprob_fwd_f32": [POINTER(DecoderDesc), P, P, P, P, P],
     "scae_render_gmm_bwd_f32": [POINTER(DecoderDesc)] + [P] * 12 + [P],
@@ -344,6 +364,8 @@ _RESTYPES = {"scae_error_string": c_char_p,
              "scae_launch_list_free": None}
 EVAL_ACC_DOUBLES = 17        # SCAE_EVAL_ACC_DOUBLES: the accumulator of scae_eval_*
 TRAIN_LOG_ROW = 19           # SCAE_TRAIN_LOG_ROW: one row of scae_train_log_desc's ring
+KMEANS_STATE_INTS = 4        # SCAE_KMEANS_STATE_INTS: per restart of scae_kmeans_desc's state
+EVAL_SINK_INT64S = 4         # struct scae_eval_sink: rows, capacity, cursor, overflow
 FLAT_OPT_STATE_INTS = 2112   # SCAE_FLAT_OPT_STATE_INTS: the step_state of scae_flat_opt_*
 ABI_VERSION = 2     # SCAE_ABI_VERSION of the include/scae_hip.h this binding mirrors
 

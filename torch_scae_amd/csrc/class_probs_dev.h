@@ -14,10 +14,32 @@ struct Args {
   float *prior_prob, *post_prob;
   int B, O, M, ncls;
   ExtraSums extra;
+  scae_eval_sink *sink;  // nullable (device): the evaluation feature sink (scae_hip.h)
 };
 struct Lds {
   float x[2][64], l[2][MAXCLS];
 };
+
+// the two classifier inputs of image b, capsule o into the sink's row cursor + b (the cursor
+// is advanced by a later launch: every workgroup of this one reads the same value)
+__device__ __forceinline__ void sink_store(const scae_eval_sink *k, int b, int O, int o,
+                                           float presence, float mass) {
+  const int64_t cap = k->capacity;
+  if (cap <= 0) return;
+  const int64_t row = k->cursor + b;
+  if (row >= cap) return;
+  k->rows[(row * 2) * O + o] = presence;
+  k->rows[(row * 2 + 1) * O + o] = mass;
+}
+
+// thread 0 of a batch's last launch: rows [cursor, cursor + B) are done
+__device__ __forceinline__ void sink_advance(scae_eval_sink *k, int B) {
+  const int64_t cap = k->capacity;
+  if (cap <= 0) return;
+  const int64_t end = k->cursor + B;
+  if (end > cap) k->overflow = 1;
+  k->cursor = end;
+}
 
 // workgroup b (one wave): b < B an image, else rider b - B
 __device__ __forceinline__ void body(const Args &a, Lds &s, int b, int lane) {
@@ -45,6 +67,7 @@ __device__ __forceinline__ void body(const Args &a, Lds &s, int b, int lane) {
     for (; m + 4 <= M; m += 4) m0 += p[m], m1 += p[m + 1], m2 += p[m + 2], m3 += p[m + 3];
     for (; m < M; ++m) m0 += p[m];
     s.x[1][lane] = (m0 + m1) + (m2 + m3);
+    if (a.sink) sink_store(a.sink, b, O, lane, s.x[0][lane], s.x[1][lane]);
   }
   __syncthreads();
   if (lane < 2 * ncls) {  // lane = (input, class): one logit each
@@ -78,7 +101,7 @@ inline int fill(Args &a, const float *caps_presence, const float *posterior, con
                M > 0);
   if (!scae_class_probs_supported(O, ncls)) return SCAE_ERR_UNSUPPORTED;
   SCAE_REQUIRE(n_extra >= 0 && n_extra <= 8 && (n_extra == 0 || extra_sums));
-  a = Args{caps_presence, posterior, w, bias, prior_prob, post_prob, B, O, M, ncls, {}};
+  a = Args{caps_presence, posterior, w, bias, prior_prob, post_prob, B, O, M, ncls, {}, nullptr};
   a.extra.n = n_extra;
   for (int i = 0; i < n_extra; ++i) {
     a.extra.j[i] = extra_sums[i];

@@ -448,6 +448,25 @@ extern "C" int scae_loss_tail_fwd_f32(const float *lpp, const float *posterior,
                   within_const, nullptr, stream);
 }
 
+extern "C" int scae_loss_tail_fwd_class_probs_sink_f32(
+    const float *lpp, const float *posterior, const float *caps_presence, const float *cls_w,
+    const float *cls_b, const int64_t *label, const scae_loss_extras *extras, float *out12,
+    float *workspace, int B, int O, int M, int ncls, int n_classes_cfg, int prior_type,
+    int post_type, int sparsity_on, const float *weights5, float within_const,
+    const float *cp_caps_presence, const float *cp_posterior, const float *cp_w,
+    const float *cp_bias, float *prior_prob, float *post_prob, int cp_B, int cp_O, int cp_M,
+    int cp_ncls, const scae_scaled_sum *extra_sums, int n_extra, scae_eval_sink *sink,
+    void *stream) {
+  scae_cp::Args cpa;
+  int rc = scae_cp::fill(cpa, cp_caps_presence, cp_posterior, cp_w, cp_bias, prior_prob,
+                         post_prob, cp_B, cp_O, cp_M, cp_ncls, extra_sums, n_extra);
+  if (rc) return rc;
+  cpa.sink = sink;
+  return tail_fwd(lpp, posterior, caps_presence, cls_w, cls_b, label, extras, out12, workspace,
+                  B, O, M, ncls, n_classes_cfg, prior_type, post_type, sparsity_on, weights5,
+                  within_const, &cpa, stream);
+}
+
 extern "C" int scae_loss_tail_fwd_class_probs_f32(
     const float *lpp, const float *posterior, const float *caps_presence, const float *cls_w,
     const float *cls_b, const int64_t *label, const scae_loss_extras *extras, float *out12,
@@ -456,13 +475,11 @@ extern "C" int scae_loss_tail_fwd_class_probs_f32(
     const float *cp_caps_presence, const float *cp_posterior, const float *cp_w,
     const float *cp_bias, float *prior_prob, float *post_prob, int cp_B, int cp_O, int cp_M,
     int cp_ncls, const scae_scaled_sum *extra_sums, int n_extra, void *stream) {
-  scae_cp::Args cpa;
-  int rc = scae_cp::fill(cpa, cp_caps_presence, cp_posterior, cp_w, cp_bias, prior_prob,
-                         post_prob, cp_B, cp_O, cp_M, cp_ncls, extra_sums, n_extra);
-  if (rc) return rc;
-  return tail_fwd(lpp, posterior, caps_presence, cls_w, cls_b, label, extras, out12, workspace,
-                  B, O, M, ncls, n_classes_cfg, prior_type, post_type, sparsity_on, weights5,
-                  within_const, &cpa, stream);
+  return scae_loss_tail_fwd_class_probs_sink_f32(
+      lpp, posterior, caps_presence, cls_w, cls_b, label, extras, out12, workspace, B, O, M,
+      ncls, n_classes_cfg, prior_type, post_type, sparsity_on, weights5, within_const,
+      cp_caps_presence, cp_posterior, cp_w, cp_bias, prior_prob, post_prob, cp_B, cp_O, cp_M,
+      cp_ncls, extra_sums, n_extra, nullptr, stream);
 }
 
 extern "C" int scae_loss_tail_bwd_f32(const float *lpp, const float *posterior,

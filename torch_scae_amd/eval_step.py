@@ -141,6 +141,9 @@ class EvalStep:
         self._stream = None
         self._home = None        # parameter storage the capture read
         self._tail_step = None   # evaluate()'s remainder batch
+        self._cap_sink = None    # the feature sink the captured launches carry
+        self._cpu_rows = None    # encode() on the CPU: the batches' (B, 2, O) rows
+        self._zero_labels = None
 
     # -- the batch ----------------------------------------------------------
     def _storage(self):
@@ -171,6 +174,9 @@ class EvalStep:
         if not self.cuda:
             res = model(self.image)
             loss, log = model.loss(res, self.image, label)
+            if self._cpu_rows is not None:
+                self._cpu_rows.append(torch.stack(
+                    [res.caps_presence, res.posterior_mixing_prob.sum(-1)], 1))
             probs = (res.prior_cls_prob, res.posterior_cls_prob) if label is not None \
                 else (None, None)
             self.batch_acc.copy_(accumulate_host(self.acc, loss, out12_from_log(loss, log),
@@ -178,7 +184,7 @@ class EvalStep:
             self.loss.copy_(loss.detach())
             return
         plan, epi = self.plan, self.epi
-        epi.fused = False
+        epi.fused = epi.sink_written = False
         with plan.active(), plan.precision(self.autocast_dtype is not None), \
                 plan.fusing(self.image if self.fuse_kernels else None), \
                 plan.evaluating(epi):
@@ -190,6 +196,10 @@ class EvalStep:
                 probs = (res.prior_cls_prob, res.posterior_cls_prob) \
                     if label is not None else (None, None)
                 epi.accumulate(loss.detach(), out12_from_log(loss, log), *probs, label)
+        if epi.sink is not None and not epi.sink_written:
+            # (the class probabilities did not ride in the loss tail: the rows on their own)
+            with plan.active():
+                epi.sink.launch_alone(res.caps_presence, res["_posterior_full"])
         if torch.cuda.is_current_stream_capturing():
             # the captured loss lives in the graph's pool at a fixed address
             self.loss = loss.detach()
@@ -289,6 +299,7 @@ class EvalStep:
                 if klist:
                     lib.scae_launch_list_free(klist)
         self._home = self._storage()
+        self._cap_sink = self.epi.sink
         self._refresh_prologue()
 
     def _graph_is_only_launches(self, n_launches):
@@ -331,9 +342,13 @@ class EvalStep:
     def capture(self):
         """Build the step's graph now (or again, when the parameters have been re-homed
         since the last capture).  The accumulator is left cleared."""
-        if self.use_graph and (self.graph is None or self._home != self._storage()):
+        if self.use_graph and self._stale():
             self.graph = None
             self._capture()
+
+    def _stale(self):
+        return self.graph is None or self._home != self._storage() or \
+            self._cap_sink is not self.epi.sink
 
     def __call__(self, image, label):
         """One evaluation batch: stage, run (replay), accumulate.  -> the batch loss."""
@@ -342,7 +357,7 @@ class EvalStep:
     def _run(self, stage):
         stage()
         if self.use_graph:
-            if self.graph is None or self._home != self._storage():
+            if self._stale():
                 # (a capture runs warm-up batches: keep what the epoch has so far)
                 kept = self.acc.clone()
                 self.capture()
@@ -485,3 +500,116 @@ class EvalStep:
         self.reset()
         view.epoch, view.cursor = epoch + 1, 0
         return means(sums)
+
+    # -- features for unsupervised classification (cluster.py) -------------------------------
+    def _attach_sink(self, sink):
+        """Aim this step's batches at ``sink`` (off while the capture's warm-ups run)."""
+        self.epi.sink = sink
+        if self.use_graph:
+            self.capture()
+
+    def _labels_for(self, labels, lo, hi):
+        if labels is not None:
+            return labels[lo:hi]
+        n = hi - lo
+        if self._zero_labels is None or self._zero_labels.shape[0] != n:
+            self._zero_labels = torch.zeros(n, dtype=torch.long, device=self.device)
+        return self._zero_labels
+
+    def encode(self, images, labels=None, out=None):
+        """The object-capsule features of a whole split, with its evaluation means: every
+        full batch replayed as ``evaluate`` runs it, the remainder through the cached tail
+        step, and each image's two classifier inputs -- ``caps_presence`` and the posterior
+        mass ``posterior_mixing_prob.sum(-1)`` -- stored into a device sink on the way (by the
+        loss tail's per-image launch where SCAE.forward's class probabilities ride in it, else
+        by one launch of its own per batch).  ``images`` may be a data.DatasetView: its rows
+        come out in ``view.materialise()`` order and the view moves on to its next epoch, as
+        with ``evaluate``.
+
+        -> {"prior" (N, O), "posterior" (N, O), "label" (N,) int64 or None, "means"
+        (``evaluate``'s), "rows" (rows written), "overflow"}.  ``out``: an (R, 2, O) fp32
+        device buffer to write into (default: N rows); rows at or beyond R are dropped and
+        ``overflow`` is True.  Without labels the step's loss sees zeros and the accuracies
+        in ``means`` mean nothing."""
+        from .data import DatasetView
+        if world()[1] > 1:
+            raise ValueError("encode gathers one process's rows: world > 1 is not supported")
+        O = self.model.obj_decoder.n_obj_capsules
+        view = images if isinstance(images, DatasetView) else None
+        if view is not None:
+            if not self.cuda:
+                raise ValueError("encoding a device-resident dataset needs a device step")
+            ds = view.dataset
+            if (ds.C, ds.H, ds.W) != self.image_shape:
+                raise ValueError(f"the view gives ({ds.C}, {ds.H}, {ds.W}) images, the step "
+                                 f"takes {self.image_shape}")
+            N = view.n
+            rows, _ = view.rows_and_shifts(view.epoch, torch.arange(N))
+            label = ds.labels[rows.to(ds.device)].to(torch.int64)
+        else:
+            N = images.shape[0]
+            if N == 0 or (labels is not None and labels.shape[0] != N):
+                raise ValueError("images and labels must hold the same number (> 0) of "
+                                 "examples")
+            label = None if labels is None else labels.to(self.device, torch.int64)
+        if out is None:
+            out = torch.empty(N, 2, O, device=self.device)
+        elif out.dim() != 3 or tuple(out.shape[1:]) != (2, O) or \
+                out.dtype != torch.float32 or out.device != self.device or \
+                not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous (R, 2, {O}) fp32 tensor on "
+                             f"{self.device}")
+        B = self.batch_size
+        full, rem = divmod(N, B)
+        tail = self._tail(rem) if rem else None
+        steps = [self] + ([tail] if tail is not None else [])
+        if self.cuda:
+            if self.epi.sink is None:
+                self.epi.sink = ops.EvalSink(self.device)
+            sink = self.epi.sink
+            sink.off()
+            for st in steps:
+                st._attach_sink(sink)
+            sink.point(out)
+        else:
+            for st in steps:
+                st._cpu_rows = []
+        try:
+            self.reset()
+            if view is not None:
+                epoch = view.epoch
+                for i in range(full):
+                    self._run(lambda: self._stage_source(view, epoch, i * B))
+                if tail is not None:
+                    tail._run(lambda: tail._stage_source(view, epoch, full * B, rank=0,
+                                                         standalone=True))
+                view.epoch, view.cursor = epoch + 1, 0
+            else:
+                for i in range(full):
+                    self(images[i * B:(i + 1) * B], self._labels_for(labels, i * B,
+                                                                     (i + 1) * B))
+                if tail is not None:
+                    tail(images[full * B:], self._labels_for(labels, full * B, N))
+            sums = self.acc.clone()
+            if tail is not None:
+                sums += tail.acc
+                tail.reset()
+            self.reset()
+            if self.cuda:
+                cursor, overflow = sink.status()
+                written = min(cursor, out.shape[0])
+            else:
+                got = torch.cat([r for st in steps for r in st._cpu_rows])
+                written = min(N, out.shape[0])
+                out[:written].copy_(got[:written])
+                overflow = N > out.shape[0]
+        finally:
+            if self.cuda:
+                sink.off()
+            else:
+                for st in steps:
+                    st._cpu_rows = None
+        feats = out[:written]
+        return {"prior": feats[:, 0], "posterior": feats[:, 1], "label": label,
+                "means": means(sums), "rows": written, "overflow": overflow,
+                "features": feats}

@@ -2907,7 +2907,12 @@ class _LossTail(torch.autograd.Function):
         if tl is not None:
             probs = (None, None) if label is None else parked.keep[4:6]
             ex.train_log = ctypes.pointer(tl.fused_desc(*probs, label))
-        if parked is not None:    # SCAE.forward's class probabilities ride along
+        if ev is not None and parked is not None and ev.sink is not None:
+            # the image workgroups store the classifier inputs, the epilogue moves the cursor
+            ev.sink_written = True
+            _lib.call("scae_loss_tail_fwd_class_probs_sink_f32", *tail, *parked.args,
+                      ctypes.c_void_p(ev.sink.ptr), _stream(lpp))
+        elif parked is not None:    # SCAE.forward's class probabilities ride along
             _lib.call("scae_loss_tail_fwd_class_probs_f32", *tail, *parked.args,
                       _stream(lpp))
         else:
@@ -3010,11 +3015,17 @@ class EvalEpilogue:
         self.batch3 = torch.zeros(3, device=device, dtype=torch.float32)
         self.fused = False      # the last forward ended in the fused epilogue
         self._keep = None       # what the last launch points into
+        self.sink = None        # EvalSink the batch's classifier inputs go to (or None)
+        self.sink_written = False   # the last forward's fused launches fed the sink
 
     def fused_launch(self, tail, prior, post, keep, stream_ref):
         _need_hip(prior, post)
-        _lib.call("scae_eval_tail_f32", *tail, _p(prior), _p(post), _p(self.acc),
-                  _p(self.batch3), _stream(stream_ref))
+        if self.sink_written:
+            _lib.call("scae_eval_tail_sink_f32", *tail, _p(prior), _p(post), _p(self.acc),
+                      _p(self.batch3), ctypes.c_void_p(self.sink.ptr), _stream(stream_ref))
+        else:
+            _lib.call("scae_eval_tail_f32", *tail, _p(prior), _p(post), _p(self.acc),
+                      _p(self.batch3), _stream(stream_ref))
         self.fused, self._keep = True, (keep, prior, post)
 
     def accumulate(self, loss, out12, prior, post, label):
@@ -3028,6 +3039,48 @@ class EvalEpilogue:
         _lib.call("scae_eval_accumulate_f32", _p(loss), _p(out12), _p(prior), _p(post), lab,
                   B, ncls, _p(self.acc), _p(self.batch3), _stream(loss))
         self._keep = (loss, out12, prior, post, label)
+
+
+class EvalSink:
+    """The evaluation feature sink (include/scae_hip.h, scae_eval_sink): a device descriptor
+    that captured launches reach by its address.  ``point(rows)`` aims it at an (N, 2, O)
+    fp32 output (rows [:, 0] prior presence, [:, 1] posterior mass) with the cursor at 0;
+    ``off()`` sets the capacity to 0 (nothing written, the cursor stays); ``status()`` reads
+    (cursor, overflow) in one transfer.  ``launch_alone``: the rows of a batch whose class
+    probabilities did not ride in the loss tail, and the cursor's advance."""
+
+    def __init__(self, device):
+        self.desc = torch.zeros(_lib.EVAL_SINK_INT64S, device=device, dtype=torch.int64)
+        self.ptr = self.desc.data_ptr()
+        self.rows = None
+
+    def point(self, rows):
+        if rows is not None:
+            if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[1] != 2 \
+                    or not rows.is_contiguous() or rows.device != self.desc.device:
+                raise ValueError("sink rows must be a contiguous (N, 2, O) fp32 tensor on "
+                                 "the sink's device")
+        self.rows = rows
+        n = 0 if rows is None else rows.shape[0]
+        self.desc.copy_(torch.tensor([0 if rows is None else rows.data_ptr(), n, 0, 0],
+                                     dtype=torch.int64))
+
+    def off(self):
+        self.point(None)
+
+    def status(self):
+        v = self.desc[2:4].cpu()
+        return int(v[0]), bool(v[1])
+
+    def launch_alone(self, caps_presence, posterior):
+        """caps_presence (B, O), posterior (B, O + 1, M) (the object decoder's full
+        posterior; its first O rows are read)."""
+        _need_hip(caps_presence, posterior)
+        cp, post = _c(caps_presence.detach()), _c(posterior.detach())
+        B, O1, M = post.shape
+        _lib.call("scae_eval_features_f32", _p(cp), _p(post), B, O1 - 1, M,
+                  ctypes.c_void_p(self.ptr), _stream(cp))
+        self._keep = (cp, post)
 
 
 # The training log's row (include/scae_hip.h, SCAE_TRAIN_LOG_ROW) by SCAE.loss's log keys:
