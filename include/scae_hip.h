@@ -862,7 +862,11 @@ int scae_step_prologue_first_f32(float *dst_image, const float *src_image, int64
  *   out[b, c, i, j] = x[row, c, i - top, j - left] where that pixel exists, else 0,
  *   top = (H - h)/2 + dy, left = (W - w)/2 + dx; uint8 pixels / 255.0f (correctly rounded).
  *   Labels (uint8 or int64) are written as int64.  C <= 4 (else SCAE_ERR_UNSUPPORTED),
- *   h <= H, w <= W, n < 2^31, position + (rank + 1) * B <= n. */
+ *   h <= H, w <= W, n < 2^31, position + (rank + 1) * B <= n.
+ *   wrap 1 (a drop_last=False epoch's short last step, DistributedSampler's padding): a
+ *   position p >= n reads view row perm(p - n) -- the epoch's first examples again -- while
+ *   its shift is still drawn from p itself; then position + (rank + 1) * B <= 2n instead.
+ *   wrap 0 (ctypes' zero): no position may reach n. */
 typedef struct scae_batch_source_desc {
   const void *images;     /* (rows, C, h, w) uint8 (image_u8 = 1) or fp32 in [0, 1] */
   const void *labels;     /* (rows) uint8 (label_u8 = 1) or int64; nullable without labels out */
@@ -875,6 +879,7 @@ typedef struct scae_batch_source_desc {
   uint64_t seed;
   int64_t epoch, position;
   int rank, world;
+  int wrap;               /* 1: positions in [n, 2n) read rows of p - n (see above) */
 } scae_batch_source_desc;
 /* The rank's batch of B from `src` into dst_image (B, C, H, W) fp32 and dst_label (B) int64
  * (nullable), one launch. */

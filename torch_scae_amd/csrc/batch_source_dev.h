@@ -12,6 +12,8 @@
 // than 4 walks on average: 2^k < 4n).  Round r's key is a Philox draw of (seed, epoch, r); its
 // round function is 3 Philox rounds of the right half under that key.  It is NOT a uniform
 // draw over all n! orders.  shuffle = 0: the identity (the reference's DataLoaders).
+// wrap = 1: a position p in [n, 2n) -- the padding of a drop_last=False epoch's short last
+// step -- takes the row of p - n (both orders) and keeps p for its shift draw.
 // Shifts: two 24-bit uniforms r of one Philox draw keyed by seed at counter (p, epoch, tag);
 // shift = round half to even of 2*pad*r / 2^24 - pad, in integers (torchvision's
 // round(U(-pad, pad))), pad = (H - h) / 2 per axis; translate = 0: no shift.
@@ -53,7 +55,8 @@ __device__ __forceinline__ Draw draw(const scae_batch_source_desc &s, int64_t p)
   if (lane == 4) c[0] = (uint32_t)p, c[3] = TAG_SHIFT;
   scae_src::philox(c, (uint32_t)s.seed, (uint32_t)(s.seed >> 32), KEY_PHILOX_ROUNDS);
   Draw d;
-  uint32_t x = (uint32_t)p;
+  // (wrap: p mod n for the row, the unwrapped p for the shift above -- check() bounds p < 2n)
+  uint32_t x = (uint32_t)(s.wrap && p >= s.n ? p - s.n : p);
   if (s.shuffle && s.n > 1) {
     int k = 0;
     while ((1ll << k) < s.n) k += 2;
@@ -121,7 +124,8 @@ inline int check(const scae_batch_source_desc *s, int B) {
   SCAE_REQUIRE(a.C > 0 && a.h > 0 && a.w > 0 && a.h <= a.H && a.w <= a.W);
   SCAE_REQUIRE(a.world > 0 && a.rank >= 0 && a.rank < a.world && a.epoch >= 0 &&
                a.position >= 0);
-  SCAE_REQUIRE(a.position + (int64_t)(a.rank + 1) * B <= a.n);
+  SCAE_REQUIRE(a.wrap == 0 || a.wrap == 1);
+  SCAE_REQUIRE(a.position + (int64_t)(a.rank + 1) * B <= (a.wrap ? 2 * a.n : a.n));
   SCAE_REQUIRE((a.image_u8 == 0 || a.image_u8 == 1) && (a.label_u8 == 0 || a.label_u8 == 1));
   if (a.C > 4) return SCAE_ERR_UNSUPPORTED;
   return 0;

@@ -219,15 +219,15 @@ class ResidentDataset:
     def __len__(self):
         return self.n
 
-    def view(self, shuffle=False, translate=True, seed=0, rank=0, world=1):
+    def view(self, shuffle=False, translate=True, seed=0, rank=0, world=1, drop_last=True):
         """The whole dataset as one view (``DatasetView``)."""
-        return DatasetView(self, None, shuffle, translate, seed, rank, world)
+        return DatasetView(self, None, shuffle, translate, seed, rank, world, drop_last)
 
     def split(self, lengths, generator=None, **view_args):
         """Views over the rows ``torch.utils.data.random_split(range(N), lengths,
         generator)`` gives (``torch.randperm(N, generator=generator)`` cut in turn); lengths
-        are integers summing to N.  ``view_args`` (shuffle, translate, seed, rank, world)
-        apply to every view; a view's attributes can be changed afterwards."""
+        are integers summing to N.  ``view_args`` (shuffle, translate, seed, rank, world,
+        drop_last) apply to every view; a view's attributes can be changed afterwards."""
         lengths = [int(v) for v in lengths]
         if sum(lengths) != self.n or any(v <= 0 for v in lengths):
             raise ValueError("lengths must be positive and sum to the dataset's size")
@@ -249,14 +249,19 @@ class DatasetView:
     test view ``translate=False`` for centred padding.
 
     Rank sharding: step s of an epoch takes the global batch of world*B positions from
-    s*world*B; rank r takes slots [r*B, (r+1)*B).  An epoch has n // (world*B) steps and
-    training drops the remainder (a captured step has a fixed batch; the reference keeps it,
-    ``drop_last=False``) -- without shuffling the same last examples are skipped every epoch.
+    s*world*B; rank r takes slots [r*B, (r+1)*B).  An epoch has spe = n // (world*B) such
+    full steps.  ``drop_last`` (the default) ends it there: the r = n - spe*world*B last
+    positions are not trained -- without shuffling the same examples every epoch.
+    ``drop_last=False`` -- the reference's loaders (base_experiment.py:79-82) -- adds one
+    short step when r > 0: each rank takes b = ceil(r / world) positions, rank k those from
+    spe*world*B + k*b, and a position p >= n reads the row of p - n (the epoch's first
+    examples again, as DistributedSampler pads) with a shift drawn from p itself.  A
+    ``TrainStep`` runs that step on its remainder step of batch b.
     ``epoch`` / ``cursor`` (steps taken in the epoch) advance with ``TrainStep.step_from``;
     ``state_dict`` carries them so that a resumed run continues in the same order."""
 
     def __init__(self, dataset, index=None, shuffle=False, translate=True, seed=0, rank=0,
-                 world=1):
+                 world=1, drop_last=True):
         self.dataset = dataset
         if index is not None:
             index = torch.as_tensor(index).to("cpu", torch.int64).contiguous()
@@ -272,6 +277,9 @@ class DatasetView:
         self.shuffle, self.translate = bool(shuffle), bool(translate)
         self.seed = int(seed) & ((1 << 64) - 1)
         self.rank, self.world = int(rank), int(world)
+        self.drop_last = bool(drop_last)
+        if not self.drop_last and self.n < self.world:
+            raise ValueError(f"{self.n} examples cannot give each of {self.world} ranks one")
         self.epoch = self.cursor = 0
 
     def __len__(self):
@@ -279,16 +287,36 @@ class DatasetView:
 
     # -- the order ------------------------------------------------------------------------
     def steps_per_epoch(self, batch):
+        """Full steps of ``batch`` per rank in an epoch."""
         return self.n // (self.world * batch)
 
+    def remainder(self, batch):
+        """Each rank's batch in the epoch's short last step: ceil(r / world) of the r
+        positions the full steps leave; 0 with ``drop_last`` or when nothing is left."""
+        if self.drop_last:
+            return 0
+        r = self.n - self.steps_per_epoch(batch) * self.world * batch
+        return -(-r // self.world)
+
+    def steps_in_epoch(self, batch):
+        """The epoch's steps: the full ones, plus the short one when there is one."""
+        return self.steps_per_epoch(batch) + (self.remainder(batch) > 0)
+
     def positions(self, step, batch):
-        """Epoch positions of this rank's slots in step ``step``."""
+        """Epoch positions of this rank's slots in step ``step`` (``step`` =
+        ``steps_per_epoch(batch)`` with a remainder: the short step's, unwrapped -- they may
+        reach past n)."""
+        b = self.remainder(batch) if step == self.steps_per_epoch(batch) else 0
+        if b:
+            return step * self.world * batch + self.rank * b + torch.arange(b)
         return step * self.world * batch + self.rank * batch + torch.arange(batch)
 
     def rows_and_shifts(self, epoch, positions):
-        """(dataset rows, (len, 2) shifts) of epoch positions -- the CPU path."""
+        """(dataset rows, (len, 2) shifts) of epoch positions -- the CPU path.  Without
+        ``drop_last`` a position p >= n takes the row of p - n and keeps p for its shift."""
         p = torch.as_tensor(positions, dtype=torch.int64)
-        vr = feistel_order(p, self.n, self.seed, epoch) if self.shuffle else p
+        q = p if self.drop_last else torch.where(p >= self.n, p - self.n, p)
+        vr = feistel_order(q, self.n, self.seed, epoch) if self.shuffle else q
         rows = vr if self.index is None else self.index[vr]
         ds = self.dataset
         shifts = translate_shifts(p, epoch, self.seed, ds.pads) if self.translate \
@@ -307,7 +335,8 @@ class DatasetView:
 
     def batch(self, epoch, step, batch):
         """This rank's batch of step ``step`` of ``epoch`` on the CPU: (image (B, C, H, W)
-        fp32, label (B,) int64) -- what the device gather writes, bit for bit."""
+        fp32, label (B,) int64) -- what the device gather writes, bit for bit.  ``step`` =
+        ``steps_per_epoch(batch)`` without ``drop_last``: the short step's (b, ...)."""
         return self._cpu_batch(epoch, self.positions(step, batch))
 
     def materialise(self, epoch=None):
@@ -331,6 +360,7 @@ class DatasetView:
         d.shuffle, d.translate = int(self.shuffle), int(self.translate)
         d.seed, d.epoch, d.position = self.seed, int(epoch), int(position)
         d.rank, d.world = self.rank if rank is None else rank, self.world
+        d.wrap = int(not self.drop_last)
         return d
 
     def check(self, batch, image_shape):
@@ -340,7 +370,7 @@ class DatasetView:
                              f"takes {tuple(image_shape)}")
         if ds.device.type != "cuda":
             raise ValueError("a step reads a dataset held on the device")
-        if self.steps_per_epoch(batch) == 0:
+        if self.steps_in_epoch(batch) == 0:
             raise ValueError(f"{self.n} examples make no batch of {batch} x {self.world} ranks")
 
     def gather(self, batch, epoch=None, step=None, image=None, label=None, rank=None,
@@ -365,21 +395,25 @@ class DatasetView:
         return image, label
 
     def take_step(self, batch):
-        """(epoch, position) of the next step's global batch; advances the cursor, wrapping
-        to the next epoch after ``steps_per_epoch(batch)`` steps."""
-        spe = self.steps_per_epoch(batch)
-        if self.cursor >= spe:          # (a state loaded for another batch size)
+        """(epoch, position) of the next step's global batch, with ``.size`` the rank's
+        batch in it (``batch``, or ``remainder(batch)`` for the short step); advances the
+        cursor, wrapping to the next epoch after ``steps_in_epoch(batch)`` steps."""
+        spe, last = self.steps_per_epoch(batch), self.steps_in_epoch(batch)
+        if self.cursor >= last:         # (a state loaded for another batch size)
             self.epoch, self.cursor = self.epoch + 1, 0
-        out = (self.epoch, self.cursor * self.world * batch)
+        size = batch if self.cursor < spe else self.remainder(batch)
+        out = StepAt(self.epoch, self.cursor * self.world * batch, size)
         self.cursor += 1
-        if self.cursor == spe:
+        if self.cursor == last:
             self.epoch, self.cursor = self.epoch + 1, 0
         return out
 
     def state_dict(self):
+        """The cursor says where the epoch stands: with ``drop_last=False`` a cursor of
+        ``steps_per_epoch(B)`` is a short step still to come."""
         return {"epoch": self.epoch, "cursor": self.cursor, "seed": self.seed,
                 "shuffle": self.shuffle, "translate": self.translate, "n": self.n,
-                "rank": self.rank, "world": self.world}
+                "rank": self.rank, "world": self.world, "drop_last": self.drop_last}
 
     def load_state_dict(self, sd):
         if sd.get("n", self.n) != self.n or sd.get("world", self.world) != self.world:
@@ -387,7 +421,18 @@ class DatasetView:
         self.seed = int(sd.get("seed", self.seed))
         self.shuffle = bool(sd.get("shuffle", self.shuffle))
         self.translate = bool(sd.get("translate", self.translate))
+        self.drop_last = bool(sd.get("drop_last", self.drop_last))
         self.epoch, self.cursor = int(sd["epoch"]), int(sd["cursor"])
+
+
+class StepAt(tuple):
+    """(epoch, position) of a step's global batch, as ``DatasetView.take_step`` hands it out;
+    ``size``: the rank's batch in that step."""
+
+    def __new__(cls, epoch, position, size):
+        out = super().__new__(cls, (epoch, position))
+        out.size = size
+        return out
 
 
 _IDX_TYPES = {0x08: torch.uint8, 0x09: torch.int8, 0x0B: torch.int16, 0x0C: torch.int32,

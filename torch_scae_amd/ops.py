@@ -273,7 +273,7 @@ def reset_noise():
     for plan in step_plan.live_plans():
         for key, (seed, state) in list(plan.noise.items()):
             # in place: captured graphs and prologues hold this tensor's address
-            fresh = int(torch.initial_seed()) & ((1 << 63) - 1)
+            fresh = (int(torch.initial_seed()) ^ plan.noise_salt) & ((1 << 63) - 1)
             state.copy_(torch.tensor([fresh, 0, 0], dtype=torch.int64))
             plan.noise[key] = (fresh, state)
 
@@ -282,11 +282,12 @@ def uniform(n, ref):
     """n floats ~ U[0,1) on ``ref``'s device from the device-resident Philox
     generator (csrc/noise.hip).  Seeded from ``torch.initial_seed()``; the
     generator state is per (device, stream) and restarts when that seed
-    changes (``torch.manual_seed``) outside a graph capture."""
+    changes (``torch.manual_seed``) outside a graph capture; the plan's
+    ``noise_salt`` is XORed into the seed."""
     _need_hip(ref)
-    seed = int(torch.initial_seed()) & ((1 << 63) - 1)
-    key = (ref.device, torch.cuda.current_stream(ref.device).cuda_stream)
     plan = _plan()
+    seed = (int(torch.initial_seed()) ^ plan.noise_salt) & ((1 << 63) - 1)
+    key = (ref.device, torch.cuda.current_stream(ref.device).cuda_stream)
     state = plan.noise.get(key)
     if state is None or (state[0] != seed and
                          not torch.cuda.is_current_stream_capturing()):

@@ -149,6 +149,9 @@ class StepPlan:
         self.prologue = prologue  # ops.StepPrologue or None
         self.bf16 = False         # configs[2]'s operand precision
         self.noise = {}           # (device, stream) -> (seed, generator state)
+        # XORed into torch's seed for this plan's generators (0: the seed itself; a training
+        # step's remainder step salts its own so that its draws are not the full step's)
+        self.noise_salt = 0
         self.side_stream = None   # torch.cuda.Stream of the second lane (None: one lane)
         # resident workgroups of the side lane's K1 backward (scae_decoder_desc.bwd_resident;
         # 0: one workgroup per (component, image) pair, which floods the chip)

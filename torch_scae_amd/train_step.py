@@ -7,6 +7,7 @@ Mirrors the semantics of the reference's BaseExperiment.training_step
 (torch_scae_experiments/base_experiment.py:109-126)."""
 import contextlib
 import os
+import weakref
 
 import torch
 import torch.distributed as dist
@@ -16,6 +17,10 @@ from .data_parallel import (FlatParameters, all_reduce_gradients,
                             broadcast_parameters, load_optimizer_state_dict,
                             make_optimizer, optimizer_state_dict, world)
 
+
+# the remainder step's noise generators: keyed by torch's seed XOR this (step_plan.StepPlan.
+# noise_salt), so that its draws do not repeat the full step's
+REMAINDER_NOISE_SALT = 0x52454D41494E4452 & ((1 << 63) - 1)
 
 # parameters whose gradients are final once backward has come down through
 # the two decoders (the object decoder's capsule MLPs alone are 66 % of the
@@ -92,6 +97,15 @@ class TrainStep:
     operator more: ``step_from`` / ``replay="launches"`` keep their form); other models log
     with one launch of their own (scae_train_log_f32).  ``last_log()``,
     ``log_history()``, ``training_epoch_end()``, ``reset_log()``.  Rows are rank-local.
+
+    A batch of 1 <= b < B (a ``drop_last=False`` loader's last batch, a view's short step)
+    runs on the step's remainder step (``remainder_step(b)``): a second step of batch b,
+    built on first use and cached (the last b only), that trains the same parameters with
+    the same optimiser -- its moments, step count, LookAhead's slow weights, learning rate
+    and the eps of THIS step's B (base_experiment.py:47) -- writes the same training log and
+    counts in the same ``steps``.  It has its own input buffers, graph(s) or launch list,
+    prologue and noise draws.  Not padded: the loss's between-example terms depend on the
+    batch size.
     """
 
     MODES = ("2 buckets", "1 bucket", "in graph")
@@ -106,6 +120,8 @@ class TrainStep:
                  log_steps=0):
         if not isinstance(log_steps, int) or isinstance(log_steps, bool) or log_steps < 0:
             raise ValueError(f"log_steps must be an int >= 0, got {log_steps!r}")
+        self._parent = None      # (a remainder step: the step whose state it shares)
+        self._rem = None         # the cached remainder step (remainder_step)
         self.model = model
         self.device = next(model.parameters()).device
         if log_steps and self.device.type != "cuda":
@@ -168,7 +184,8 @@ class TrainStep:
             look_ahead=look_ahead, look_ahead_k=look_ahead_k,
             look_ahead_alpha=look_ahead_alpha) \
             if optimizer not in (None, False) else None
-        self.steps = 0           # steps taken (host count; the optimisers keep their own)
+        self.steps = 0           # steps taken (host count, with the remainder step's; the
+        #                          optimisers keep their own)
         # the training log (ops.TrainLog): ring, step counter, epoch accumulator
         self.train_log = ops.TrainLog(
             log_steps, self.device, lr=None if self.opt is None else self.opt.lr_dev) \
@@ -232,6 +249,78 @@ class TrainStep:
         self.graph = None        # the whole step, or its part A when split
         self.graph_b = None
         self._cut = None
+
+    @property
+    def steps(self):
+        return self._steps if self._parent is None else self._parent.steps
+
+    @steps.setter
+    def steps(self, value):
+        if self._parent is None:
+            self._steps = value
+        else:
+            self._parent.steps = value
+
+    # -- the remainder step ---------------------------------------------------
+    def remainder_step(self, size):
+        """The step that runs this step's batches of ``size`` (1 <= size < B): built on the
+        first call for that size and cached -- only the last size: another one rebuilds it.
+        ``capture()`` on it builds its graph(s) ahead of the first short batch (its warm-ups
+        draw from its own noise generator, as this step's do)."""
+        if self._parent is not None:
+            raise ValueError("a remainder step has no remainder step of its own")
+        B = self.image.shape[0]
+        if not (isinstance(size, int) and 1 <= size < B):
+            raise ValueError(f"a remainder batch holds 1 .. {B - 1} examples, got {size!r}")
+        rem = self._rem
+        if rem is None or rem.image.shape[0] != size:
+            if rem is not None:
+                rem._free_list()
+            self._rem = None
+            rem = self._rem = self._remainder_of(size)
+        if self._with_log and not rem._with_log:
+            rem._with_log, rem.graph, rem.graph_b = True, None, None
+        return rem
+
+    def _remainder_of(self, size):
+        """A step of batch ``size`` sharing this step's training state: the model and its
+        FlatParameters (a second one would re-home the parameters under this step's captured
+        graph), the optimiser object, the training log, the host step count, the capture
+        stream (autograd keeps each parameter's AccumulateGrad node with the stream it first
+        ran on) and every setting.  Its own: plan, prologue, input buffers, graph(s) / launch
+        list and noise generators (salted: its draws are not this step's)."""
+        rem = TrainStep.__new__(TrainStep)
+        rem.__dict__.update(self.__dict__)
+        if self._stream is None and self.device.type == "cuda":
+            self._stream = torch.cuda.Stream(self.device)
+        rem._stream = self._stream
+        # (a weak reference: a cycle would leave both steps to the cyclic collector, whose
+        # run may then free their graphs in the middle of another step's capture)
+        rem._parent, rem._rem = weakref.proxy(self), None
+        rem._pro = ops.StepPrologue() if self._pro is not None else None
+        rem.plan = ops.StepPlan("train step remainder", prologue=rem._pro)
+        rem.plan.sums_to_optimizer = self.plan.sums_to_optimizer
+        rem.plan.side_stream = self.plan.side_stream
+        rem.plan.noise_salt = REMAINDER_NOISE_SALT
+        rem.image = torch.zeros(size, *self.image.shape[1:], device=self.device)
+        rem.label = torch.zeros(size, dtype=torch.long, device=self.device)
+        rem.loss = torch.zeros((), device=self.device)
+        rem.log = None
+        rem._launches = rem._klist = rem.graph_nodes = None
+        rem.graph = rem.graph_b = rem._cut = None
+        rem._capturing = rem._warming = False
+        return rem
+
+    def _for_batch(self, size):
+        """The step that runs a batch of ``size``: this one, or its remainder step."""
+        B = self.image.shape[0]
+        if size == B:
+            return self
+        if self._parent is not None or not 1 <= size < B:
+            raise ValueError(f"a step of batch {B} takes batches of 1 .. {B} examples, "
+                             f"got {size}" if self._parent is None else
+                             f"a remainder step takes batches of {B} only, got {size}")
+        return self.remainder_step(int(size))
 
     @contextlib.contextmanager
     def _lazy(self):
@@ -302,6 +391,8 @@ class TrainStep:
         if unknown:
             raise ValueError(f"log keys {unknown} have no place in the training log's row")
         self._log_keys = keys
+        if self._parent is not None:
+            self._parent._log_keys = keys
         if tlog.fused:
             return
         from .eval_step import out12_from_log
@@ -633,20 +724,23 @@ class TrainStep:
         ResidentDataset on this step's device): the batch is gathered -- order, padding
         and shifts applied -- in the step's prologue launch, with no torch operator and no
         host-to-device copy.  Advances the view's cursor and wraps to its next epoch after
-        ``view.steps_per_epoch(batch)`` steps (the LR decays in ``end_epoch``).  -> the
-        loss (a device tensor the next step overwrites)."""
+        ``view.steps_in_epoch(batch)`` steps (the LR decays in ``end_epoch``); a
+        ``drop_last=False`` view's short step runs on the remainder step, gathered the same
+        way.  -> the loss (a device tensor the next step overwrites)."""
         B = self.image.shape[0]
         view.check(B, self.image.shape[1:])
         if self.world > 1 and (view.rank, view.world) != world():
             raise ValueError(f"view of rank {view.rank} / world {view.world} in a step "
                              f"of rank {world()[0]} / world {self.world}")
-        epoch, position = view.take_step(B)
-        self._stage_source(view, epoch, position)
-        return self._step_staged()
+        at = view.take_step(B)
+        step = self._for_batch(at.size)
+        step._stage_source(view, *at)
+        return step._step_staged()
 
     def train_epoch(self, view):
-        """The view's remaining steps of its current epoch (``step_from``), then
-        ``end_epoch()``.  -> the last step's loss (a device tensor)."""
+        """The view's remaining steps of its current epoch (``step_from``: the full ones,
+        then the short one of a ``drop_last=False`` view), then ``end_epoch()`` once.
+        -> the last step's loss (a device tensor)."""
         B = self.image.shape[0]
         view.check(B, self.image.shape[1:])
         epoch, loss = view.epoch, None
@@ -656,9 +750,11 @@ class TrainStep:
         return loss
 
     def __call__(self, image, label):
-        """image / label may be device tensors; copied into the static inputs."""
-        self._stage(image, label)
-        return self._step_staged()
+        """image / label may be device tensors; copied into the static inputs.  A batch of
+        1 <= b < B runs on the remainder step."""
+        step = self._for_batch(image.shape[0])
+        step._stage(image, label)
+        return step._step_staged()
 
     def _step_staged(self):
         self.steps += 1
@@ -693,8 +789,9 @@ class TrainStep:
         first use (costs a few extra small kernels per step)."""
         if not self._with_log:
             self._with_log, self.graph, self.graph_b = True, None, None
-        loss = self(image, label)
-        return dict(loss=loss, log=self.log)
+        step = self._for_batch(image.shape[0])
+        loss = step(image, label)
+        return dict(loss=loss, log=step.log)
 
     # -- the training log (log_steps) ---------------------------------------------
     def _need_log(self):
