@@ -797,6 +797,44 @@ int scae_flat_opt_sums_step_f32(float *param, float *grad, float *exp_avg, float
                                 float look_ahead_alpha, const struct scae_sum_job *jobs,
                                 int n_jobs, void *stream);
 
+/* Gradient clipping by global norm -- torch.nn.utils.clip_grad_norm_(params, max_norm), which
+ * Lightning's Trainer(gradient_clip_val) applies between backward and the optimiser step:
+ *   total = || g ||_2 over every parameter gradient,  coef = min(1, max_norm / (total + 1e-6)),
+ *   g <- coef g.
+ * In two launches: scae_grad_sq_partials_f32 writes *n_partials (<= max_partials; a function
+ * of n -- and of the jobs -- only) fp64 partial sums of g^2 over the n floats of `grad` (any
+ * 4-byte aligned start) into `partials`; the clip forms of the optimiser passes below reduce
+ * them in every workgroup in one fixed order (fp64), form total = grad_scale sqrt(sum) and
+ * coef in fp32 and apply g <- coef (grad_scale g) before the weight decay.  No atomics: the
+ * same inputs give the same bits.  With coef == 1 (max_norm above the norm) the clip forms
+ * equal the plain passes bit for bit. */
+#define SCAE_GRAD_SQ_MAX_PARTIALS 4096
+int scae_grad_sq_partials_f32(const float *grad, int64_t n, double *partials, int max_partials,
+                              int *n_partials, void *stream);
+
+/* The step's last column sums riding in the norm launch (as scae_rmsprop_sums_step_f32 hosts
+ * them in the optimiser pass): the sums equal scae_sum_rows_multi_f32's bit for bit, and those
+ * whose destinations lie in `grad` are counted in the partials. */
+int scae_grad_sq_partials_sums_f32(float *grad, int64_t n, double *partials, int max_partials,
+                                   int *n_partials, const struct scae_sum_job *jobs, int n_jobs,
+                                   void *stream);
+
+/* scae_rmsprop_step_f32 / scae_flat_opt_step_f32 with g scaled by the clip coefficient of the
+ * norm launch's `partials` (max_norm > 0).  `norm_out` (device float, may be NULL): the
+ * norm before clipping, written by the launch's first workgroup. */
+int scae_rmsprop_clip_step_f32(float *param, const float *grad, float *square_avg, float *buf,
+                               int64_t n, float lr, const float *lr_dev, float alpha, float eps,
+                               float momentum, float weight_decay, float grad_scale,
+                               const double *partials, int n_partials, float max_norm,
+                               float *norm_out, void *stream);
+int scae_flat_opt_clip_step_f32(float *param, const float *grad, float *exp_avg,
+                                float *exp_avg_sq, float *slow, int64_t n, const float *lr_dev,
+                                int32_t *step_state, int kind, double beta1, double beta2,
+                                float eps, float weight_decay, float grad_scale,
+                                int look_ahead_k, float look_ahead_alpha, int advance,
+                                const double *partials, int n_partials, float max_norm,
+                                float *norm_out, void *stream);
+
 /* The batch hand-over of a training step (base_experiment.py:109-112): n_image
  * floats and n_label int64 labels (device memory) into the step's resident
  * input buffers, in one launch. */

@@ -291,6 +291,14 @@ SIGNATURES = {
                                c_float, c_float, c_int, c_float, c_int, P],
     "scae_flat_opt_sums_step_f32": [P, P, P, P, P, c_int64, P, P, c_int, c_double, c_double,
                                     c_float, c_float, c_int, c_float, POINTER(SumJob), c_int, P],
+    "scae_grad_sq_partials_f32": [P, c_int64, P, c_int, POINTER(c_int), P],
+    "scae_grad_sq_partials_sums_f32": [P, c_int64, P, c_int, POINTER(c_int), POINTER(SumJob),
+                                       c_int, P],
+    "scae_rmsprop_clip_step_f32": [P, P, P, P, c_int64, c_float, P, c_float, c_float, c_float,
+                                   c_float, c_float, P, c_int, c_float, P, P],
+    "scae_flat_opt_clip_step_f32": [P, P, P, P, P, c_int64, P, P, c_int, c_double, c_double,
+                                    c_float, c_float, c_float, c_int, c_float, c_int, P, c_int,
+                                    c_float, P, P],
     "scae_capsule_head_fwd_f32": [P, P, c_float, c_int, P, P, P, P, P] + [c_int] * 4 + [P],
     "scae_capsule_head_conv_supported": [c_int] * 4,
     "scae_capsule_head_conv_preferred": [c_int] * 5,
@@ -367,6 +375,7 @@ TRAIN_LOG_ROW = 19           # SCAE_TRAIN_LOG_ROW: one row of scae_train_log_des
 KMEANS_STATE_INTS = 4        # SCAE_KMEANS_STATE_INTS: per restart of scae_kmeans_desc's state
 EVAL_SINK_INT64S = 4         # struct scae_eval_sink: rows, capacity, cursor, overflow
 FLAT_OPT_STATE_INTS = 2112   # SCAE_FLAT_OPT_STATE_INTS: the step_state of scae_flat_opt_*
+GRAD_SQ_MAX_PARTIALS = 4096  # SCAE_GRAD_SQ_MAX_PARTIALS: scae_grad_sq_partials_*
 ABI_VERSION = 2     # SCAE_ABI_VERSION of the include/scae_hip.h this binding mirrors
 
 _lib = None

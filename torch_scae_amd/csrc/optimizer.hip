@@ -7,7 +7,9 @@
 //   p   <- p - lr buf                    (momentum == 0: p <- p - lr g / (sqrt(v)+eps))
 // with g <- g + weight_decay p first, as torch does; lr optionally read from device memory.
 // HBM-bound: 4 streams read, 3 written, 28 bytes per parameter.
-#include "sum_rows_dev.h"
+// The clip form (scae_rmsprop_clip_step_f32) scales g by clip_grad_norm_'s coefficient from
+// the norm launch's partials (grad_clip_dev.h) after grad_scale, before the weight decay.
+#include "grad_clip_dev.h"
 
 namespace {
 struct OptArgs {
@@ -21,9 +23,11 @@ struct OptArgs {
 // (no FMA contraction: the update is compiled into three kernels -- vector, scalar edge, the
 // sum workgroups of rmsprop_sums_kernel -- that must round alike, bit for bit)
 #pragma clang fp contract(off)
+template <bool CLIP = false>
 __device__ __forceinline__ void update(float &p, float &v, float &b, float g, const OptArgs &a,
-                                       float lr) {
+                                       float lr, float coef = 1.f) {
   g *= a.grad_scale;  // e.g. 1/world_size after a SUM all-reduce
+  if (CLIP) g *= coef;   // clip_grad_norm_ (exact for coef == 1: the unclipped pass's bits)
   if (a.weight_decay != 0.f) g = fmaf(a.weight_decay, p, g);  // torch: grad.add(param, alpha=wd)
   v = a.alpha * v + (1.f - a.alpha) * g * g;
   const float step = g / (sqrtf(v) + a.eps);
@@ -36,8 +40,9 @@ __device__ __forceinline__ void update(float &p, float &v, float &b, float g, co
 }
 
 // `head` leading elements bring the (equally misaligned) buffers to a 16-byte
-// boundary; then float4 lanes; then the tail
-__global__ __launch_bounds__(256) void rmsprop_kernel(OptArgs a, int head) {
+// boundary; then float4 lanes; then the tail.  CLIP: g scaled by `coef`
+template <bool CLIP>
+__device__ __forceinline__ void rmsprop_pass(OptArgs a, int head, float coef) {
   const long stride = (long)gridDim.x * blockDim.x;
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const float lr = a.lr_dev ? a.lr_dev[0] : a.lr;
@@ -48,10 +53,10 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(OptArgs a, int head) {
     float4 p = reinterpret_cast<float4 *>(p4)[i], v = reinterpret_cast<float4 *>(v4)[i];
     float4 b = b4 ? reinterpret_cast<float4 *>(b4)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 g = reinterpret_cast<const float4 *>(g4)[i];
-    update(p.x, v.x, b.x, g.x, a, lr);
-    update(p.y, v.y, b.y, g.y, a, lr);
-    update(p.z, v.z, b.z, g.z, a, lr);
-    update(p.w, v.w, b.w, g.w, a, lr);
+    update<CLIP>(p.x, v.x, b.x, g.x, a, lr, coef);
+    update<CLIP>(p.y, v.y, b.y, g.y, a, lr, coef);
+    update<CLIP>(p.z, v.z, b.z, g.z, a, lr, coef);
+    update<CLIP>(p.w, v.w, b.w, g.w, a, lr, coef);
     reinterpret_cast<float4 *>(p4)[i] = p;
     reinterpret_cast<float4 *>(v4)[i] = v;
     if (b4) reinterpret_cast<float4 *>(b4)[i] = b;
@@ -61,9 +66,18 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(OptArgs a, int head) {
   for (long e = tid; e < edge; e += stride) {
     const long i = e < head ? e : tail0 + (e - head);
     float b = a.buf ? a.buf[i] : 0.f;
-    update(a.p[i], a.v[i], b, a.g[i], a, lr);
+    update<CLIP>(a.p[i], a.v[i], b, a.g[i], a, lr, coef);
     if (a.buf) a.buf[i] = b;
   }
+}
+__global__ __launch_bounds__(256) void rmsprop_kernel(OptArgs a, int head) {
+  rmsprop_pass<false>(a, head, 1.f);
+}
+// the clip form: every workgroup first reduces the norm launch's partials to the coefficient
+// (the same bits in every workgroup)
+__global__ __launch_bounds__(256) void rmsprop_clip_kernel(OptArgs a, int head,
+                                                           scae_clip::Clip clip) {
+  rmsprop_pass<true>(a, head, scae_clip::clip_coef(clip, a.grad_scale));
 }
 // The step's LAST column sums and the optimiser in one launch.  A training step's backward
 // ends in one scae_sum_rows_multi launch whose outputs are slots of the flat gradient buffer
@@ -74,7 +88,7 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(OptArgs a, int head) {
 // gradient base); the streaming workgroups behind them skip exactly those elements -- the
 // segments' destination ranges, rebuilt from the job table into LDS by every workgroup.  The
 // arithmetic per element is unchanged: the results equal the two launches' bit for bit.
-constexpr int MAXR = scae_sums::MAXJOBS * 8;
+using scae_sums::MAXR;
 __global__ __launch_bounds__(256) void rmsprop_sums_kernel(OptArgs a, int head,
                                                            scae_sums::Jobs jobs, int sum_blocks) {
   __shared__ float red[scae_sums::NT];
@@ -93,24 +107,8 @@ __global__ __launch_bounds__(256) void rmsprop_sums_kernel(OptArgs a, int head,
     });
     return;
   }
-  // the ranges of the flat buffers the sum workgroups own (a thread per segment)
-  if (threadIdx.x == 0) r_n = 0;
-  __syncthreads();
-  if (threadIdx.x < MAXR) {
-    const int j = threadIdx.x >> 3, i = threadIdx.x & 7;
-    if (j < jobs.n && i < jobs.j[j].n) {
-      const scae_sums::Seg &g = jobs.j[j].s[i];
-      const long width = g.end - g.begin;
-      const long len = g.period > 0 ? (long)(jobs.j[j].cols / g.period) * width : width;
-      const long lo = g.dst - a.g;
-      if (lo + len > 0 && lo < a.n) {
-        const int k = atomicAdd(&r_n, 1);   // (order is irrelevant: membership only)
-        r_lo[k] = (int)max(lo, 0l), r_hi[k] = (int)min(lo + len, a.n);
-      }
-    }
-  }
-  __syncthreads();
-  const int nr = r_n;
+  // the ranges of the flat buffers the sum workgroups own
+  const int nr = scae_sums::owned_ranges(jobs, a.g, a.n, r_lo, r_hi, &r_n);
   const long stride = (long)(gridDim.x - sum_blocks) * blockDim.x;
   const long tid = (long)(blockIdx.x - sum_blocks) * blockDim.x + threadIdx.x;
   const long n4 = (a.n - head) >> 2;
@@ -123,11 +121,7 @@ __global__ __launch_bounds__(256) void rmsprop_sums_kernel(OptArgs a, int head,
     const float4 g = reinterpret_cast<const float4 *>(g4)[i];
     const int e0 = head + 4 * (int)i;
     // bit u: element e0 + u belongs to a sum workgroup
-    int own = 0;
-    for (int k = 0; k < nr; ++k) {
-      const int lo = r_lo[k] - e0, hi = r_hi[k] - e0;   // the range relative to the quad
-      if (hi > 0 && lo < 4) own |= ((hi >= 4 ? 15 : (1 << hi) - 1) & ~((lo <= 0 ? 0 : (1 << lo) - 1)));
-    }
+    const int own = scae_sums::quad_owned(e0, r_lo, r_hi, nr);
     if (own == 15) continue;
     update(p.x, v.x, b.x, g.x, a, lr);
     update(p.y, v.y, b.y, g.y, a, lr);
@@ -151,9 +145,7 @@ __global__ __launch_bounds__(256) void rmsprop_sums_kernel(OptArgs a, int head,
   const long tail0 = head + (n4 << 2), edge = head + (a.n - tail0);
   for (long e = tid; e < edge; e += stride) {
     const long i = e < head ? e : tail0 + (e - head);
-    bool owned = false;
-    for (int k = 0; k < nr; ++k) owned |= i >= r_lo[k] && i < r_hi[k];
-    if (owned) continue;
+    if (scae_sums::owned(i, r_lo, r_hi, nr)) continue;
     float b = a.buf ? a.buf[i] : 0.f;
     update(a.p[i], a.v[i], b, a.g[i], a, lr);
     if (a.buf) a.buf[i] = b;
@@ -212,6 +204,31 @@ extern "C" int scae_rmsprop_step_f32(float *param, const float *grad, float *squ
   blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
   scae::launch(rmsprop_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a,
                      head);
+  return scae_launch_status();
+}
+
+// scae_rmsprop_step_f32 with g scaled by clip_grad_norm_'s coefficient (grad_clip_dev.h)
+extern "C" int scae_rmsprop_clip_step_f32(float *param, const float *grad, float *square_avg,
+                                          float *buf, int64_t n, float lr, const float *lr_dev,
+                                          float alpha, float eps, float momentum,
+                                          float weight_decay, float grad_scale,
+                                          const double *partials, int n_partials, float max_norm,
+                                          float *norm_out, void *stream) {
+  SCAE_REQUIRE(param && grad && square_avg && n > 0 && partials && n_partials > 0 &&
+               n_partials <= SCAE_GRAD_SQ_MAX_PARTIALS && max_norm > 0.f);
+  if (momentum > 0.f && !buf) return SCAE_ERR_BAD_ARG;
+  const size_t phase = (size_t)param & 15;
+  if ((phase & 3) || ((size_t)grad & 15) != phase || ((size_t)square_avg & 15) != phase ||
+      (momentum > 0.f && ((size_t)buf & 15) != phase))
+    return SCAE_ERR_BAD_ARG;
+  int head = (int)((16 - phase) & 15) / 4;
+  if (head > n) head = (int)n;
+  OptArgs a{param, square_avg, momentum > 0.f ? buf : nullptr, grad, lr_dev, (long)n, lr, alpha,
+            eps, momentum, weight_decay, grad_scale};
+  long blocks = (n / 4 + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  scae::launch(rmsprop_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+               a, head, scae_clip::Clip{partials, n_partials, max_norm, norm_out});
   return scae_launch_status();
 }
 

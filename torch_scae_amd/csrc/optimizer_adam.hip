@@ -19,7 +19,9 @@
 // every workgroup derives the step's scalars from it in fp64 (identical values everywhere), and
 // the last workgroup to arrive writes t + 1.  Non-sync steps move 28 bytes per parameter, like
 // RMSprop with momentum; a sync step 8 more.
-#include "sum_rows_dev.h"
+// The clip form (scae_flat_opt_clip_step_f32) scales g by clip_grad_norm_'s coefficient from
+// the norm launch's partials (grad_clip_dev.h) after grad_scale, before the weight decay.
+#include "grad_clip_dev.h"
 
 namespace {
 enum { ADAM = 0, RADAM = 1, RMSPROP = 2 };   // scae_flat_opt_step_f32's `kind`
@@ -42,6 +44,7 @@ struct StepScalars {
   float bc2;                 // Adam: sqrt(1 - b2^t)
   float decay;               // RAdam: wd x lr
   int t;                     // steps taken before this one
+  float coef;                // clip_grad_norm_'s coefficient (the clip form only)
   bool rect, sync, init;     // RAdam's regime; LookAhead: a sync step, slow already made
 };
 
@@ -86,11 +89,18 @@ __device__ __forceinline__ StepScalars step_scalars(const AdamArgs &a) {
   return s;
 }
 
-// ... computed by one thread of the workgroup, read by all (the same values in every workgroup)
-template <int K>
-__device__ __forceinline__ StepScalars shared_scalars(const AdamArgs &a) {
+// ... computed by one thread of the workgroup, read by all (the same values in every workgroup);
+// CLIP: with the clip coefficient, reduced from the norm launch's partials by the whole workgroup
+template <int K, bool CLIP = false>
+__device__ __forceinline__ StepScalars shared_scalars(const AdamArgs &a,
+                                                      const scae_clip::Clip *clip = nullptr) {
   __shared__ StepScalars sh;
-  if (threadIdx.x == 0) sh = step_scalars<K>(a);
+  float coef = 1.f;
+  if (CLIP) coef = scae_clip::clip_coef(*clip, a.grad_scale);
+  if (threadIdx.x == 0) {
+    sh = step_scalars<K>(a);
+    if (CLIP) sh.coef = coef;
+  }
   __syncthreads();
   return sh;
 }
@@ -99,10 +109,11 @@ __device__ __forceinline__ StepScalars shared_scalars(const AdamArgs &a) {
 // workgroups of adam_sums_kernel -- that must round alike, bit for bit; the fmaf calls are the
 // fused multiply-adds of torch's CPU kernels)
 #pragma clang fp contract(off)
-template <int K>
+template <int K, bool CLIP = false>
 __device__ __forceinline__ void update(float &p, float &m, float &v, float g, const AdamArgs &a,
                                        const StepScalars &s) {
   g *= a.grad_scale;  // e.g. 1/world_size after a SUM all-reduce
+  if (CLIP) g *= s.coef;   // clip_grad_norm_ (exact for coef == 1: the unclipped pass's bits)
   if (K == RMSPROP) {   // optimizer.hip's update(): b1 = momentum, b2 = alpha
     if (a.weight_decay != 0.f) g = fmaf(a.weight_decay, p, g);
     v = s.b2 * v + s.omb2 * g * g;
@@ -141,11 +152,11 @@ __device__ __forceinline__ void look_ahead(float &p, float &slow, const AdamArgs
 }
 
 // one element in place (scalar edges, sum workgroups)
-template <int K>
+template <int K, bool CLIP = false>
 __device__ __forceinline__ void update_at(const AdamArgs &a, const StepScalars &s, long i,
                                           float g) {
   float p = a.p[i], m = a.m[i], v = a.v[i];
-  update<K>(p, m, v, g, a, s);
+  update<K, CLIP>(p, m, v, g, a, s);
   if (s.sync) {
     float sl = a.slow[i];
     look_ahead(p, sl, a, s);
@@ -180,17 +191,17 @@ __device__ __forceinline__ void arrive(const AdamArgs &a, const StepScalars &s) 
 
 // the float4 lanes of elements [head + 4 i, head + 4 i + 4): `own` bit u set = element u is
 // not this workgroup's to write
-template <int K>
+template <int K, bool CLIP = false>
 __device__ __forceinline__ void update_quad(const AdamArgs &a, const StepScalars &s, int head,
                                             long i, int own) {
   float *p4 = a.p + head, *m4 = a.m + head, *v4 = a.v + head, *s4 = a.slow + head;
   float4 p = reinterpret_cast<float4 *>(p4)[i], m = reinterpret_cast<float4 *>(m4)[i],
          v = reinterpret_cast<float4 *>(v4)[i];
   const float4 g = reinterpret_cast<const float4 *>(a.g + head)[i];
-  update<K>(p.x, m.x, v.x, g.x, a, s);
-  update<K>(p.y, m.y, v.y, g.y, a, s);
-  update<K>(p.z, m.z, v.z, g.z, a, s);
-  update<K>(p.w, m.w, v.w, g.w, a, s);
+  update<K, CLIP>(p.x, m.x, v.x, g.x, a, s);
+  update<K, CLIP>(p.y, m.y, v.y, g.y, a, s);
+  update<K, CLIP>(p.z, m.z, v.z, g.z, a, s);
+  update<K, CLIP>(p.w, m.w, v.w, g.w, a, s);
   float4 sl;
   if (s.sync) {   // (workgroup-uniform)
     sl = reinterpret_cast<float4 *>(s4)[i];
@@ -221,19 +232,29 @@ __device__ __forceinline__ void update_quad(const AdamArgs &a, const StepScalars
 
 // `head` leading elements bring the (equally misaligned) buffers to a 16-byte boundary; then
 // float4 lanes; then the tail
-template <int K>
-__global__ __launch_bounds__(256) void adam_kernel(AdamArgs a, int head) {
-  const StepScalars s = shared_scalars<K>(a);
+template <int K, bool CLIP>
+__device__ __forceinline__ void adam_pass(const AdamArgs &a, int head, const StepScalars &s) {
   const long stride = (long)gridDim.x * blockDim.x;
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long n4 = (a.n - head) >> 2;
-  for (long i = tid; i < n4; i += stride) update_quad<K>(a, s, head, i, 0);
+  for (long i = tid; i < n4; i += stride) update_quad<K, CLIP>(a, s, head, i, 0);
   const long tail0 = head + (n4 << 2), edge = head + (a.n - tail0);
   for (long e = tid; e < edge; e += stride) {
     const long i = e < head ? e : tail0 + (e - head);
-    update_at<K>(a, s, i, a.g[i]);
+    update_at<K, CLIP>(a, s, i, a.g[i]);
   }
   arrive(a, s);
+}
+template <int K>
+__global__ __launch_bounds__(256) void adam_kernel(AdamArgs a, int head) {
+  adam_pass<K, false>(a, head, shared_scalars<K>(a));
+}
+// the clip form: every workgroup first reduces the norm launch's partials to the coefficient
+// (the same bits in every workgroup)
+template <int K>
+__global__ __launch_bounds__(256) void adam_clip_kernel(AdamArgs a, int head,
+                                                        scae_clip::Clip clip) {
+  adam_pass<K, true>(a, head, shared_scalars<K, true>(a, &clip));
 }
 
 // The step's last column sums and the optimiser in one launch, as optimizer.hip's
@@ -241,7 +262,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a, int head) {
 // produce, the streaming workgroups behind them skip exactly those (the segments' destination
 // ranges, rebuilt from the job table into LDS by every workgroup).  Same arithmetic per element:
 // the results equal the two launches' bit for bit.
-constexpr int MAXR = scae_sums::MAXJOBS * 8;
+using scae_sums::MAXR;
 template <int K>
 __global__ __launch_bounds__(256) void adam_sums_kernel(AdamArgs a, int head, scae_sums::Jobs jobs,
                                                         int sum_blocks) {
@@ -258,42 +279,21 @@ __global__ __launch_bounds__(256) void adam_sums_kernel(AdamArgs a, int head, sc
     arrive(a, s);
     return;
   }
-  // the ranges of the flat buffers the sum workgroups own (a thread per segment)
-  if (threadIdx.x == 0) r_n = 0;
-  __syncthreads();
-  if (threadIdx.x < MAXR) {
-    const int j = threadIdx.x >> 3, i = threadIdx.x & 7;
-    if (j < jobs.n && i < jobs.j[j].n) {
-      const scae_sums::Seg &g = jobs.j[j].s[i];
-      const long width = g.end - g.begin;
-      const long len = g.period > 0 ? (long)(jobs.j[j].cols / g.period) * width : width;
-      const long lo = g.dst - a.g;
-      if (lo + len > 0 && lo < a.n) {
-        const int k = atomicAdd(&r_n, 1);   // (order is irrelevant: membership only)
-        r_lo[k] = (int)max(lo, 0l), r_hi[k] = (int)min(lo + len, a.n);
-      }
-    }
-  }
-  __syncthreads();
-  const int nr = r_n;
+  // the ranges of the flat buffers the sum workgroups own
+  const int nr = scae_sums::owned_ranges(jobs, a.g, a.n, r_lo, r_hi, &r_n);
   const long stride = (long)(gridDim.x - sum_blocks) * blockDim.x;
   const long tid = (long)(blockIdx.x - sum_blocks) * blockDim.x + threadIdx.x;
   const long n4 = (a.n - head) >> 2;
   for (long i = tid; i < n4; i += stride) {
     const int e0 = head + 4 * (int)i;
-    int own = 0;   // bit u: element e0 + u belongs to a sum workgroup
-    for (int k = 0; k < nr; ++k) {
-      const int lo = r_lo[k] - e0, hi = r_hi[k] - e0;   // the range relative to the quad
-      if (hi > 0 && lo < 4) own |= ((hi >= 4 ? 15 : (1 << hi) - 1) & ~((lo <= 0 ? 0 : (1 << lo) - 1)));
-    }
+    // bit u: element e0 + u belongs to a sum workgroup
+    const int own = scae_sums::quad_owned(e0, r_lo, r_hi, nr);
     if (own != 15) update_quad<K>(a, s, head, i, own);
   }
   const long tail0 = head + (n4 << 2), edge = head + (a.n - tail0);
   for (long e = tid; e < edge; e += stride) {
     const long i = e < head ? e : tail0 + (e - head);
-    bool owned = false;
-    for (int k = 0; k < nr; ++k) owned |= i >= r_lo[k] && i < r_hi[k];
-    if (!owned) update_at<K>(a, s, i, a.g[i]);
+    if (!scae_sums::owned(i, r_lo, r_hi, nr)) update_at<K>(a, s, i, a.g[i]);
   }
   arrive(a, s);
 }
@@ -328,6 +328,7 @@ void launch_kind(int kind, dim3 grid, hipStream_t st, T... args) {
 }
 template <int K> struct Plain { static constexpr auto fn = adam_kernel<K>; };
 template <int K> struct Sums { static constexpr auto fn = adam_sums_kernel<K>; };
+template <int K> struct Clipped { static constexpr auto fn = adam_clip_kernel<K>; };
 
 extern "C" int scae_flat_opt_step_f32(float *param, const float *grad, float *exp_avg,
                                       float *exp_avg_sq, float *slow, int64_t n,
@@ -368,5 +369,28 @@ extern "C" int scae_flat_opt_sums_step_f32(float *param, float *grad, float *exp
   blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
   launch_kind<Sums>(kind, dim3((unsigned)(sum_blocks + blocks)), (hipStream_t)stream, a, head,
                     js, sum_blocks);
+  return scae_launch_status();
+}
+
+// scae_flat_opt_step_f32 with g scaled by clip_grad_norm_'s coefficient (grad_clip_dev.h)
+extern "C" int scae_flat_opt_clip_step_f32(float *param, const float *grad, float *exp_avg,
+                                           float *exp_avg_sq, float *slow, int64_t n,
+                                           const float *lr_dev, int32_t *step_state, int kind,
+                                           double beta1, double beta2, float eps,
+                                           float weight_decay, float grad_scale,
+                                           int look_ahead_k, float look_ahead_alpha, int advance,
+                                           const double *partials, int n_partials,
+                                           float max_norm, float *norm_out, void *stream) {
+  AdamArgs a;
+  const int head = prepare(a, param, grad, exp_avg, exp_avg_sq, slow, n, lr_dev, step_state,
+                           kind, beta1, beta2, eps, weight_decay, grad_scale, look_ahead_k,
+                           look_ahead_alpha, advance);
+  if (head < 0) return SCAE_ERR_BAD_ARG;
+  SCAE_REQUIRE(partials && n_partials > 0 && n_partials <= SCAE_GRAD_SQ_MAX_PARTIALS &&
+               max_norm > 0.f);
+  long blocks = (n / 4 + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  launch_kind<Clipped>(kind, dim3((unsigned)blocks), (hipStream_t)stream, a, head,
+                       scae_clip::Clip{partials, n_partials, max_norm, norm_out});
   return scae_launch_status();
 }

@@ -69,6 +69,49 @@ __device__ __forceinline__ void sum_block(const Jobs &jobs, int blk, float *red,
   }
 }
 
+// The streaming workgroups of a launch headed by sum workgroups (the optimiser passes of
+// optimizer*.hip, the gradient norm of grad_clip.hip) skip exactly the elements the sum
+// workgroups produce: the segments' destination ranges within the flat buffer [base, base + n),
+// rebuilt from the job table into LDS (r_lo / r_hi: MAXR ints each) by every workgroup, a
+// thread per segment.  Every thread of the workgroup calls it; -> the number of ranges.
+constexpr int MAXR = MAXJOBS * 8;
+__device__ __forceinline__ int owned_ranges(const Jobs &jobs, const float *base, long n,
+                                            int *r_lo, int *r_hi, int *r_n) {
+  if (threadIdx.x == 0) *r_n = 0;
+  __syncthreads();
+  if (threadIdx.x < MAXR) {
+    const int j = threadIdx.x >> 3, i = threadIdx.x & 7;
+    if (j < jobs.n && i < jobs.j[j].n) {
+      const Seg &g = jobs.j[j].s[i];
+      const long width = g.end - g.begin;
+      const long len = g.period > 0 ? (long)(jobs.j[j].cols / g.period) * width : width;
+      const long lo = g.dst - base;
+      if (lo + len > 0 && lo < n) {
+        const int k = atomicAdd(r_n, 1);   // (order is irrelevant: membership only)
+        r_lo[k] = (int)max(lo, 0l), r_hi[k] = (int)min(lo + len, n);
+      }
+    }
+  }
+  __syncthreads();
+  return *r_n;
+}
+
+// bit u set: element e0 + u lies in one of the nr ranges
+__device__ __forceinline__ int quad_owned(int e0, const int *r_lo, const int *r_hi, int nr) {
+  int own = 0;
+  for (int k = 0; k < nr; ++k) {
+    const int lo = r_lo[k] - e0, hi = r_hi[k] - e0;   // the range relative to the quad
+    if (hi > 0 && lo < 4) own |= ((hi >= 4 ? 15 : (1 << hi) - 1) & ~((lo <= 0 ? 0 : (1 << lo) - 1)));
+  }
+  return own;
+}
+
+__device__ __forceinline__ bool owned(long i, const int *r_lo, const int *r_hi, int nr) {
+  bool own = false;
+  for (int k = 0; k < nr; ++k) own |= i >= r_lo[k] && i < r_hi[k];
+  return own;
+}
+
 // host: scae_sum_job[] -> Jobs; returns the workgroup count or < 0 (bad argument)
 inline int fill_jobs(Jobs &js, const scae_sum_job *jobs, int n_jobs) {
   if (!(jobs && n_jobs > 0 && n_jobs <= MAXJOBS)) return -1;

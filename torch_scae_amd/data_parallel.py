@@ -12,6 +12,7 @@ bound rings.
 """
 import ctypes
 import math
+import numbers
 
 import torch
 import torch.distributed as dist
@@ -235,7 +236,7 @@ class RMSpropFlat:
 
     def __init__(self, flat: FlatParameters, lr=3e-5, alpha=0.99, eps=1e-8,
                  momentum=0.9, weight_decay=0.0, look_ahead=False,
-                 look_ahead_k=5, look_ahead_alpha=0.5):
+                 look_ahead_k=5, look_ahead_alpha=0.5, gradient_clip_val=0.0):
         self.flat = flat
         self.lr, self.alpha, self.eps, self.momentum = lr, alpha, eps, momentum
         self.weight_decay = weight_decay
@@ -244,6 +245,7 @@ class RMSpropFlat:
         self.lr_dev = torch.full((1,), lr, device=flat.flat_param.device,
                                  dtype=flat.flat_param.dtype)
         _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
+        _init_clip(self, gradient_clip_val)
 
     def set_lr(self, lr):
         self.lr = float(lr)
@@ -265,6 +267,9 @@ class RMSpropFlat:
             _fused_step(self, self.buf, self.square_avg,
                         (self.momentum, self.alpha), grad_scale, sum_units,
                         self._cpu_update)
+            return
+        if self.max_norm:
+            self._clipped_step(grad_scale, sum_units)
             return
         g = self.flat.flat_grad
         if sum_units:
@@ -321,6 +326,34 @@ class RMSpropFlat:
                                  self.buf), saved):
                 cur.copy_(torch.where(keep, cur, old))
 
+    def _clipped_step(self, grad_scale, sum_units):
+        """``step`` with clipping by global norm: the norm launch (``sum_units`` ride in
+        it), then scae_rmsprop_clip_step_f32 over each active range; on CPU tensors
+        ``_cpu_update`` on the clipped gradient."""
+        flat = self.flat
+        g = flat.flat_grad
+        ranges = flat.active_ranges() if self.weight_decay != 0 else [(0, g.numel())]
+        if not g.is_cuda:
+            if sum_units:
+                from . import ops
+                ops._launch_sum_units(sum_units)
+            saved = _keep_inactive(self, ranges, [flat.flat_param, self.square_avg, self.buf])
+            self._cpu_update(_cpu_clipped_grad(self, g, grad_scale), None)
+            _restore_inactive(saved)
+            return
+        from . import _lib
+        P = ctypes.c_void_p
+        st = P(torch.cuda.current_stream(g.device).cuda_stream)
+        n_partials = _launch_norm(self, g, sum_units, st)
+        for i, (off, n) in enumerate(ranges):
+            ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
+            _lib.call("scae_rmsprop_clip_step_f32", ptr(flat.flat_param), ptr(g),
+                      ptr(self.square_avg), ptr(self.buf), n, self.lr,
+                      P(self.lr_dev.data_ptr()), self.alpha, self.eps, self.momentum,
+                      self.weight_decay, float(grad_scale), P(self.grad_sq.data_ptr()),
+                      n_partials, self.max_norm,
+                      P(self.grad_norm.data_ptr()) if i == 0 else None, st)
+
     def _cpu_update(self, g, t):
         """The CPU form of the update (torch.optim.RMSprop's arithmetic) on
         whole buffers; ``g`` already scaled."""
@@ -368,6 +401,85 @@ def _init_look_ahead(opt, look_ahead, k, alpha):
     opt.slow = torch.zeros_like(flat.flat_param) if opt.look_ahead_k else None
 
 
+def clip_value(v):
+    """``gradient_clip_val`` as Lightning 0.9 reads it: any value <= 0 is off (-> 0.0); a
+    non-numeric or non-finite value is an error."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(float(v)):
+        raise ValueError(f"gradient_clip_val must be a finite number, got {v!r}")
+    return float(v) if v > 0 else 0.0
+
+
+def _init_clip(opt, gradient_clip_val):
+    """Clipping by global norm (torch.nn.utils.clip_grad_norm_, which Lightning's
+    Trainer(gradient_clip_val) applies before every optimiser step): ``max_norm`` (0.0: off),
+    the norm launch's fp64 partial sums and the last norm before clipping, both in device
+    memory (read by a captured step's launches, never by the host)."""
+    opt.max_norm = clip_value(gradient_clip_val)
+    dev = opt.flat.flat_param.device
+    opt.grad_sq = opt.grad_norm = None
+    if opt.max_norm:
+        from ._lib import GRAD_SQ_MAX_PARTIALS
+        opt.grad_sq = torch.zeros(GRAD_SQ_MAX_PARTIALS, dtype=torch.float64, device=dev)
+        opt.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+
+
+def _launch_norm(opt, g, sum_units, st):
+    """The gradient's fp64 partial sums of squares into ``opt.grad_sq`` (the last 16 column-sum
+    units ride in the launch, the rest are launched first); -> the partial count."""
+    from . import _lib
+    P = ctypes.c_void_p
+    cnt = ctypes.c_int(0)
+    if sum_units:
+        from . import ops
+        if len(sum_units) > 16:
+            ops._launch_sum_units(sum_units[:-16])
+            sum_units = sum_units[-16:]
+        _lib.call("scae_grad_sq_partials_sums_f32", P(g.data_ptr()), g.numel(),
+                  P(opt.grad_sq.data_ptr()), opt.grad_sq.numel(), ctypes.byref(cnt),
+                  ops._sum_job_array(sum_units), len(sum_units), st)
+    else:
+        _lib.call("scae_grad_sq_partials_f32", P(g.data_ptr()), g.numel(),
+                  P(opt.grad_sq.data_ptr()), opt.grad_sq.numel(), ctypes.byref(cnt), st)
+    return cnt.value
+
+
+def _cpu_clipped_grad(opt, g, grad_scale):
+    """The CPU form: torch.nn.utils.clip_grad_norm_'s arithmetic on the (scaled) gradients of
+    the parameters that have one (a norm per parameter, then the norm of those), applied to
+    the whole flat gradient; the norm into ``opt.grad_norm``."""
+    if grad_scale != 1.0:
+        g = g * grad_scale
+    flat = opt.flat
+    norms = [torch.linalg.vector_norm(g[off:off + p.numel()])
+             for p, off in zip(flat.params, flat.offsets)
+             if getattr(p, "_flat_was_set", True)]
+    total = torch.linalg.vector_norm(torch.stack(norms)) if norms else g.new_zeros(())
+    opt.grad_norm.copy_(total)
+    coef = torch.clamp(opt.max_norm / (total + 1e-6), max=1.0)
+    return g * coef
+
+
+def _keep_inactive(opt, ranges, bufs):
+    """(CPU forms) what ``_restore_inactive`` needs to put back the elements outside
+    ``ranges`` -- parameters without a gradient, which torch.optim skips; None when the
+    ranges cover the whole buffer."""
+    g = opt.flat.flat_grad
+    if ranges == [(0, g.numel())]:
+        return None
+    keep = torch.zeros_like(g, dtype=torch.bool)
+    for off, n in ranges:
+        keep[off:off + n] = True
+    return keep, [(b, b.clone()) for b in bufs]
+
+
+def _restore_inactive(saved):
+    if saved is None:
+        return
+    keep, pairs = saved
+    for cur, old in pairs:
+        cur.copy_(torch.where(keep, cur, old))
+
+
 def _split_sums(opt, g, sum_units):
     """The column-sum units that may ride in the optimiser's launch (the rest
     launched now); None when none ride."""
@@ -392,7 +504,8 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update):
     (zero moments stay zero, LookAhead's slow copy of such a parameter equals it)."""
     flat = opt.flat
     g = flat.flat_grad
-    sum_units = _split_sums(opt, g, sum_units)
+    clip = opt.max_norm and g.is_cuda
+    sum_units = _split_sums(opt, g, sum_units) if not clip else sum_units
     ranges = flat.active_ranges() if opt.weight_decay != 0 else \
         [(0, g.numel())]
     if g.is_cuda:
@@ -402,6 +515,16 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update):
         slow = opt.slow if opt.slow is not None else flat.flat_param
         common = (P(opt.lr_dev.data_ptr()), P(opt.step_state.data_ptr()),
                   opt.kind, float(betas[0]), float(betas[1]), float(opt.eps))
+        if clip:     # the norm launch (the column sums ride in it), then the clip forms
+            n_partials = _launch_norm(opt, g, sum_units, st)
+            for i, (off, n) in enumerate(ranges):
+                ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
+                _lib.call("scae_flat_opt_clip_step_f32", ptr(flat.flat_param), ptr(g),
+                          ptr(m), ptr(v), ptr(slow), n, *common, float(opt.weight_decay),
+                          float(grad_scale), opt.look_ahead_k, opt.look_ahead_alpha,
+                          int(i == len(ranges) - 1), P(opt.grad_sq.data_ptr()), n_partials,
+                          opt.max_norm, P(opt.grad_norm.data_ptr()) if i == 0 else None, st)
+            return
         if sum_units:
             from . import ops
             arr = ops._sum_job_array(sum_units)
@@ -421,7 +544,9 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update):
         return
     if not ranges:
         return
-    if grad_scale != 1.0:
+    if opt.max_norm:
+        g = _cpu_clipped_grad(opt, g, grad_scale)
+    elif grad_scale != 1.0:
         g = g * grad_scale
     bufs = [flat.flat_param, m, v] + ([opt.slow] if opt.slow is not None else [])
     if opt.weight_decay != 0:
@@ -457,7 +582,7 @@ class _FlatAdamBase:
 
     def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=0.0, look_ahead=False, look_ahead_k=5,
-                 look_ahead_alpha=0.5):
+                 look_ahead_alpha=0.5, gradient_clip_val=0.0):
         b1, b2 = (float(b) for b in betas)
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
             raise ValueError(f"betas must lie in [0, 1), got {betas}")
@@ -469,6 +594,7 @@ class _FlatAdamBase:
         self.lr_dev = torch.full((1,), self.lr, device=flat.flat_param.device,
                                  dtype=flat.flat_param.dtype)
         _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
+        _init_clip(self, gradient_clip_val)
 
     def set_lr(self, lr):
         self.lr = float(lr)
@@ -543,11 +669,12 @@ class RAdamFlat(_FlatAdamBase):
 
 def make_optimizer(kind, flat, lr, eps, betas=(0.9, 0.999), momentum=0.9,
                    weight_decay=0.0, look_ahead=False, look_ahead_k=5,
-                   look_ahead_alpha=0.5):
-    """``kind``: "rmsprop" | "adam" | "radam" (any case) -> the flat optimiser."""
+                   look_ahead_alpha=0.5, gradient_clip_val=0.0):
+    """``kind``: "rmsprop" | "adam" | "radam" (any case) -> the flat optimiser.
+    ``gradient_clip_val`` > 0: every step clips the gradient to that global norm first."""
     name = str(kind).lower()
     la = dict(look_ahead=look_ahead, look_ahead_k=look_ahead_k,
-              look_ahead_alpha=look_ahead_alpha)
+              look_ahead_alpha=look_ahead_alpha, gradient_clip_val=gradient_clip_val)
     if name == "rmsprop":
         return RMSpropFlat(flat, lr=lr, momentum=momentum, eps=eps,
                            weight_decay=weight_decay, **la)

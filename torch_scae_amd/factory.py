@@ -163,11 +163,14 @@ def make_train_step(model, cfg: dict, **kw):
     weight_decay, momentum}``, ``meta_optimizer.{look_ahead, look_ahead_k,
     look_ahead_alpha}``, ``lr_scheduler.{active, decay_rate}`` (the
     per-epoch ExponentialLR: ``TrainStep.end_epoch``),
-    ``data_loader.batch_size`` (eps = 1e-2 / batch_size**2) and
-    ``model.image_shape``.  The reference reads LookAhead's k and alpha from
+    ``data_loader.batch_size`` (eps = 1e-2 / batch_size**2),
+    ``model.image_shape`` and, when present, ``trainer.gradient_clip_val`` (the
+    ``Trainer(**cfg.trainer)`` of train.py:40: clipping by global norm, off
+    when absent or <= 0; a non-numeric or non-finite value raises ValueError).  The reference reads LookAhead's k and alpha from
     ``cfg.optimizer``, where none of its yaml files defines them
     (base_experiment.py:67-70); they are read from ``meta_optimizer`` here,
     where config.yaml puts them.  ``kw``: further TrainStep arguments."""
+    from .data_parallel import clip_value
     from .train_step import TrainStep
     opt = cfg["optimizer"]
     kind = _OPTIMIZERS.get(opt["type"])
@@ -185,5 +188,8 @@ def make_train_step(model, cfg: dict, **kw):
                 look_ahead_alpha=float(meta.get("look_ahead_alpha", 0.5)))
     if kind == "rmsprop":
         args["momentum"] = float(opt["momentum"])
+    clip = (cfg.get("trainer") or {}).get("gradient_clip_val")
+    if clip is not None:
+        args["gradient_clip_val"] = clip_value(clip)
     args.update(kw)
     return TrainStep(model, int(cfg["data_loader"]["batch_size"]), shape, **args)

@@ -14,7 +14,7 @@ import torch.distributed as dist
 
 from . import ops
 from .data_parallel import (FlatParameters, all_reduce_gradients,
-                            broadcast_parameters, load_optimizer_state_dict,
+                            broadcast_parameters, clip_value, load_optimizer_state_dict,
                             make_optimizer, optimizer_state_dict, world)
 
 
@@ -106,6 +106,14 @@ class TrainStep:
     counts in the same ``steps``.  It has its own input buffers, graph(s) or launch list,
     prologue and noise draws.  Not padded: the loss's between-example terms depend on the
     batch size.
+
+    ``gradient_clip_val``: Lightning's ``Trainer(gradient_clip_val)`` -- every step clips the
+    averaged gradient (after the all-reduce) to that global L2 norm before the optimiser, as
+    torch.nn.utils.clip_grad_norm_ does; any value <= 0 (the default) is off, and then the
+    step is exactly the unclipped one.  One launch more per step (scae_grad_sq_partials_f32:
+    the gradient's sum of squares, the step's last column sums riding in it); the optimiser
+    pass reads the coefficient from its partials.  ``last_grad_norm()``: the last step's norm
+    before clipping, a device scalar.
     """
 
     MODES = ("2 buckets", "1 bucket", "in graph")
@@ -117,9 +125,12 @@ class TrainStep:
                  prologue=True, fuse_kernels=True, collective_mode=None,
                  replay="graph", two_lanes=False, betas=(0.9, 0.999),
                  look_ahead=False, look_ahead_k=5, look_ahead_alpha=0.5,
-                 log_steps=0):
+                 log_steps=0, gradient_clip_val=0.0):
         if not isinstance(log_steps, int) or isinstance(log_steps, bool) or log_steps < 0:
             raise ValueError(f"log_steps must be an int >= 0, got {log_steps!r}")
+        gradient_clip_val = clip_value(gradient_clip_val)
+        if gradient_clip_val and optimizer in (None, False):
+            raise ValueError("gradient_clip_val needs an optimizer: clipping is part of its step")
         self._parent = None      # (a remainder step: the step whose state it shares)
         self._rem = None         # the cached remainder step (remainder_step)
         self.model = model
@@ -182,7 +193,7 @@ class TrainStep:
             optimizer, self.flat, lr=lr, eps=1e-2 / float(batch_size) ** 2,
             betas=betas, momentum=momentum, weight_decay=weight_decay,
             look_ahead=look_ahead, look_ahead_k=look_ahead_k,
-            look_ahead_alpha=look_ahead_alpha) \
+            look_ahead_alpha=look_ahead_alpha, gradient_clip_val=gradient_clip_val) \
             if optimizer not in (None, False) else None
         self.steps = 0           # steps taken (host count, with the remainder step's; the
         #                          optimisers keep their own)
@@ -195,7 +206,8 @@ class TrainStep:
         self.lr_decay_rate = lr_decay_rate
         # the backward's last column sums (parameter gradients only) ride in the optimiser's
         # launch: one launch less on the step's dependent chain.  Not with a collective (the
-        # all-reduce reads the finished gradient buffer first) nor with weight decay.
+        # all-reduce reads the finished gradient buffer first) nor with weight decay.  With
+        # clipping they ride in the norm launch, the optimiser's first.
         self.plan.sums_to_optimizer = bool(
             self.opt is not None and fuse_kernels and not self.collective
             and weight_decay == 0 and self.device.type == "cuda")
@@ -792,6 +804,13 @@ class TrainStep:
         step = self._for_batch(image.shape[0])
         loss = step(image, label)
         return dict(loss=loss, log=step.log)
+
+    def last_grad_norm(self):
+        """The last step's total gradient norm before clipping (what Lightning's
+        ``track_grad_norm`` reports): a device scalar the next step overwrites, no read.  None
+        when the step does not clip."""
+        opt = self.opt
+        return None if opt is None or not opt.max_norm else opt.grad_norm
 
     # -- the training log (log_steps) ---------------------------------------------
     def _need_log(self):
