@@ -13,9 +13,10 @@ from tests.golden_util import load, model_names, sub
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_at_abi_3():
     from torch_scae_amd import _lib
     header = open(os.path.join(ROOT, "include", "scae_hip.h")).read()
+    assert re.search(r"#define SCAE_ABI_VERSION (\d+)\n", header).group(1) == "3"
     declared = set(re.findall(r"\b(scae_[a-z0-9_]+)\s*\(", header))
     declared -= {"scae_decoder_desc"}
     assert declared, "no declarations found"
@@ -24,7 +25,7 @@ def test_library_exports_every_declared_symbol():
     lib = _lib.load()
     for name in declared:
         assert hasattr(lib, name), name
-    assert lib.scae_abi_version() == _lib.ABI_VERSION == 2
+    assert lib.scae_abi_version() == _lib.ABI_VERSION == 3
     assert lib.scae_conv3x3_wf_floats(128, 128) == 5 * 128 * 9 * 128 // 2   # (+ the packed planes)
     assert lib.scae_conv3x3_wf_floats(8, 8) == 8 * 9 * 8
     assert lib.scae_conv3x3_wf_floats(0, 8) == 0
@@ -58,32 +59,26 @@ def test_launch_list_bookkeeping_without_a_gpu():
     assert lib.scae_launch_list_size(None) == 0
 
 
-def test_launch_list_lanes_and_order_edges_without_a_gpu():
-    """A recording with a side stream: stream-order edges the caller reports
-    (scae_launch_list_order) are noted by the recordings that hold BOTH streams, an edge
-    that is already implied (same edge, nothing given to the earlier lane since) is not
-    noted twice, and a list without launches runs as a no-op on one stream or two."""
+def test_launch_list_lane_and_timeline_checks_without_a_gpu():
+    """A list records one stream: every launch is lane 0 and an index past the end is -1;
+    the timeline refuses an open list, too short an output and a second stream before any
+    HIP call; a closed list without launches runs as a no-op."""
     import ctypes
     from torch_scae_amd import _lib
     lib = _lib.load()
     P = ctypes.c_void_p
+    out = (ctypes.c_float * 4)()
     a = lib.scae_launch_list_begin(P(0x10))
-    b = lib.scae_launch_list_begin(P(0x30))             # knows nothing of 0x20
-    assert lib.scae_launch_list_side_stream(P(a), P(0x20)) == 0
-    assert lib.scae_launch_list_side_stream(P(a), P(0x40)) == -1   # one side lane per list
-    assert lib.scae_launch_list_side_stream(P(b), P(0x30)) == -1   # not its own stream
-    assert lib.scae_launch_list_order(P(0x20), P(0x10)) == 1       # side waits for main: a
-    assert lib.scae_launch_list_order(P(0x20), P(0x10)) == 1       # (implied: not noted again)
-    assert lib.scae_launch_list_order(P(0x10), P(0x20)) == 1       # main waits for side
-    assert lib.scae_launch_list_order(P(0x20), P(0x30)) == 0       # no list holds both
-    assert lib.scae_launch_list_end(P(a)) == 0 and lib.scae_launch_list_end(P(b)) == 0
-    assert lib.scae_launch_list_order(P(0x20), P(0x10)) == 0       # nothing open
-    assert lib.scae_launch_list_size(P(a)) == 0 and lib.scae_launch_list_side_size(P(a)) == 0
+    assert lib.scae_launch_list_timeline(P(a), P(0x10), None, out, 4) == -1   # still recording
+    assert lib.scae_launch_list_end(P(a)) == 0
+    assert lib.scae_launch_list_size(P(a)) == 0
     assert lib.scae_launch_list_lane(P(a), 0) == -1
-    assert lib.scae_launch_list_run2(P(a), None, None) == 0        # (one stream: edges skipped)
-    assert lib.scae_launch_list_side_stream(P(a), P(0x50)) == -1   # closed
+    assert lib.scae_launch_list_lane(P(a), -1) == -1
+    assert lib.scae_launch_list_timeline(P(a), P(0x10), None, out, -1) == -1  # n_out < 2 size
+    assert lib.scae_launch_list_timeline(P(a), P(0x10), P(0x20), out, 4) == -1   # two streams
+    assert lib.scae_launch_list_run(P(a), P(0x10)) == 0
     lib.scae_launch_list_free(P(a))
-    lib.scae_launch_list_free(P(b))
+    assert lib.scae_launch_list_lane(None, 0) == -1
 
 
 def test_bf16_resident_conv_entry_points_reject_bad_arguments_without_a_gpu():

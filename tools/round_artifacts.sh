@@ -37,9 +37,8 @@ rm -f $O/*_domain_stats.csv
 [ -f tools/ablibs/libfwd_prof.so ] && timeout 300 python tools/fwd_prof.py tools/ablibs/libfwd_prof.so > $O/fwd_tile_timeline.txt 2>&1
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O -o gap -- python3 $R/tools/graph_gap_probe.py > /dev/null 2>&1)
 python3 tools/graph_gap_report.py $O/gap_kernel_trace.csv > $O/graph_gap.txt 2>&1; rm -f $O/gap_*.csv
-# round 6: do two plain streams overlap (yes); graph replay / launch list on one lane / on two lanes
+# round 6: do two plain streams overlap (yes)
 [ -x tools/probes/stream_overlap ] && ./tools/probes/stream_overlap > $O/stream_overlap.txt 2>&1
-RESIDENT=0,384,512,768 timeout 400 python tools/lanes_probe.py 2>&1 | grep -v amdgpu.ids > $O/lanes.txt
 # the bf16-resident K8 kernels alone at cfg-3's layer shapes
 timeout 200 python tools/conv_bf16_time.py 2>&1 | grep "B=1024" > $O/conv_bf16_time.txt
 ls $O

@@ -25,7 +25,7 @@ class DecoderDesc(Structure):
                 ("out_scale", P),
                 ("B", c_int), ("M", c_int), ("C", c_int), ("th", c_int),
                 ("tw", c_int), ("H", c_int), ("W", c_int),
-                ("template_repeat", c_int), ("bwd_resident", c_int)]
+                ("template_repeat", c_int)]
 
 
 class LikelihoodBwdDesc(Structure):
@@ -226,10 +226,6 @@ SIGNATURES = {
     "scae_launch_list_end": [P],
     "scae_launch_list_size": [P],
     "scae_launch_list_run": [P, P],
-    "scae_launch_list_side_stream": [P, P],
-    "scae_launch_list_order": [P, P],
-    "scae_launch_list_run2": [P, P, P],
-    "scae_launch_list_side_size": [P],
     "scae_launch_list_lane": [P, c_int],
     "scae_launch_list_timeline": [P, P, P, POINTER(c_float), c_int],
     "scae_launch_list_free": [P],
@@ -376,7 +372,7 @@ KMEANS_STATE_INTS = 4        # SCAE_KMEANS_STATE_INTS: per restart of scae_kmean
 EVAL_SINK_INT64S = 4         # struct scae_eval_sink: rows, capacity, cursor, overflow
 FLAT_OPT_STATE_INTS = 2112   # SCAE_FLAT_OPT_STATE_INTS: the step_state of scae_flat_opt_*
 GRAD_SQ_MAX_PARTIALS = 4096  # SCAE_GRAD_SQ_MAX_PARTIALS: scae_grad_sq_partials_*
-ABI_VERSION = 2     # SCAE_ABI_VERSION of the include/scae_hip.h this binding mirrors
+ABI_VERSION = 3     # SCAE_ABI_VERSION of the include/scae_hip.h this binding mirrors
 
 _lib = None
 

@@ -47,6 +47,7 @@ template <class... KA, size_t... I, class... A>
 inline void launch_impl(void (*kernel)(KA...), std::index_sequence<I...>, dim3 grid, dim3 block,
                         size_t lds, hipStream_t st, A &&...args) {
   static_assert(sizeof...(KA) == sizeof...(A), "one argument per kernel parameter");
+  static_assert(sizeof...(KA) <= 64, "a launch list replays at most 64 arguments (abi.hip)");
   std::tuple<std::remove_cv_t<KA>...> held{static_cast<std::remove_cv_t<KA>>(args)...};
   void *ptrs[sizeof...(KA) + 1] = {const_cast<void *>(static_cast<const void *>(&std::get<I>(held)))...};
   const hipError_t e =

@@ -75,7 +75,7 @@ extern "C" int scae_render_gmm_sums_bwd_likelihood_f32(
   // per step merged, 3.78 apart, profiles/r06/cfg3_fuse.txt)
   const bool fits = !(e && *e == '0') && g.lds && (d->C == 1 || d->C == 3) && k->O <= 64 &&
                     scae_lk::lk_lds(k->O, k->M, true) <= g.lds && k->B > 0 && k->O > 0 &&
-                    k->M > 0 && d->template_repeat <= 1 && d->bwd_resident <= 0;
+                    k->M > 0 && d->template_repeat <= 1;
   if (!fits) {   // two launches, same results
     int rc = scae_render_gmm_sums_bwd_f32(d, x, lse_post, lse_prior, g_tile_sums, g_templates,
                                           g_alpha_partial, g_pose, g_presence, g_bg_image,

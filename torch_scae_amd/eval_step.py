@@ -366,8 +366,8 @@ class EvalStep:
             if self._klist:
                 import ctypes
                 from . import _lib
-                _lib.call("scae_launch_list_run2", self._klist, ctypes.c_void_p(
-                    torch.cuda.current_stream(self.device).cuda_stream), None)
+                _lib.call("scae_launch_list_run", self._klist, ctypes.c_void_p(
+                    torch.cuda.current_stream(self.device).cuda_stream))
             else:
                 self.graph.replay()
         else:
