@@ -819,6 +819,62 @@ int scae_flat_opt_clip_step_f32(float *param, const float *grad, float *exp_avg,
                                 const double *partials, int n_partials, float max_norm,
                                 float *norm_out, void *stream);
 
+/* Gradient accumulation over k batches -- Lightning's Trainer(accumulate_grad_batches=k):
+ * the optimiser steps on the gradient of a group of batches.  acc: a flat fp32 buffer laid out
+ * like `grad` (n floats at grad's offset within a 16-byte line).
+ *   scae_grad_accumulate_f32: acc <- acc + grad (fp32, one add per element: adding the
+ *   group's gradients in batch order gives acc = g_1 + g_2 + ... bit for bit).
+ *   scae_grad_accumulate_sums_f32: the step's last column sums riding in that launch: the sums
+ *   equal scae_sum_rows_multi_f32's bit for bit, and those whose destinations lie in `grad`
+ *   are added into acc there.
+ * The accumulate forms of the optimiser passes and of the norm launch below are the passes
+ * above with g = acc + grad in place of grad (then g <- grad_scale g, clipping, weight decay,
+ * the update; the norm launch sums (acc + grad)^2); the optimiser passes leave acc = 0 in the
+ * elements they update.  With acc == 0 they equal the plain passes bit for bit. */
+int scae_grad_accumulate_f32(float *acc, const float *grad, int64_t n, void *stream);
+int scae_grad_accumulate_sums_f32(float *acc, float *grad, int64_t n,
+                                  const struct scae_sum_job *jobs, int n_jobs, void *stream);
+int scae_grad_sq_acc_partials_f32(const float *grad, const float *acc, int64_t n,
+                                  double *partials, int max_partials, int *n_partials,
+                                  void *stream);
+int scae_grad_sq_acc_partials_sums_f32(float *grad, const float *acc, int64_t n,
+                                       double *partials, int max_partials, int *n_partials,
+                                       const struct scae_sum_job *jobs, int n_jobs,
+                                       void *stream);
+int scae_rmsprop_acc_step_f32(float *param, const float *grad, float *acc, float *square_avg,
+                              float *buf, int64_t n, float lr, const float *lr_dev, float alpha,
+                              float eps, float momentum, float weight_decay, float grad_scale,
+                              void *stream);
+int scae_rmsprop_acc_sums_step_f32(float *param, float *grad, float *acc, float *square_avg,
+                                   float *buf, int64_t n, float lr, const float *lr_dev,
+                                   float alpha, float eps, float momentum, float grad_scale,
+                                   const struct scae_sum_job *jobs, int n_jobs, void *stream);
+int scae_rmsprop_acc_clip_step_f32(float *param, const float *grad, float *acc,
+                                   float *square_avg, float *buf, int64_t n, float lr,
+                                   const float *lr_dev, float alpha, float eps, float momentum,
+                                   float weight_decay, float grad_scale, const double *partials,
+                                   int n_partials, float max_norm, float *norm_out,
+                                   void *stream);
+int scae_flat_opt_acc_step_f32(float *param, const float *grad, float *acc, float *exp_avg,
+                               float *exp_avg_sq, float *slow, int64_t n, const float *lr_dev,
+                               int32_t *step_state, int kind, double beta1, double beta2,
+                               float eps, float weight_decay, float grad_scale,
+                               int look_ahead_k, float look_ahead_alpha, int advance,
+                               void *stream);
+int scae_flat_opt_acc_sums_step_f32(float *param, float *grad, float *acc, float *exp_avg,
+                                    float *exp_avg_sq, float *slow, int64_t n,
+                                    const float *lr_dev, int32_t *step_state, int kind,
+                                    double beta1, double beta2, float eps, float grad_scale,
+                                    int look_ahead_k, float look_ahead_alpha,
+                                    const struct scae_sum_job *jobs, int n_jobs, void *stream);
+int scae_flat_opt_acc_clip_step_f32(float *param, const float *grad, float *acc,
+                                    float *exp_avg, float *exp_avg_sq, float *slow, int64_t n,
+                                    const float *lr_dev, int32_t *step_state, int kind,
+                                    double beta1, double beta2, float eps, float weight_decay,
+                                    float grad_scale, int look_ahead_k, float look_ahead_alpha,
+                                    int advance, const double *partials, int n_partials,
+                                    float max_norm, float *norm_out, void *stream);
+
 /* The batch hand-over of a training step (base_experiment.py:109-112): n_image
  * floats and n_label int64 labels (device memory) into the step's resident
  * input buffers, in one launch. */

@@ -295,6 +295,26 @@ SIGNATURES = {
     "scae_flat_opt_clip_step_f32": [P, P, P, P, P, c_int64, P, P, c_int, c_double, c_double,
                                     c_float, c_float, c_float, c_int, c_float, c_int, P, c_int,
                                     c_float, P, P],
+    # gradient accumulation (grad_accumulate.hip; the accumulate forms take acc after grad)
+    "scae_grad_accumulate_f32": [P, P, c_int64, P],
+    "scae_grad_accumulate_sums_f32": [P, P, c_int64, POINTER(SumJob), c_int, P],
+    "scae_grad_sq_acc_partials_f32": [P, P, c_int64, P, c_int, POINTER(c_int), P],
+    "scae_grad_sq_acc_partials_sums_f32": [P, P, c_int64, P, c_int, POINTER(c_int),
+                                           POINTER(SumJob), c_int, P],
+    "scae_rmsprop_acc_step_f32": [P, P, P, P, P, c_int64, c_float, P, c_float, c_float,
+                                  c_float, c_float, c_float, P],
+    "scae_rmsprop_acc_sums_step_f32": [P, P, P, P, P, c_int64, c_float, P, c_float, c_float,
+                                       c_float, c_float, POINTER(SumJob), c_int, P],
+    "scae_rmsprop_acc_clip_step_f32": [P, P, P, P, P, c_int64, c_float, P, c_float, c_float,
+                                       c_float, c_float, c_float, P, c_int, c_float, P, P],
+    "scae_flat_opt_acc_step_f32": [P, P, P, P, P, P, c_int64, P, P, c_int, c_double, c_double,
+                                   c_float, c_float, c_float, c_int, c_float, c_int, P],
+    "scae_flat_opt_acc_sums_step_f32": [P, P, P, P, P, P, c_int64, P, P, c_int, c_double,
+                                        c_double, c_float, c_float, c_int, c_float,
+                                        POINTER(SumJob), c_int, P],
+    "scae_flat_opt_acc_clip_step_f32": [P, P, P, P, P, P, c_int64, P, P, c_int, c_double,
+                                        c_double, c_float, c_float, c_float, c_int, c_float,
+                                        c_int, P, c_int, c_float, P, P],
     "scae_capsule_head_fwd_f32": [P, P, c_float, c_int, P, P, P, P, P] + [c_int] * 4 + [P],
     "scae_capsule_head_conv_supported": [c_int] * 4,
     "scae_capsule_head_conv_preferred": [c_int] * 5,

@@ -9,6 +9,8 @@
 // HBM-bound: 4 streams read, 3 written, 28 bytes per parameter.
 // The clip form (scae_rmsprop_clip_step_f32) scales g by clip_grad_norm_'s coefficient from
 // the norm launch's partials (grad_clip_dev.h) after grad_scale, before the weight decay.
+// The accumulate forms (scae_rmsprop_acc_*: gradient accumulation, grad_accumulate.hip) read
+// g = acc + grad in place of grad and leave acc = 0 behind.
 #include "grad_clip_dev.h"
 
 namespace {
@@ -40,9 +42,14 @@ __device__ __forceinline__ void update(float &p, float &v, float &b, float g, co
 }
 
 // `head` leading elements bring the (equally misaligned) buffers to a 16-byte
-// boundary; then float4 lanes; then the tail.  CLIP: g scaled by `coef`
-template <bool CLIP>
-__device__ __forceinline__ void rmsprop_pass(OptArgs a, int head, float coef) {
+// boundary; then float4 lanes; then the tail.  CLIP: g scaled by `coef`; ACC: g = acc + grad,
+// acc zeroed
+__device__ __forceinline__ float4 add4(float4 a, float4 b) {
+  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+template <bool CLIP, bool ACC = false>
+__device__ __forceinline__ void rmsprop_pass(OptArgs a, int head, float coef,
+                                             float *acc = nullptr) {
   const long stride = (long)gridDim.x * blockDim.x;
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const float lr = a.lr_dev ? a.lr_dev[0] : a.lr;
@@ -52,7 +59,11 @@ __device__ __forceinline__ void rmsprop_pass(OptArgs a, int head, float coef) {
   for (long i = tid; i < n4; i += stride) {
     float4 p = reinterpret_cast<float4 *>(p4)[i], v = reinterpret_cast<float4 *>(v4)[i];
     float4 b = b4 ? reinterpret_cast<float4 *>(b4)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 g = reinterpret_cast<const float4 *>(g4)[i];
+    float4 g = reinterpret_cast<const float4 *>(g4)[i];
+    if (ACC) {
+      g = add4(reinterpret_cast<float4 *>(acc + head)[i], g);
+      reinterpret_cast<float4 *>(acc + head)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     update<CLIP>(p.x, v.x, b.x, g.x, a, lr, coef);
     update<CLIP>(p.y, v.y, b.y, g.y, a, lr, coef);
     update<CLIP>(p.z, v.z, b.z, g.z, a, lr, coef);
@@ -66,7 +77,9 @@ __device__ __forceinline__ void rmsprop_pass(OptArgs a, int head, float coef) {
   for (long e = tid; e < edge; e += stride) {
     const long i = e < head ? e : tail0 + (e - head);
     float b = a.buf ? a.buf[i] : 0.f;
-    update<CLIP>(a.p[i], a.v[i], b, a.g[i], a, lr, coef);
+    float g = a.g[i];
+    if (ACC) g = acc[i] + g, acc[i] = 0.f;
+    update<CLIP>(a.p[i], a.v[i], b, g, a, lr, coef);
     if (a.buf) a.buf[i] = b;
   }
 }
@@ -79,6 +92,14 @@ __global__ __launch_bounds__(256) void rmsprop_clip_kernel(OptArgs a, int head,
                                                            scae_clip::Clip clip) {
   rmsprop_pass<true>(a, head, scae_clip::clip_coef(clip, a.grad_scale));
 }
+// the accumulate forms of the two above
+__global__ __launch_bounds__(256) void rmsprop_acc_kernel(OptArgs a, int head, float *acc) {
+  rmsprop_pass<false, true>(a, head, 1.f, acc);
+}
+__global__ __launch_bounds__(256) void rmsprop_acc_clip_kernel(OptArgs a, int head,
+                                                               scae_clip::Clip clip, float *acc) {
+  rmsprop_pass<true, true>(a, head, scae_clip::clip_coef(clip, a.grad_scale), acc);
+}
 // The step's LAST column sums and the optimiser in one launch.  A training step's backward
 // ends in one scae_sum_rows_multi launch whose outputs are slots of the flat gradient buffer
 // (parameter gradients nothing else reads), followed by this file's pass over the four flat
@@ -88,9 +109,12 @@ __global__ __launch_bounds__(256) void rmsprop_clip_kernel(OptArgs a, int head,
 // gradient base); the streaming workgroups behind them skip exactly those elements -- the
 // segments' destination ranges, rebuilt from the job table into LDS by every workgroup.  The
 // arithmetic per element is unchanged: the results equal the two launches' bit for bit.
+// ACC: the accumulate form (g = acc + grad, acc zeroed; the sum workgroups add acc to the
+// sums they produce and zero it there).
 using scae_sums::MAXR;
-__global__ __launch_bounds__(256) void rmsprop_sums_kernel(OptArgs a, int head,
-                                                           scae_sums::Jobs jobs, int sum_blocks) {
+template <bool ACC>
+__device__ __forceinline__ void rmsprop_sums(OptArgs a, int head, const scae_sums::Jobs &jobs,
+                                             int sum_blocks, float *acc) {
   __shared__ float red[scae_sums::NT];
   __shared__ int r_lo[MAXR], r_hi[MAXR];
   __shared__ int r_n;
@@ -101,6 +125,7 @@ __global__ __launch_bounds__(256) void rmsprop_sums_kernel(OptArgs a, int head,
       const long off = dst - a.g;
       if (off >= 0 && off < a.n) {
         float b = a.buf ? a.buf[off] : 0.f;
+        if (ACC) v = acc[off] + v, acc[off] = 0.f;
         update(a.p[off], a.v[off], b, v, a, lr);
         if (a.buf) a.buf[off] = b;
       }
@@ -118,11 +143,13 @@ __global__ __launch_bounds__(256) void rmsprop_sums_kernel(OptArgs a, int head,
     // (the loads first: the range scan runs under their latency)
     float4 p = reinterpret_cast<float4 *>(p4)[i], v = reinterpret_cast<float4 *>(v4)[i];
     float4 b = b4 ? reinterpret_cast<float4 *>(b4)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 g = reinterpret_cast<const float4 *>(g4)[i];
+    float4 g = reinterpret_cast<const float4 *>(g4)[i];
+    float4 ac = ACC ? reinterpret_cast<float4 *>(acc + head)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     const int e0 = head + 4 * (int)i;
     // bit u: element e0 + u belongs to a sum workgroup
     const int own = scae_sums::quad_owned(e0, r_lo, r_hi, nr);
     if (own == 15) continue;
+    if (ACC) g = add4(ac, g);
     update(p.x, v.x, b.x, g.x, a, lr);
     update(p.y, v.y, b.y, g.y, a, lr);
     update(p.z, v.z, b.z, g.z, a, lr);
@@ -131,6 +158,7 @@ __global__ __launch_bounds__(256) void rmsprop_sums_kernel(OptArgs a, int head,
       reinterpret_cast<float4 *>(p4)[i] = p;
       reinterpret_cast<float4 *>(v4)[i] = v;
       if (b4) reinterpret_cast<float4 *>(b4)[i] = b;
+      if (ACC) reinterpret_cast<float4 *>(acc + head)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {   // (rare: a quad that straddles the edge of an owned range)
       const float pe[4] = {p.x, p.y, p.z, p.w}, ve[4] = {v.x, v.y, v.z, v.w},
                   be[4] = {b.x, b.y, b.z, b.w};
@@ -139,6 +167,7 @@ __global__ __launch_bounds__(256) void rmsprop_sums_kernel(OptArgs a, int head,
         if (!((own >> u) & 1)) {
           p4[4 * i + u] = pe[u], v4[4 * i + u] = ve[u];
           if (b4) b4[4 * i + u] = be[u];
+          if (ACC) acc[head + 4 * i + u] = 0.f;
         }
     }
   }
@@ -147,9 +176,20 @@ __global__ __launch_bounds__(256) void rmsprop_sums_kernel(OptArgs a, int head,
     const long i = e < head ? e : tail0 + (e - head);
     if (scae_sums::owned(i, r_lo, r_hi, nr)) continue;
     float b = a.buf ? a.buf[i] : 0.f;
-    update(a.p[i], a.v[i], b, a.g[i], a, lr);
+    float g = a.g[i];
+    if (ACC) g = acc[i] + g, acc[i] = 0.f;
+    update(a.p[i], a.v[i], b, g, a, lr);
     if (a.buf) a.buf[i] = b;
   }
+}
+__global__ __launch_bounds__(256) void rmsprop_sums_kernel(OptArgs a, int head,
+                                                           scae_sums::Jobs jobs, int sum_blocks) {
+  rmsprop_sums<false>(a, head, jobs, sum_blocks, nullptr);
+}
+__global__ __launch_bounds__(256) void rmsprop_acc_sums_kernel(OptArgs a, int head,
+                                                               scae_sums::Jobs jobs,
+                                                               int sum_blocks, float *acc) {
+  rmsprop_sums<true>(a, head, jobs, sum_blocks, acc);
 }
 
 // The batch hand-over of a training step: image floats and int64 labels into the
@@ -262,5 +302,84 @@ extern "C" int scae_rmsprop_sums_step_f32(float *param, float *grad, float *squa
   blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
   scae::launch(rmsprop_sums_kernel, dim3((unsigned)(sum_blocks + blocks)), dim3(256), 0,
                      (hipStream_t)stream, a, head, js, sum_blocks);
+  return scae_launch_status();
+}
+
+// ---- the accumulate forms (gradient accumulation): g = acc + grad, acc = 0 afterwards; acc
+// n floats at the same phase within a 16-byte line as the other buffers -----------------------
+namespace {
+// the checks all accumulate forms share; -> head, or < 0
+int acc_prepare(OptArgs &a, float *param, const float *grad, float *acc, float *square_avg,
+                float *buf, int64_t n, float lr, const float *lr_dev, float alpha, float eps,
+                float momentum, float weight_decay, float grad_scale) {
+  if (!(param && grad && acc && square_avg && n > 0 && n < (1l << 31))) return -1;
+  if (momentum > 0.f && !buf) return -1;
+  const size_t phase = (size_t)param & 15;
+  if ((phase & 3) || ((size_t)grad & 15) != phase || ((size_t)acc & 15) != phase ||
+      ((size_t)square_avg & 15) != phase || (momentum > 0.f && ((size_t)buf & 15) != phase))
+    return -1;
+  a = OptArgs{param, square_avg, momentum > 0.f ? buf : nullptr, grad, lr_dev, (long)n, lr, alpha,
+              eps, momentum, weight_decay, grad_scale};
+  const int head = (int)((16 - phase) & 15) / 4;
+  return head > n ? (int)n : head;
+}
+}  // namespace
+
+extern "C" int scae_rmsprop_acc_step_f32(float *param, const float *grad, float *acc,
+                                         float *square_avg, float *buf, int64_t n, float lr,
+                                         const float *lr_dev, float alpha, float eps,
+                                         float momentum, float weight_decay, float grad_scale,
+                                         void *stream) {
+  OptArgs a;
+  const int head = acc_prepare(a, param, grad, acc, square_avg, buf, n, lr, lr_dev, alpha, eps,
+                               momentum, weight_decay, grad_scale);
+  if (head < 0) return SCAE_ERR_BAD_ARG;
+  long blocks = (n / 4 + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  scae::launch(rmsprop_acc_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a,
+               head, acc);
+  return scae_launch_status();
+}
+
+extern "C" int scae_rmsprop_acc_clip_step_f32(float *param, const float *grad, float *acc,
+                                              float *square_avg, float *buf, int64_t n, float lr,
+                                              const float *lr_dev, float alpha, float eps,
+                                              float momentum, float weight_decay,
+                                              float grad_scale, const double *partials,
+                                              int n_partials, float max_norm, float *norm_out,
+                                              void *stream) {
+  OptArgs a;
+  const int head = acc_prepare(a, param, grad, acc, square_avg, buf, n, lr, lr_dev, alpha, eps,
+                               momentum, weight_decay, grad_scale);
+  if (head < 0) return SCAE_ERR_BAD_ARG;
+  SCAE_REQUIRE(partials && n_partials > 0 && n_partials <= SCAE_GRAD_SQ_MAX_PARTIALS &&
+               max_norm > 0.f);
+  long blocks = (n / 4 + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  scae::launch(rmsprop_acc_clip_kernel, dim3((unsigned)blocks), dim3(256), 0,
+               (hipStream_t)stream, a, head,
+               scae_clip::Clip{partials, n_partials, max_norm, norm_out}, acc);
+  return scae_launch_status();
+}
+
+extern "C" int scae_rmsprop_acc_sums_step_f32(float *param, float *grad, float *acc,
+                                              float *square_avg, float *buf, int64_t n, float lr,
+                                              const float *lr_dev, float alpha, float eps,
+                                              float momentum, float grad_scale,
+                                              const scae_sum_job *jobs, int n_jobs,
+                                              void *stream) {
+  OptArgs a;
+  const int head = acc_prepare(a, param, grad, acc, square_avg, buf, n, lr, lr_dev, alpha, eps,
+                               momentum, 0.f, grad_scale);
+  if (head < 0) return SCAE_ERR_BAD_ARG;
+  scae_sums::Jobs js;
+  const int sum_blocks = scae_sums::fill_jobs(js, jobs, n_jobs);
+  SCAE_REQUIRE(sum_blocks > 0);
+  long blocks = (n / 4 + 255) / 256;
+  const long room = 2048 - sum_blocks;
+  const long cap = room > 512 ? room : 512;
+  blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
+  scae::launch(rmsprop_acc_sums_kernel, dim3((unsigned)(sum_blocks + blocks)), dim3(256), 0,
+               (hipStream_t)stream, a, head, js, sum_blocks, acc);
   return scae_launch_status();
 }

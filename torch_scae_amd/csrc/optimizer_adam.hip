@@ -21,6 +21,8 @@
 // RMSprop with momentum; a sync step 8 more.
 // The clip form (scae_flat_opt_clip_step_f32) scales g by clip_grad_norm_'s coefficient from
 // the norm launch's partials (grad_clip_dev.h) after grad_scale, before the weight decay.
+// The accumulate forms (scae_flat_opt_acc_*: gradient accumulation, grad_accumulate.hip) read
+// g = acc + grad in place of grad and leave acc = 0 behind.
 #include "grad_clip_dev.h"
 
 namespace {
@@ -151,10 +153,11 @@ __device__ __forceinline__ void look_ahead(float &p, float &slow, const AdamArgs
   }
 }
 
-// one element in place (scalar edges, sum workgroups)
-template <int K, bool CLIP = false>
+// one element in place (scalar edges, sum workgroups); ACC: g = acc + grad, acc zeroed
+template <int K, bool CLIP = false, bool ACC = false>
 __device__ __forceinline__ void update_at(const AdamArgs &a, const StepScalars &s, long i,
-                                          float g) {
+                                          float g, float *acc = nullptr) {
+  if (ACC) g = acc[i] + g, acc[i] = 0.f;
   float p = a.p[i], m = a.m[i], v = a.v[i];
   update<K, CLIP>(p, m, v, g, a, s);
   if (s.sync) {
@@ -190,14 +193,19 @@ __device__ __forceinline__ void arrive(const AdamArgs &a, const StepScalars &s) 
 }
 
 // the float4 lanes of elements [head + 4 i, head + 4 i + 4): `own` bit u set = element u is
-// not this workgroup's to write
-template <int K, bool CLIP = false>
+// not this workgroup's to write; ACC: g = acc + grad, acc zeroed
+template <int K, bool CLIP = false, bool ACC = false>
 __device__ __forceinline__ void update_quad(const AdamArgs &a, const StepScalars &s, int head,
-                                            long i, int own) {
+                                            long i, int own, float *acc = nullptr) {
   float *p4 = a.p + head, *m4 = a.m + head, *v4 = a.v + head, *s4 = a.slow + head;
   float4 p = reinterpret_cast<float4 *>(p4)[i], m = reinterpret_cast<float4 *>(m4)[i],
          v = reinterpret_cast<float4 *>(v4)[i];
-  const float4 g = reinterpret_cast<const float4 *>(a.g + head)[i];
+  float4 g = reinterpret_cast<const float4 *>(a.g + head)[i];
+  float *a4 = acc + head;
+  if (ACC) {
+    const float4 ac = reinterpret_cast<float4 *>(a4)[i];
+    g = make_float4(ac.x + g.x, ac.y + g.y, ac.z + g.z, ac.w + g.w);
+  }
   update<K, CLIP>(p.x, m.x, v.x, g.x, a, s);
   update<K, CLIP>(p.y, m.y, v.y, g.y, a, s);
   update<K, CLIP>(p.z, m.z, v.z, g.z, a, s);
@@ -215,12 +223,16 @@ __device__ __forceinline__ void update_quad(const AdamArgs &a, const StepScalars
     reinterpret_cast<float4 *>(m4)[i] = m;
     reinterpret_cast<float4 *>(v4)[i] = v;
     if (s.sync) reinterpret_cast<float4 *>(s4)[i] = sl;
+    if (ACC) reinterpret_cast<float4 *>(a4)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   } else {   // (rare: a quad that straddles the edge of a range the sum workgroups own)
     const float pe[4] = {p.x, p.y, p.z, p.w}, me[4] = {m.x, m.y, m.z, m.w},
                 ve[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int u = 0; u < 4; ++u)
-      if (!((own >> u) & 1)) p4[4 * i + u] = pe[u], m4[4 * i + u] = me[u], v4[4 * i + u] = ve[u];
+      if (!((own >> u) & 1)) {
+        p4[4 * i + u] = pe[u], m4[4 * i + u] = me[u], v4[4 * i + u] = ve[u];
+        if (ACC) a4[4 * i + u] = 0.f;
+      }
     if (s.sync) {
       const float se[4] = {sl.x, sl.y, sl.z, sl.w};
 #pragma unroll
@@ -232,16 +244,17 @@ __device__ __forceinline__ void update_quad(const AdamArgs &a, const StepScalars
 
 // `head` leading elements bring the (equally misaligned) buffers to a 16-byte boundary; then
 // float4 lanes; then the tail
-template <int K, bool CLIP>
-__device__ __forceinline__ void adam_pass(const AdamArgs &a, int head, const StepScalars &s) {
+template <int K, bool CLIP, bool ACC = false>
+__device__ __forceinline__ void adam_pass(const AdamArgs &a, int head, const StepScalars &s,
+                                          float *acc = nullptr) {
   const long stride = (long)gridDim.x * blockDim.x;
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long n4 = (a.n - head) >> 2;
-  for (long i = tid; i < n4; i += stride) update_quad<K, CLIP>(a, s, head, i, 0);
+  for (long i = tid; i < n4; i += stride) update_quad<K, CLIP, ACC>(a, s, head, i, 0, acc);
   const long tail0 = head + (n4 << 2), edge = head + (a.n - tail0);
   for (long e = tid; e < edge; e += stride) {
     const long i = e < head ? e : tail0 + (e - head);
-    update_at<K, CLIP>(a, s, i, a.g[i]);
+    update_at<K, CLIP, ACC>(a, s, i, a.g[i], acc);
   }
   arrive(a, s);
 }
@@ -256,16 +269,28 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(AdamArgs a, int head,
                                                         scae_clip::Clip clip) {
   adam_pass<K, true>(a, head, shared_scalars<K, true>(a, &clip));
 }
+// the accumulate forms of the two above
+template <int K>
+__global__ __launch_bounds__(256) void adam_acc_kernel(AdamArgs a, int head, float *acc) {
+  adam_pass<K, false, true>(a, head, shared_scalars<K>(a), acc);
+}
+template <int K>
+__global__ __launch_bounds__(256) void adam_acc_clip_kernel(AdamArgs a, int head,
+                                                            scae_clip::Clip clip, float *acc) {
+  adam_pass<K, true, true>(a, head, shared_scalars<K, true>(a, &clip), acc);
+}
 
 // The step's last column sums and the optimiser in one launch, as optimizer.hip's
 // rmsprop_sums_kernel: the sum workgroups (the head of the grid) update the elements they
 // produce, the streaming workgroups behind them skip exactly those (the segments' destination
 // ranges, rebuilt from the job table into LDS by every workgroup).  Same arithmetic per element:
 // the results equal the two launches' bit for bit.
+// ACC: the accumulate form.
 using scae_sums::MAXR;
-template <int K>
-__global__ __launch_bounds__(256) void adam_sums_kernel(AdamArgs a, int head, scae_sums::Jobs jobs,
-                                                        int sum_blocks) {
+template <int K, bool ACC>
+__device__ __forceinline__ void adam_sums(const AdamArgs &a, int head,
+                                          const scae_sums::Jobs &jobs, int sum_blocks,
+                                          float *acc) {
   __shared__ float red[scae_sums::NT];
   __shared__ int r_lo[MAXR], r_hi[MAXR];
   __shared__ int r_n;
@@ -274,7 +299,7 @@ __global__ __launch_bounds__(256) void adam_sums_kernel(AdamArgs a, int head, sc
     scae_sums::sum_block(jobs, blockIdx.x, red, [&](float *dst, float v) {
       *dst = v;
       const long off = dst - a.g;
-      if (off >= 0 && off < a.n) update_at<K>(a, s, off, v);
+      if (off >= 0 && off < a.n) update_at<K, false, ACC>(a, s, off, v, acc);
     });
     arrive(a, s);
     return;
@@ -288,14 +313,25 @@ __global__ __launch_bounds__(256) void adam_sums_kernel(AdamArgs a, int head, sc
     const int e0 = head + 4 * (int)i;
     // bit u: element e0 + u belongs to a sum workgroup
     const int own = scae_sums::quad_owned(e0, r_lo, r_hi, nr);
-    if (own != 15) update_quad<K>(a, s, head, i, own);
+    if (own != 15) update_quad<K, false, ACC>(a, s, head, i, own, acc);
   }
   const long tail0 = head + (n4 << 2), edge = head + (a.n - tail0);
   for (long e = tid; e < edge; e += stride) {
     const long i = e < head ? e : tail0 + (e - head);
-    if (!scae_sums::owned(i, r_lo, r_hi, nr)) update_at<K>(a, s, i, a.g[i]);
+    if (!scae_sums::owned(i, r_lo, r_hi, nr)) update_at<K, false, ACC>(a, s, i, a.g[i], acc);
   }
   arrive(a, s);
+}
+template <int K>
+__global__ __launch_bounds__(256) void adam_sums_kernel(AdamArgs a, int head, scae_sums::Jobs jobs,
+                                                        int sum_blocks) {
+  adam_sums<K, false>(a, head, jobs, sum_blocks, nullptr);
+}
+template <int K>
+__global__ __launch_bounds__(256) void adam_acc_sums_kernel(AdamArgs a, int head,
+                                                            scae_sums::Jobs jobs, int sum_blocks,
+                                                            float *acc) {
+  adam_sums<K, true>(a, head, jobs, sum_blocks, acc);
 }
 
 // the checks both entry points share; -> head, or < 0
@@ -329,6 +365,9 @@ void launch_kind(int kind, dim3 grid, hipStream_t st, T... args) {
 template <int K> struct Plain { static constexpr auto fn = adam_kernel<K>; };
 template <int K> struct Sums { static constexpr auto fn = adam_sums_kernel<K>; };
 template <int K> struct Clipped { static constexpr auto fn = adam_clip_kernel<K>; };
+template <int K> struct AccPlain { static constexpr auto fn = adam_acc_kernel<K>; };
+template <int K> struct AccSums { static constexpr auto fn = adam_acc_sums_kernel<K>; };
+template <int K> struct AccClipped { static constexpr auto fn = adam_acc_clip_kernel<K>; };
 
 extern "C" int scae_flat_opt_step_f32(float *param, const float *grad, float *exp_avg,
                                       float *exp_avg_sq, float *slow, int64_t n,
@@ -392,5 +431,76 @@ extern "C" int scae_flat_opt_clip_step_f32(float *param, const float *grad, floa
   blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
   launch_kind<Clipped>(kind, dim3((unsigned)blocks), (hipStream_t)stream, a, head,
                        scae_clip::Clip{partials, n_partials, max_norm, norm_out});
+  return scae_launch_status();
+}
+
+// ---- the accumulate forms (gradient accumulation): the three entry points above with
+// g = acc + grad; acc (n floats at the buffers' phase in a 16-byte line) is 0 afterwards -----
+static bool acc_ok(const float *acc, const float *param) {
+  return acc && ((size_t)acc & 15) == ((size_t)param & 15);
+}
+
+extern "C" int scae_flat_opt_acc_step_f32(float *param, const float *grad, float *acc,
+                                          float *exp_avg, float *exp_avg_sq, float *slow,
+                                          int64_t n, const float *lr_dev, int32_t *step_state,
+                                          int kind, double beta1, double beta2, float eps,
+                                          float weight_decay, float grad_scale, int look_ahead_k,
+                                          float look_ahead_alpha, int advance, void *stream) {
+  AdamArgs a;
+  const int head = prepare(a, param, grad, exp_avg, exp_avg_sq, slow, n, lr_dev, step_state,
+                           kind, beta1, beta2, eps, weight_decay, grad_scale, look_ahead_k,
+                           look_ahead_alpha, advance);
+  if (head < 0 || !acc_ok(acc, param)) return SCAE_ERR_BAD_ARG;
+  long blocks = (n / 4 + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  launch_kind<AccPlain>(kind, dim3((unsigned)blocks), (hipStream_t)stream, a, head, acc);
+  return scae_launch_status();
+}
+
+extern "C" int scae_flat_opt_acc_sums_step_f32(float *param, float *grad, float *acc,
+                                               float *exp_avg, float *exp_avg_sq, float *slow,
+                                               int64_t n, const float *lr_dev,
+                                               int32_t *step_state, int kind, double beta1,
+                                               double beta2, float eps, float grad_scale,
+                                               int look_ahead_k, float look_ahead_alpha,
+                                               const scae_sum_job *jobs, int n_jobs,
+                                               void *stream) {
+  AdamArgs a;
+  const int head = prepare(a, param, grad, exp_avg, exp_avg_sq, slow, n, lr_dev, step_state,
+                           kind, beta1, beta2, eps, 0.f, grad_scale, look_ahead_k,
+                           look_ahead_alpha, 1);
+  if (head < 0 || !acc_ok(acc, param)) return SCAE_ERR_BAD_ARG;
+  scae_sums::Jobs js;
+  const int sum_blocks = scae_sums::fill_jobs(js, jobs, n_jobs);
+  SCAE_REQUIRE(sum_blocks > 0);
+  long blocks = (n / 4 + 255) / 256;
+  const long room = 2048 - sum_blocks;
+  const long cap = room > 512 ? room : 512;
+  blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
+  launch_kind<AccSums>(kind, dim3((unsigned)(sum_blocks + blocks)), (hipStream_t)stream, a, head,
+                       js, sum_blocks, acc);
+  return scae_launch_status();
+}
+
+extern "C" int scae_flat_opt_acc_clip_step_f32(float *param, const float *grad, float *acc,
+                                               float *exp_avg, float *exp_avg_sq, float *slow,
+                                               int64_t n, const float *lr_dev,
+                                               int32_t *step_state, int kind, double beta1,
+                                               double beta2, float eps, float weight_decay,
+                                               float grad_scale, int look_ahead_k,
+                                               float look_ahead_alpha, int advance,
+                                               const double *partials, int n_partials,
+                                               float max_norm, float *norm_out, void *stream) {
+  AdamArgs a;
+  const int head = prepare(a, param, grad, exp_avg, exp_avg_sq, slow, n, lr_dev, step_state,
+                           kind, beta1, beta2, eps, weight_decay, grad_scale, look_ahead_k,
+                           look_ahead_alpha, advance);
+  if (head < 0 || !acc_ok(acc, param)) return SCAE_ERR_BAD_ARG;
+  SCAE_REQUIRE(partials && n_partials > 0 && n_partials <= SCAE_GRAD_SQ_MAX_PARTIALS &&
+               max_norm > 0.f);
+  long blocks = (n / 4 + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  launch_kind<AccClipped>(kind, dim3((unsigned)blocks), (hipStream_t)stream, a, head,
+                          scae_clip::Clip{partials, n_partials, max_norm, norm_out}, acc);
   return scae_launch_status();
 }

@@ -166,14 +166,16 @@ class FlatParameters:
                 v.zero_()
             p._flat_was_set = p.grad is not None
 
-    def active_ranges(self):
+    def active_ranges(self, also=None):
         """[(offset, numel)] of the maximal runs of parameters that received a
         gradient in the last backward (torch optimisers skip ``grad is None``
-        parameters altogether -- it matters with weight decay)."""
+        parameters altogether -- it matters with weight decay).  ``also``: a flag
+        per parameter that counts it in too (a gradient in an earlier batch of an
+        accumulated group)."""
         runs = []
-        for p, off in zip(self.params, self.offsets):
+        for i, (p, off) in enumerate(zip(self.params, self.offsets)):
             n = p.numel()
-            if getattr(p, "_flat_was_set", True):
+            if getattr(p, "_flat_was_set", True) or (also is not None and also[i]):
                 if runs and runs[-1][0] + runs[-1][1] == off:
                     runs[-1][1] += n
                 else:
@@ -223,7 +225,101 @@ def all_reduce_gradients(flat: FlatParameters, async_op=False, average=True,
     return dist.all_reduce(g, op=dist.ReduceOp.SUM, async_op=async_op)
 
 
-class RMSpropFlat:
+class _Accumulating:
+    """Gradient accumulation over k batches (Lightning's Trainer(accumulate_grad_batches=k)),
+    shared by the flat optimisers: ``acc``, a buffer laid out like ``flat_grad`` (None for
+    k = 1), collects the gradients of a group's batches (``accumulate``: acc += g, in batch
+    order, fp32); the group's last batch steps through the accumulate forms of the passes,
+    which read g_eff = grad_scale (acc + g) and leave acc = 0.  The caller folds 1/k into
+    ``grad_scale``.  Weight decay applies to the parameters that had a gradient in ANY batch
+    of the group (torch skips only ``grad is None`` parameters)."""
+
+    @torch.no_grad()
+    def accumulate(self, sum_units=None):
+        """acc <- acc + g (HIP: scae_grad_accumulate_f32; ``sum_units``, the step's column
+        sums not launched yet, ride in the launch: scae_grad_accumulate_sums_f32)."""
+        if self.acc is None:
+            raise ValueError("this optimiser does not accumulate (accumulate_grad_batches=1)")
+        flat = self.flat
+        g = flat.flat_grad
+        self._acc_seen = _group_seen(self)
+        if sum_units:
+            from . import ops
+            if not g.is_cuda:
+                ops._launch_sum_units(sum_units)
+                sum_units = None
+            elif len(sum_units) > 16:
+                ops._launch_sum_units(sum_units[:-16])
+                sum_units = sum_units[-16:]
+        if not g.is_cuda:
+            self.acc.add_(g)
+            return
+        from . import _lib, ops
+        P = ctypes.c_void_p
+        st = P(torch.cuda.current_stream(g.device).cuda_stream)
+        if sum_units:
+            _lib.call("scae_grad_accumulate_sums_f32", P(self.acc.data_ptr()), P(g.data_ptr()),
+                      g.numel(), ops._sum_job_array(sum_units), len(sum_units), st)
+        else:
+            _lib.call("scae_grad_accumulate_f32", P(self.acc.data_ptr()), P(g.data_ptr()),
+                      g.numel(), st)
+
+    @torch.no_grad()
+    def fold(self):
+        """g <- g + acc, acc <- 0: the group's gradient in the flat gradient buffer, for an
+        all-reduce of that buffer and the plain pass (``step(with_acc=False)``)."""
+        g = self.flat.flat_grad
+        if g.is_cuda:
+            from . import _lib
+            P = ctypes.c_void_p
+            _lib.call("scae_grad_accumulate_f32", P(g.data_ptr()), P(self.acc.data_ptr()),
+                      g.numel(), P(torch.cuda.current_stream(g.device).cuda_stream))
+        else:
+            g.add_(self.acc)
+        self.acc.zero_()
+
+    @torch.no_grad()
+    def flush(self, grad_scale):
+        """One step on acc alone (a group that ended before its k-th batch): the flat
+        gradient buffer zeroed, then the accumulate form."""
+        self.flat.flat_grad.zero_()
+        self.step(grad_scale=grad_scale)
+
+
+def accumulate_value(v):
+    """``accumulate_grad_batches`` as an int >= 1; a bool, another type (a per-epoch dict
+    schedule included) or a value < 1 is an error."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or int(v) < 1:
+        raise ValueError(f"accumulate_grad_batches must be an int >= 1, got {v!r}")
+    return int(v)
+
+
+def _init_accumulate(opt, k):
+    opt.accumulate_grad_batches = accumulate_value(k)
+    opt.acc = torch.zeros_like(opt.flat.flat_grad) if opt.accumulate_grad_batches > 1 \
+        else None
+    opt._acc_seen = None     # per parameter: a gradient in an earlier batch of the group
+
+
+def _group_seen(opt):
+    """Per parameter: a gradient in the last backward or an earlier batch of the group."""
+    now = [getattr(p, "_flat_was_set", True) for p in opt.flat.params]
+    seen = getattr(opt, "_acc_seen", None)
+    return now if seen is None else [a or b for a, b in zip(now, seen)]
+
+
+def _take_ranges(opt):
+    """The ranges an optimiser step updates (with weight decay: the parameters with a
+    gradient, in the group when accumulating; else the whole buffer); ends the group."""
+    g = opt.flat.flat_grad
+    seen = getattr(opt, "_acc_seen", None)
+    opt._acc_seen = None
+    if opt.weight_decay == 0:
+        return [(0, g.numel())]
+    return opt.flat.active_ranges(also=seen)
+
+
+class RMSpropFlat(_Accumulating):
     """RMSprop with momentum on the flat buffers -- the reference's default
     optimiser (torch.optim.RMSprop(lr, momentum=0.9, eps=1e-2/bs**2,
     weight_decay), base_experiment.py:44-77) as ONE fused pass over the flat
@@ -236,7 +332,8 @@ class RMSpropFlat:
 
     def __init__(self, flat: FlatParameters, lr=3e-5, alpha=0.99, eps=1e-8,
                  momentum=0.9, weight_decay=0.0, look_ahead=False,
-                 look_ahead_k=5, look_ahead_alpha=0.5, gradient_clip_val=0.0):
+                 look_ahead_k=5, look_ahead_alpha=0.5, gradient_clip_val=0.0,
+                 accumulate_grad_batches=1):
         self.flat = flat
         self.lr, self.alpha, self.eps, self.momentum = lr, alpha, eps, momentum
         self.weight_decay = weight_decay
@@ -246,6 +343,7 @@ class RMSpropFlat:
                                  dtype=flat.flat_param.dtype)
         _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
         _init_clip(self, gradient_clip_val)
+        _init_accumulate(self, accumulate_grad_batches)
 
     def set_lr(self, lr):
         self.lr = float(lr)
@@ -256,20 +354,23 @@ class RMSpropFlat:
         self.set_lr(self.lr * gamma)
 
     @torch.no_grad()
-    def step(self, grad_scale=1.0, sum_units=None):
+    def step(self, grad_scale=1.0, sum_units=None, with_acc=True):
         """``grad_scale`` multiplies the gradient on the fly (1/world after a
         SUM all-reduce).  ``sum_units``: column-sum units (``ops._sum_rows_multi``)
         whose outputs are slots of the flat gradient buffer and which have NOT
         been launched yet: they ride in this step's launch
         (``scae_rmsprop_sums_step_f32``: the sum workgroups update the elements
-        they produce), bit for bit the two launches' result."""
+        they produce), bit for bit the two launches' result.  Accumulating
+        (``acc``, unless ``with_acc`` is False): the gradient is acc + g, and acc is 0
+        afterwards."""
+        acc = self.acc if with_acc else None
         if self.look_ahead_k:     # (the fused form that counts steps)
             _fused_step(self, self.buf, self.square_avg,
                         (self.momentum, self.alpha), grad_scale, sum_units,
-                        self._cpu_update)
+                        self._cpu_update, acc)
             return
         if self.max_norm:
-            self._clipped_step(grad_scale, sum_units)
+            self._clipped_step(grad_scale, sum_units, acc)
             return
         g = self.flat.flat_grad
         if sum_units:
@@ -282,8 +383,10 @@ class RMSpropFlat:
                 sum_units = sum_units[-16:]
         # parameters without a gradient are left alone, like torch.optim does;
         # without weight decay a zero gradient already is a no-op
-        ranges = self.flat.active_ranges() if self.weight_decay != 0 else \
-            [(0, g.numel())]
+        ranges = _take_ranges(self)
+        if g.is_cuda and acc is not None:
+            self._acc_step(g, acc, ranges, grad_scale, sum_units)
+            return
         if g.is_cuda:      # one fused pass over the four flat buffers
             from . import _lib
             P = ctypes.c_void_p
@@ -305,6 +408,9 @@ class RMSpropFlat:
                           self.eps, self.momentum, self.weight_decay,
                           float(grad_scale), st)
             return
+        if acc is not None:
+            g = acc + g
+            acc.zero_()
         if grad_scale != 1.0:
             g = g * grad_scale
         if self.weight_decay != 0:
@@ -326,28 +432,55 @@ class RMSpropFlat:
                                  self.buf), saved):
                 cur.copy_(torch.where(keep, cur, old))
 
-    def _clipped_step(self, grad_scale, sum_units):
+    def _acc_step(self, g, acc, ranges, grad_scale, sum_units):
+        """The accumulate forms of the two plain launches above (g = acc + g, acc -> 0)."""
+        from . import _lib
+        P = ctypes.c_void_p
+        st = P(torch.cuda.current_stream(g.device).cuda_stream)
+        if sum_units:
+            from . import ops
+            _lib.call("scae_rmsprop_acc_sums_step_f32", P(self.flat.flat_param.data_ptr()),
+                      P(g.data_ptr()), P(acc.data_ptr()), P(self.square_avg.data_ptr()),
+                      P(self.buf.data_ptr()), g.numel(), self.lr, P(self.lr_dev.data_ptr()),
+                      self.alpha, self.eps, self.momentum, float(grad_scale),
+                      ops._sum_job_array(sum_units), len(sum_units), st)
+            return
+        for off, n in ranges:
+            ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
+            _lib.call("scae_rmsprop_acc_step_f32", ptr(self.flat.flat_param), ptr(g), ptr(acc),
+                      ptr(self.square_avg), ptr(self.buf), n, self.lr,
+                      P(self.lr_dev.data_ptr()), self.alpha, self.eps, self.momentum,
+                      self.weight_decay, float(grad_scale), st)
+
+    def _clipped_step(self, grad_scale, sum_units, acc=None):
         """``step`` with clipping by global norm: the norm launch (``sum_units`` ride in
         it), then scae_rmsprop_clip_step_f32 over each active range; on CPU tensors
-        ``_cpu_update`` on the clipped gradient."""
+        ``_cpu_update`` on the clipped gradient.  ``acc``: of acc + g (the accumulate
+        forms), acc -> 0."""
         flat = self.flat
         g = flat.flat_grad
-        ranges = flat.active_ranges() if self.weight_decay != 0 else [(0, g.numel())]
+        seen = _group_seen(self)
+        ranges = _take_ranges(self)
         if not g.is_cuda:
             if sum_units:
                 from . import ops
                 ops._launch_sum_units(sum_units)
+            if acc is not None:
+                g = acc + g
+                acc.zero_()
             saved = _keep_inactive(self, ranges, [flat.flat_param, self.square_avg, self.buf])
-            self._cpu_update(_cpu_clipped_grad(self, g, grad_scale), None)
+            self._cpu_update(_cpu_clipped_grad(self, g, grad_scale, seen), None)
             _restore_inactive(saved)
             return
         from . import _lib
         P = ctypes.c_void_p
         st = P(torch.cuda.current_stream(g.device).cuda_stream)
-        n_partials = _launch_norm(self, g, sum_units, st)
+        n_partials = _launch_norm(self, g, sum_units, st, acc)
         for i, (off, n) in enumerate(ranges):
             ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
-            _lib.call("scae_rmsprop_clip_step_f32", ptr(flat.flat_param), ptr(g),
+            name, a = ("scae_rmsprop_clip_step_f32", ()) if acc is None else \
+                ("scae_rmsprop_acc_clip_step_f32", (ptr(acc),))
+            _lib.call(name, ptr(flat.flat_param), ptr(g), *a,
                       ptr(self.square_avg), ptr(self.buf), n, self.lr,
                       P(self.lr_dev.data_ptr()), self.alpha, self.eps, self.momentum,
                       self.weight_decay, float(grad_scale), P(self.grad_sq.data_ptr()),
@@ -423,9 +556,10 @@ def _init_clip(opt, gradient_clip_val):
         opt.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
 
 
-def _launch_norm(opt, g, sum_units, st):
+def _launch_norm(opt, g, sum_units, st, acc=None):
     """The gradient's fp64 partial sums of squares into ``opt.grad_sq`` (the last 16 column-sum
-    units ride in the launch, the rest are launched first); -> the partial count."""
+    units ride in the launch, the rest are launched first); -> the partial count.  ``acc``: of
+    acc + g (the accumulate forms)."""
     from . import _lib
     P = ctypes.c_void_p
     cnt = ctypes.c_int(0)
@@ -434,25 +568,36 @@ def _launch_norm(opt, g, sum_units, st):
         if len(sum_units) > 16:
             ops._launch_sum_units(sum_units[:-16])
             sum_units = sum_units[-16:]
+        if acc is not None:
+            _lib.call("scae_grad_sq_acc_partials_sums_f32", P(g.data_ptr()), P(acc.data_ptr()),
+                      g.numel(), P(opt.grad_sq.data_ptr()), opt.grad_sq.numel(),
+                      ctypes.byref(cnt), ops._sum_job_array(sum_units), len(sum_units), st)
+            return cnt.value
         _lib.call("scae_grad_sq_partials_sums_f32", P(g.data_ptr()), g.numel(),
                   P(opt.grad_sq.data_ptr()), opt.grad_sq.numel(), ctypes.byref(cnt),
                   ops._sum_job_array(sum_units), len(sum_units), st)
+    elif acc is not None:
+        _lib.call("scae_grad_sq_acc_partials_f32", P(g.data_ptr()), P(acc.data_ptr()),
+                  g.numel(), P(opt.grad_sq.data_ptr()), opt.grad_sq.numel(), ctypes.byref(cnt),
+                  st)
     else:
         _lib.call("scae_grad_sq_partials_f32", P(g.data_ptr()), g.numel(),
                   P(opt.grad_sq.data_ptr()), opt.grad_sq.numel(), ctypes.byref(cnt), st)
     return cnt.value
 
 
-def _cpu_clipped_grad(opt, g, grad_scale):
+def _cpu_clipped_grad(opt, g, grad_scale, seen=None):
     """The CPU form: torch.nn.utils.clip_grad_norm_'s arithmetic on the (scaled) gradients of
     the parameters that have one (a norm per parameter, then the norm of those), applied to
-    the whole flat gradient; the norm into ``opt.grad_norm``."""
+    the whole flat gradient; the norm into ``opt.grad_norm``.  ``seen``: which parameters
+    have one (default: a gradient in the last backward)."""
     if grad_scale != 1.0:
         g = g * grad_scale
     flat = opt.flat
+    if seen is None:
+        seen = [getattr(p, "_flat_was_set", True) for p in flat.params]
     norms = [torch.linalg.vector_norm(g[off:off + p.numel()])
-             for p, off in zip(flat.params, flat.offsets)
-             if getattr(p, "_flat_was_set", True)]
+             for p, off, s in zip(flat.params, flat.offsets, seen) if s]
     total = torch.linalg.vector_norm(torch.stack(norms)) if norms else g.new_zeros(())
     opt.grad_norm.copy_(total)
     coef = torch.clamp(opt.max_norm / (total + 1e-6), max=1.0)
@@ -496,18 +641,22 @@ def _split_sums(opt, g, sum_units):
 
 
 @torch.no_grad()
-def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update):
+def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update, acc=None):
     """One step of ``opt`` through scae_flat_opt_step_f32 / scae_flat_opt_sums_step_f32
     (HIP device) or ``cpu_update(g, t)`` + LookAhead in whole-buffer torch ops (CPU
     tensors: the host-logic tests).  Parameters without a gradient are left alone,
     like torch.optim does; without weight decay a zero gradient already is a no-op
-    (zero moments stay zero, LookAhead's slow copy of such a parameter equals it)."""
+    (zero moments stay zero, LookAhead's slow copy of such a parameter equals it).
+    ``acc``: the accumulate forms (scae_flat_opt_acc_*: the gradient is acc + g, acc -> 0)."""
     flat = opt.flat
     g = flat.flat_grad
     clip = opt.max_norm and g.is_cuda
     sum_units = _split_sums(opt, g, sum_units) if not clip else sum_units
-    ranges = flat.active_ranges() if opt.weight_decay != 0 else \
-        [(0, g.numel())]
+    seen = _group_seen(opt)
+    ranges = _take_ranges(opt)
+    # the accumulate forms take acc right after grad
+    A = "" if acc is None else "_acc"
+    ac = lambda off: () if acc is None else (ctypes.c_void_p(acc.data_ptr() + 4 * off),)  # noqa: E731
     if g.is_cuda:
         from . import _lib
         P = ctypes.c_void_p
@@ -516,11 +665,11 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update):
         common = (P(opt.lr_dev.data_ptr()), P(opt.step_state.data_ptr()),
                   opt.kind, float(betas[0]), float(betas[1]), float(opt.eps))
         if clip:     # the norm launch (the column sums ride in it), then the clip forms
-            n_partials = _launch_norm(opt, g, sum_units, st)
+            n_partials = _launch_norm(opt, g, sum_units, st, acc)
             for i, (off, n) in enumerate(ranges):
                 ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
-                _lib.call("scae_flat_opt_clip_step_f32", ptr(flat.flat_param), ptr(g),
-                          ptr(m), ptr(v), ptr(slow), n, *common, float(opt.weight_decay),
+                _lib.call(f"scae_flat_opt{A}_clip_step_f32", ptr(flat.flat_param), ptr(g),
+                          *ac(off), ptr(m), ptr(v), ptr(slow), n, *common, float(opt.weight_decay),
                           float(grad_scale), opt.look_ahead_k, opt.look_ahead_alpha,
                           int(i == len(ranges) - 1), P(opt.grad_sq.data_ptr()), n_partials,
                           opt.max_norm, P(opt.grad_norm.data_ptr()) if i == 0 else None, st)
@@ -528,8 +677,8 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update):
         if sum_units:
             from . import ops
             arr = ops._sum_job_array(sum_units)
-            _lib.call("scae_flat_opt_sums_step_f32", P(flat.flat_param.data_ptr()),
-                      P(g.data_ptr()), P(m.data_ptr()), P(v.data_ptr()),
+            _lib.call(f"scae_flat_opt{A}_sums_step_f32", P(flat.flat_param.data_ptr()),
+                      P(g.data_ptr()), *ac(0), P(m.data_ptr()), P(v.data_ptr()),
                       P(slow.data_ptr()), g.numel(), *common, float(grad_scale),
                       opt.look_ahead_k, opt.look_ahead_alpha, arr, len(sum_units), st)
             return
@@ -537,15 +686,18 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update):
             ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
             # (one launch per step advances the count: the last, so that every
             # range reads the same t)
-            _lib.call("scae_flat_opt_step_f32", ptr(flat.flat_param), ptr(g), ptr(m),
-                      ptr(v), ptr(slow), n, *common, float(opt.weight_decay),
+            _lib.call(f"scae_flat_opt{A}_step_f32", ptr(flat.flat_param), ptr(g), *ac(off),
+                      ptr(m), ptr(v), ptr(slow), n, *common, float(opt.weight_decay),
                       float(grad_scale), opt.look_ahead_k, opt.look_ahead_alpha,
                       int(i == len(ranges) - 1), st)
         return
+    if acc is not None:     # (acc -> 0 even when no parameter takes the step)
+        g = acc + g
+        acc.zero_()
     if not ranges:
         return
     if opt.max_norm:
-        g = _cpu_clipped_grad(opt, g, grad_scale)
+        g = _cpu_clipped_grad(opt, g, grad_scale, seen)
     elif grad_scale != 1.0:
         g = g * grad_scale
     bufs = [flat.flat_param, m, v] + ([opt.slow] if opt.slow is not None else [])
@@ -571,7 +723,7 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update):
     opt.step_state[0] = t
 
 
-class _FlatAdamBase:
+class _FlatAdamBase(_Accumulating):
     """What AdamFlat and RAdamFlat share: the surface of RMSpropFlat
     (``step(grad_scale, sum_units)``, ``set_lr``, ``decay_lr``, ``lr``,
     ``lr_dev``), two moment buffers, the step count in device memory and
@@ -582,7 +734,7 @@ class _FlatAdamBase:
 
     def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=0.0, look_ahead=False, look_ahead_k=5,
-                 look_ahead_alpha=0.5, gradient_clip_val=0.0):
+                 look_ahead_alpha=0.5, gradient_clip_val=0.0, accumulate_grad_batches=1):
         b1, b2 = (float(b) for b in betas)
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
             raise ValueError(f"betas must lie in [0, 1), got {betas}")
@@ -595,6 +747,7 @@ class _FlatAdamBase:
                                  dtype=flat.flat_param.dtype)
         _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
         _init_clip(self, gradient_clip_val)
+        _init_accumulate(self, accumulate_grad_batches)
 
     def set_lr(self, lr):
         self.lr = float(lr)
@@ -604,11 +757,12 @@ class _FlatAdamBase:
         """One ExponentialLR step (call once per epoch, gamma = decay_rate)."""
         self.set_lr(self.lr * gamma)
 
-    def step(self, grad_scale=1.0, sum_units=None):
+    def step(self, grad_scale=1.0, sum_units=None, with_acc=True):
         """As ``RMSpropFlat.step``: ``grad_scale`` multiplies the gradient on
-        the fly, ``sum_units`` ride in the launch (scae_flat_opt_sums_step_f32)."""
+        the fly, ``sum_units`` ride in the launch (scae_flat_opt_sums_step_f32);
+        accumulating, the gradient is acc + g and acc is 0 afterwards."""
         _fused_step(self, self.exp_avg, self.exp_avg_sq, self.betas, grad_scale,
-                    sum_units, self._cpu_update)
+                    sum_units, self._cpu_update, self.acc if with_acc else None)
 
     def state_buffers(self):
         """(torch.optim's state key, flat buffer) pairs."""
@@ -669,12 +823,14 @@ class RAdamFlat(_FlatAdamBase):
 
 def make_optimizer(kind, flat, lr, eps, betas=(0.9, 0.999), momentum=0.9,
                    weight_decay=0.0, look_ahead=False, look_ahead_k=5,
-                   look_ahead_alpha=0.5, gradient_clip_val=0.0):
+                   look_ahead_alpha=0.5, gradient_clip_val=0.0, accumulate_grad_batches=1):
     """``kind``: "rmsprop" | "adam" | "radam" (any case) -> the flat optimiser.
-    ``gradient_clip_val`` > 0: every step clips the gradient to that global norm first."""
+    ``gradient_clip_val`` > 0: every step clips the gradient to that global norm first.
+    ``accumulate_grad_batches`` > 1: the optimiser keeps an accumulator (``accumulate``)."""
     name = str(kind).lower()
     la = dict(look_ahead=look_ahead, look_ahead_k=look_ahead_k,
-              look_ahead_alpha=look_ahead_alpha, gradient_clip_val=gradient_clip_val)
+              look_ahead_alpha=look_ahead_alpha, gradient_clip_val=gradient_clip_val,
+              accumulate_grad_batches=accumulate_grad_batches)
     if name == "rmsprop":
         return RMSpropFlat(flat, lr=lr, momentum=momentum, eps=eps,
                            weight_decay=weight_decay, **la)

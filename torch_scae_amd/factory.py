@@ -166,11 +166,13 @@ def make_train_step(model, cfg: dict, **kw):
     ``data_loader.batch_size`` (eps = 1e-2 / batch_size**2),
     ``model.image_shape`` and, when present, ``trainer.gradient_clip_val`` (the
     ``Trainer(**cfg.trainer)`` of train.py:40: clipping by global norm, off
-    when absent or <= 0; a non-numeric or non-finite value raises ValueError).  The reference reads LookAhead's k and alpha from
+    when absent or <= 0; a non-numeric or non-finite value raises ValueError) and
+    ``trainer.accumulate_grad_batches`` (gradient accumulation over that many batches: 1 when
+    absent; anything but an int >= 1 raises ValueError).  The reference reads LookAhead's k and alpha from
     ``cfg.optimizer``, where none of its yaml files defines them
     (base_experiment.py:67-70); they are read from ``meta_optimizer`` here,
     where config.yaml puts them.  ``kw``: further TrainStep arguments."""
-    from .data_parallel import clip_value
+    from .data_parallel import accumulate_value, clip_value
     from .train_step import TrainStep
     opt = cfg["optimizer"]
     kind = _OPTIMIZERS.get(opt["type"])
@@ -188,8 +190,12 @@ def make_train_step(model, cfg: dict, **kw):
                 look_ahead_alpha=float(meta.get("look_ahead_alpha", 0.5)))
     if kind == "rmsprop":
         args["momentum"] = float(opt["momentum"])
-    clip = (cfg.get("trainer") or {}).get("gradient_clip_val")
+    trainer = cfg.get("trainer") or {}
+    clip = trainer.get("gradient_clip_val")
     if clip is not None:
         args["gradient_clip_val"] = clip_value(clip)
+    k = trainer.get("accumulate_grad_batches")
+    if k is not None:
+        args["accumulate_grad_batches"] = accumulate_value(k)
     args.update(kw)
     return TrainStep(model, int(cfg["data_loader"]["batch_size"]), shape, **args)

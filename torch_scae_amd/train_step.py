@@ -13,7 +13,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .data_parallel import (FlatParameters, all_reduce_gradients,
+from .data_parallel import (FlatParameters, accumulate_value, all_reduce_gradients,
                             broadcast_parameters, clip_value, load_optimizer_state_dict,
                             make_optimizer, optimizer_state_dict, world)
 
@@ -27,6 +27,22 @@ REMAINDER_NOISE_SALT = 0x52454D41494E4452 & ((1 << 63) - 1)
 # model): the first all-reduce bucket
 EARLY_PREFIXES = ("obj_decoder.", "part_decoder.", "prior_classifier.",
                   "posterior_classifier.")
+
+# what a captured form of the step holds (TrainStep._use_form swaps them)
+FORM_ATTRS = ("graph", "graph_b", "_klist", "_launches", "graph_nodes", "loss")
+
+
+def update_batch(i, steps_in_epoch, k):
+    """Lightning's rule for accumulate_grad_batches = k: the optimiser steps after batch i
+    (0-based in the epoch) when (i + 1) % k == 0 or i is the epoch's last batch."""
+    return (i + 1) % k == 0 or i == steps_in_epoch - 1
+
+
+def update_at(view, batch, k):
+    """``update_batch`` for the step ``view.take_step(batch)`` hands out next (the view is not
+    advanced)."""
+    last = view.steps_in_epoch(batch)
+    return update_batch(view.cursor if view.cursor < last else 0, last, k)
 
 
 class TrainStep:
@@ -84,6 +100,18 @@ class TrainStep:
     the gradient's sum of squares, the step's last column sums riding in it); the optimiser
     pass reads the coefficient from its partials.  ``last_grad_norm()``: the last step's norm
     before clipping, a device scalar.
+
+    ``accumulate_grad_batches`` (k, an int >= 1): Lightning's ``Trainer(accumulate_grad_batches)``
+    -- the optimiser steps once per group of k batches, on the sum of their gradients scaled
+    by 1/k (the loss itself is not scaled: acc = g_1 + g_2 + ... in fp32, the 1/k rides in the
+    optimiser pass).  ``step_from`` / ``train_epoch`` step after batch i of the epoch when
+    (i + 1) % k == 0 or i is the epoch's last batch; ``step(image, label)`` counts groups, and
+    ``end_epoch()`` first steps on a group still pending.  A batch that does not end its group
+    ends in an accumulate pass instead of the optimiser (the column sums ride in it); the
+    group's last batch in the accumulate form of the optimiser pass.  Each is a captured form
+    of its own (captured on first use).  With a collective: no all-reduce until the group's
+    last batch, then one of the accumulated gradient.  ``steps`` counts batches,
+    ``optimizer_steps`` optimiser steps; k = 1 (the default) is the step as it was.
     """
 
     MODES = ("2 buckets", "1 bucket", "in graph")
@@ -95,12 +123,20 @@ class TrainStep:
                  prologue=True, fuse_kernels=True, collective_mode=None,
                  replay="graph", betas=(0.9, 0.999),
                  look_ahead=False, look_ahead_k=5, look_ahead_alpha=0.5,
-                 log_steps=0, gradient_clip_val=0.0):
+                 log_steps=0, gradient_clip_val=0.0, accumulate_grad_batches=1):
         if not isinstance(log_steps, int) or isinstance(log_steps, bool) or log_steps < 0:
             raise ValueError(f"log_steps must be an int >= 0, got {log_steps!r}")
         gradient_clip_val = clip_value(gradient_clip_val)
         if gradient_clip_val and optimizer in (None, False):
             raise ValueError("gradient_clip_val needs an optimizer: clipping is part of its step")
+        self.accumulate_grad_batches = accumulate_value(accumulate_grad_batches)
+        if self.accumulate_grad_batches > 1 and optimizer in (None, False):
+            raise ValueError("accumulate_grad_batches needs an optimizer: it steps once a group")
+        # batches accumulated since the last optimiser step, optimiser steps taken (one dict,
+        # shared with the remainder step)
+        self._acc_state = {"pending": 0, "optimizer_steps": 0}
+        self._form = "update"     # the captured form in the step's attributes (FORM_ATTRS)
+        self._other_form = None   # ... and the other one, once captured
         self._parent = None      # (a remainder step: the step whose state it shares)
         self._rem = None         # the cached remainder step (remainder_step)
         self.model = model
@@ -163,7 +199,8 @@ class TrainStep:
             optimizer, self.flat, lr=lr, eps=1e-2 / float(batch_size) ** 2,
             betas=betas, momentum=momentum, weight_decay=weight_decay,
             look_ahead=look_ahead, look_ahead_k=look_ahead_k,
-            look_ahead_alpha=look_ahead_alpha, gradient_clip_val=gradient_clip_val) \
+            look_ahead_alpha=look_ahead_alpha, gradient_clip_val=gradient_clip_val,
+            accumulate_grad_batches=self.accumulate_grad_batches) \
             if optimizer not in (None, False) else None
         self.steps = 0           # steps taken (host count, with the remainder step's; the
         #                          optimisers keep their own)
@@ -232,6 +269,38 @@ class TrainStep:
         else:
             self._parent.steps = value
 
+    @property
+    def optimizer_steps(self):
+        """Optimiser steps taken (== ``steps`` without accumulation)."""
+        return self._acc_state["optimizer_steps"]
+
+    # -- the two captured forms of an accumulating step -------------------------
+    def _tail_captured(self):
+        return self.use_graph and not self.split and \
+            (not self.collective or self.in_graph_collective)
+
+    def _use_form(self, form):
+        """Make ``form`` ("update": the optimiser ends the step; "acc": the accumulate pass)
+        the one the step's graph attributes hold, stashing the other (captured lazily)."""
+        if form == self._form:
+            return
+        if self._tail_captured():
+            keep = {k: getattr(self, k) for k in FORM_ATTRS}
+            other = self._other_form or dict(
+                {k: None for k in FORM_ATTRS}, loss=torch.zeros((), device=self.device))
+            for k, v in other.items():
+                setattr(self, k, v)
+            self._other_form = keep
+        self._form = form
+
+    def _drop_forms(self):
+        """Forget both captured forms (the next step captures again)."""
+        other, self._other_form = self._other_form, None
+        if other and other.get("_klist"):
+            from . import _lib
+            _lib.load().scae_launch_list_free(other["_klist"])
+        self.graph = self.graph_b = None
+
     # -- the remainder step ---------------------------------------------------
     def remainder_step(self, size):
         """The step that runs this step's batches of ``size`` (1 <= size < B): built on the
@@ -250,7 +319,8 @@ class TrainStep:
             self._rem = None
             rem = self._rem = self._remainder_of(size)
         if self._with_log and not rem._with_log:
-            rem._with_log, rem.graph, rem.graph_b = True, None, None
+            rem._with_log = True
+            rem._drop_forms()
         return rem
 
     def _remainder_of(self, size):
@@ -279,6 +349,7 @@ class TrainStep:
         rem._launches = rem._klist = rem.graph_nodes = None
         rem.graph = rem.graph_b = rem._cut = None
         rem._capturing = rem._warming = False
+        rem._form, rem._other_form = "update", None
         return rem
 
     def _for_batch(self, size):
@@ -405,16 +476,47 @@ class TrainStep:
                                     force=self.collective)
 
     def _finish(self):
+        k = self.accumulate_grad_batches
+        if k > 1:
+            self._finish_group()
+            return
         if self.collective:
             self._reduce()
         if self.opt is not None:
             self.opt.step(grad_scale=1.0 / self.world,
                           sum_units=self.plan.take_held_sums())
 
+    def _finish_group(self):
+        """The end of an accumulating step: the accumulate pass ("acc" form), or the
+        optimiser on the group's gradient -- with a collective, folded into the flat
+        gradient buffer and all-reduced first."""
+        if self._form == "acc":
+            self.opt.accumulate(sum_units=self.plan.take_held_sums())
+            return
+        scale = 1.0 / (self.accumulate_grad_batches * self.world)
+        if self.collective:
+            self.opt.fold()
+            self._reduce()
+            self.opt.step(grad_scale=scale, sum_units=self.plan.take_held_sums(),
+                          with_acc=False)
+        else:
+            self.opt.step(grad_scale=scale, sum_units=self.plan.take_held_sums())
+
+    def _after_buckets(self):
+        """What follows a split step's parts (their all-reduces included)."""
+        if self.accumulate_grad_batches > 1:
+            self._finish_group()
+        elif self.opt is not None:
+            self.opt.step(grad_scale=1.0 / self.world)
+
     def _run(self, part_a, part_b):
         """One step from its two parts (graph replays or eager calls)."""
         if not self.split:
             part_a()
+            return
+        if self.accumulate_grad_batches > 1:   # (one all-reduce after the backward: _finish_group)
+            part_a()
+            part_b()
             return
         part_a()
         w0 = self._reduce(0, async_op=True)     # overlaps part B
@@ -466,7 +568,11 @@ class TrainStep:
         self._capturing = True
         ok = False
         try:
-            with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode), \
+            # an accumulating step's second form shares the first one's memory pool: the two
+            # never replay at once, and each rewrites its temporaries before reading them
+            other = (self._other_form or {}).get("graph")
+            pool = dict(pool=other.pool()) if other is not None else {}
+            with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode, **pool), \
                     _lib.recorder() as launches:
                 self._part_a()
                 if not self.split:
@@ -556,6 +662,7 @@ class TrainStep:
     def __del__(self):
         try:
             self._free_list()
+            self._drop_forms()
         except Exception:      # (interpreter shutdown)
             pass
 
@@ -584,6 +691,8 @@ class TrainStep:
         parameters (folding products, filter re-layouts) is recomputed by
         every step's own prologue / graph."""
         snap = {"param": self.flat.flat_param.clone(), "steps": self.steps}
+        if self.accumulate_grad_batches > 1:
+            snap.update(acc=self.opt.acc.clone(), acc_state=dict(self._acc_state))
         if self.opt is not None:
             snap.update({k: b.clone() for k, b in self.opt.state_buffers()},
                         lr=self.opt.lr)
@@ -597,6 +706,9 @@ class TrainStep:
     def restore(self, snap):
         self.flat.flat_param.copy_(snap["param"])
         self.steps = snap.get("steps", self.steps)
+        if "acc" in snap:
+            self.opt.acc.copy_(snap["acc"])
+            self._acc_state.update(snap["acc_state"])
         if self.opt is not None:
             for k, b in self.opt.state_buffers():
                 b.copy_(snap[k])
@@ -616,16 +728,24 @@ class TrainStep:
         if self.opt is None:
             raise ValueError("this step has no optimiser")
         return optimizer_state_dict(self.opt, list(self.model.parameters()),
-                                    steps=self.steps)
+                                    steps=self.optimizer_steps
+                                    if self.accumulate_grad_batches > 1 else self.steps)
 
     def load_optimizer_state_dict(self, sd):
         """Load a ``torch.optim``-schema state (``optimizer_state_dict``, or a
         stock optimiser's over ``model.parameters()``); a captured graph
-        replays from it."""
+        replays from it.  ``steps`` and ``optimizer_steps`` become the state's step
+        count; accumulating, a group in progress is dropped (acc zeroed, nothing
+        pending)."""
         if self.opt is None:
             raise ValueError("this step has no optimiser")
         self.steps = load_optimizer_state_dict(
             self.opt, list(self.model.parameters()), sd)
+        # the state dict holds optimiser steps and no group in progress: a group pending
+        # here is dropped (acc cleared), and the batch count restarts at the step count
+        self._acc_state.update(pending=0, optimizer_steps=self.steps)
+        if self.opt.acc is not None:
+            self.opt.acc.zero_()
 
     def _refresh_prologue(self):
         """Noise + folding products for the next forward (no batch)."""
@@ -698,10 +818,12 @@ class TrainStep:
         if self.world > 1 and (view.rank, view.world) != world():
             raise ValueError(f"view of rank {view.rank} / world {view.world} in a step "
                              f"of rank {world()[0]} / world {self.world}")
+        update = update_at(view, B, self.accumulate_grad_batches) \
+            if self.accumulate_grad_batches > 1 else None
         at = view.take_step(B)
         step = self._for_batch(at.size)
         step._stage_source(view, *at)
-        return step._step_staged()
+        return step._step_staged(update)
 
     def train_epoch(self, view):
         """The view's remaining steps of its current epoch (``step_from``: the full ones,
@@ -722,16 +844,31 @@ class TrainStep:
         step._stage(image, label)
         return step._step_staged()
 
-    def _step_staged(self):
+    def _step_staged(self, update=None):
+        """``update``: whether this batch ends its group (accumulating; None: the host's
+        count of the group's batches decides)."""
+        k, acc = self.accumulate_grad_batches, self._acc_state
+        if k > 1:
+            if update is None:
+                update = acc["pending"] + 1 >= k
+            self._use_form("update" if update else "acc")
         self.steps += 1
         if self.train_log is not None:
             self.train_log.count += 1   # (the row this step writes)
+        self._step_form()
+        if k > 1 and not update:
+            acc["pending"] += 1
+        elif self.opt is not None:
+            acc["pending"] = 0
+            acc["optimizer_steps"] += 1
+        return self.loss
+
+    def _step_form(self):
         if self.use_graph:
             self.capture()
             if self.split:
                 self._run(self.graph.replay, self.graph_b.replay)
-                if self.opt is not None:
-                    self.opt.step(grad_scale=1.0 / self.world)
+                self._after_buckets()
             else:
                 if self.replay == "launches" and self._klist:
                     self.replay_launches()
@@ -741,12 +878,10 @@ class TrainStep:
                     self._finish()
         elif self.split:
             self._run(self._part_a, self._part_b)
-            if self.opt is not None:
-                self.opt.step(grad_scale=1.0 / self.world)
+            self._after_buckets()
         else:
             self._fwd_bwd()
             self._finish()
-        return self.loss
 
     def training_step(self, image, label):
         """-> {'loss': tensor, 'log': {...}} like BaseExperiment.training_step
@@ -754,7 +889,8 @@ class TrainStep:
         the next call overwrites.  Builds the step with the log outputs on
         first use (costs a few extra small kernels per step)."""
         if not self._with_log:
-            self._with_log, self.graph, self.graph_b = True, None, None
+            self._with_log = True
+            self._drop_forms()
         step = self._for_batch(image.shape[0])
         loss = step(image, label)
         return dict(loss=loss, log=step.log)
@@ -815,6 +951,20 @@ class TrainStep:
         self._need_log().reset()
 
     def end_epoch(self):
-        """Per-epoch ExponentialLR step (base_experiment.py:73-76)."""
+        """Per-epoch ExponentialLR step (base_experiment.py:73-76); accumulating, a group
+        still pending (``step(image, label)`` batches short of k) first steps the optimiser
+        on what it has: one eager pass over acc alone."""
+        acc = self._acc_state
+        if self.accumulate_grad_batches > 1 and acc["pending"]:
+            scale = 1.0 / (self.accumulate_grad_batches * self.world)
+            if self.collective:
+                self.flat.flat_grad.zero_()
+                self.opt.fold()
+                self._reduce()
+                self.opt.step(grad_scale=scale, with_acc=False)
+            else:
+                self.opt.flush(scale)
+            acc["pending"] = 0
+            acc["optimizer_steps"] += 1
         if self.opt is not None and self.lr_decay_rate:
             self.opt.decay_lr(self.lr_decay_rate)
