@@ -23,6 +23,12 @@ ACC_KEYS = {"loss": 1, "accuracy": 2, "prior_accuracy": 3, "posterior_accuracy":
             "cpr_dynamic_reg_loss": 16}
 ACC_DOUBLES = 17
 
+# the evaluation steps' noise generators: keyed by torch's seed XOR these (step_plan.StepPlan.
+# noise_salt).  Unsalted, validation batch i would draw the (seed, launch i) stream training
+# step i draws, and evaluate()'s tail batch the stream of one of its full batches.
+EVAL_NOISE_SALT = 0x4556414C53544550 & ((1 << 63) - 1)
+EVAL_TAIL_NOISE_SALT = 0x4556414C5441494C & ((1 << 63) - 1)
+
 
 def means(sums):
     """{key: fp32 mean} of an accumulator (fp64, any device): sum / number of batches --
@@ -87,9 +93,11 @@ class EvalStep:
     The step runs its warm-ups, capture and eager calls with ``model.eval()`` (the part
     encoder draws no noise; the object decoder's uniform noise comes from the step's own
     device generator) and restores ``model.training``.  It has its own plan, prologue and
-    noise generator and writes no gradients and no optimiser state.  Parameters re-homed
-    after the capture (a ``TrainStep`` built later moves them into flat buffers) are
-    detected by a pointer check and the step recaptures; in-place updates need nothing.
+    noise generator (salted: its draws are neither a training step's nor, for ``evaluate()``'s
+    tail step, the full batches') and writes no gradients and no optimiser state.
+    Parameters re-homed after the capture (a ``TrainStep`` built later moves them into flat
+    buffers) are detected by a pointer check and the step recaptures; in-place updates need
+    nothing.
     With a process group of world > 1 ``*_epoch_end`` / ``epoch_means`` sum the
     accumulators of all ranks first (data_parallel.all_reduce_sums).
 
@@ -126,6 +134,7 @@ class EvalStep:
         self._pro = ops.StepPrologue() if prologue and self.cuda else None
         # this step's plan: its prologue, parked launches and noise generator
         self.plan = ops.StepPlan("eval step", prologue=self._pro)
+        self.plan.noise_salt = EVAL_NOISE_SALT
         self.epi = ops.EvalEpilogue(self.device) if self.cuda else None
         self.acc = self.epi.acc if self.cuda else \
             torch.zeros(ACC_DOUBLES, dtype=torch.float64)
@@ -438,6 +447,7 @@ class EvalStep:
                 replay=self.replay, autocast_dtype=self.autocast_dtype,
                 lazy_render=self.lazy_render, prologue=self.prologue,
                 fuse_kernels=self.fuse_kernels)
+            tail.plan.noise_salt = EVAL_TAIL_NOISE_SALT     # (before its first draw)
         tail.reset()
         return tail
 

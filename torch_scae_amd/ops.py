@@ -276,7 +276,12 @@ def uniform(n, ref):
     generator (csrc/noise.hip).  Seeded from ``torch.initial_seed()``; the
     generator state is per (device, stream) and restarts when that seed
     changes (``torch.manual_seed``) outside a graph capture; the plan's
-    ``noise_salt`` is XORed into the seed."""
+    ``noise_salt`` is XORed into the seed (0 for a training step and for ops
+    outside any step; a remainder step, an evaluation step and its tail step
+    have a salt each, so no two of them draw one (seed, launch) stream).
+    Launch L of seed s writes, for group g of four floats, the 24 high bits of
+    each word of Philox4x32-10((g, g >> 32, L, L >> 32), (s, s >> 32)) scaled
+    by 2^-24 (tests/philox_ref.py)."""
     _need_hip(ref)
     plan = _plan()
     seed = (int(torch.initial_seed()) ^ plan.noise_salt) & ((1 << 63) - 1)
