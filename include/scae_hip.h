@@ -1499,6 +1499,34 @@ int scae_gmm_mode_f32(const float *loc, const float *mixing_logits,
                       const float *sigma, float *out, int maximum, int B,
                       int K, int C, int Cm, int64_t P, void *stream);
 
+/* distributions.py:37-39 (mean) / :50-77 (mode) of the mixture part_decoder.py:174-237 builds,
+ * from the compact inputs: no (B,K,C,H,W) tensor exists.  Images [first, first + count) of
+ * d->B only (the grid is sized by count).  out: (count, C, H, W) dense.  what: 0 = mode,
+ * 1 = mean.  The bits are those of the materialising entry point followed by the generic
+ * mode / mean over its tensors: each component's value and mixing logit in the arithmetic of
+ * the render form that entry point takes for d, the first largest logit wins (mode), two-pass
+ * softmax in component order (mean).  Every shape the descriptor check accepts is served: the
+ * image's template planes are staged in LDS whole, or in chunks of templates (one template's
+ * padded planes are at most 5 x SCAE_RENDER_MAX_TEMPLATE_ELEMS floats plus their corners,
+ * 82 KB, for a one-texel-wide template: inside a CU's LDS). */
+int scae_render_gmm_mode_f32(const scae_decoder_desc *d, float *out, int what, int first,
+                             int count, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Image sheets (csrc/image_sheet.hip): up to 4 sources (n[i], C, H, W), taken as one batch of
+ * N = sum n[i] images in source order, laid into sheet (3, Hs, Ws) in one launch.
+ *   N > 1: xmaps = min(nrow, N) images per row, ymaps = ceil(N / xmaps) rows, cells of
+ *     (H + padding, W + padding); Hs = ymaps (H + padding) + padding, Ws = xmaps (W + padding)
+ *     + padding; image k at row (k / xmaps)(H + padding) + padding, column
+ *     (k % xmaps)(W + padding) + padding; everything else, cells beyond N included, is
+ *     pad_value.
+ *   N = 1: the image itself, Hs = H, Ws = W.
+ *   C = 1 is repeated to the 3 channels, C = 3 copied; any other C is rejected.
+ * src and n are host arrays of nsrc entries.
+ * ------------------------------------------------------------------------ */
+int scae_image_sheet_f32(int nsrc, const float *const *src, const int *n, int C, int H, int W,
+                         int nrow, int padding, float pad_value, float *sheet, void *stream);
+
 /* ------------------------------------------------------------------------
  * k-means (csrc/kmeans.hip): Lloyd iterations of n_init restarts in one grid, no float atomics.
  *   distance sum_f (x_f - c_f)^2 in f order, ties to the lowest cluster; update the mean of the

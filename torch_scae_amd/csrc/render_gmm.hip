@@ -97,12 +97,6 @@ __device__ __forceinline__ void tap_value_grad(const float *plane, const Taps &t
   dy = (v10 - v00) * wx0 + (v11 - v01) * wx1;
 }
 
-struct PTaps {
-  int base;      // offset of tap (y0, x0) inside a padded plane
-  float fx, fy;  // fractional position
-  float xn, yn;  // normalised output-pixel coordinates
-};
-
 __device__ __forceinline__ void make_ptaps(const float *a, int p, int W, int H, int tw, int th,
                                            PTaps &t) {
   const float inv_w = 1.f / (float)W;
@@ -134,35 +128,6 @@ __device__ __forceinline__ void ptap_value_grad(const float *plane, const PTaps 
   v = v00 * (wx0 * wy0) + v01 * (wx1 * wy0) + v10 * (wx0 * wy1) + v11 * (wx1 * wy1);
   dx = (v01 - v00) * wy0 + (v11 - v10) * wy1;
   dy = (v10 - v00) * wx0 + (v11 - v01) * wx1;
-}
-
-// stage `n` dense (th x tw) planes from global memory as padded planes (NTHREADS
-// threads of the workgroup; the caller synchronises afterwards)
-template <int NTHREADS>
-__device__ __forceinline__ void stage_padded(float *dst, const float *src, int n, int th, int tw) {
-  const int psz = pad_elems(th, tw), pw = pad_w(tw);
-  // zero everything (16-byte stores where dst allows), then one thread per texel
-  // row: a single division per row
-  const int total = n * psz, n4 = (((size_t)dst & 15) == 0) ? total >> 2 : 0;
-  for (int i = threadIdx.x; i < n4; i += NTHREADS)
-    reinterpret_cast<float4 *>(dst)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int i = 4 * n4 + threadIdx.x; i < total; i += NTHREADS) dst[i] = 0.f;
-  __syncthreads();
-  if (!src) return;
-  if (n * th >= NTHREADS) {  // many planes: a thread per texel row (one division per row)
-    for (int row = threadIdx.x; row < n * th; row += NTHREADS) {
-      const int pl = row / th, y = row - pl * th;
-      const float *sp = src + (size_t)row * tw;
-      float *dp = dst + pl * psz + (y + 2) * pw + 2;
-      for (int x = 0; x < tw; ++x) dp[x] = sp[x];
-    }
-  } else {  // few planes: a thread per texel
-    const int tsz = th * tw;
-    for (int i = threadIdx.x; i < n * tsz; i += NTHREADS) {
-      const int pl = i / tsz, e = i - pl * tsz, y = e / tw, x = e - y * tw;
-      dst[pl * psz + (y + 2) * pw + x + 2] = src[i];
-    }
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1123,18 +1088,11 @@ int check_desc(const scae_decoder_desc *d) {
   return SCAE_OK;
 }
 
-template <typename KernelT>
-int set_lds(KernelT kernel, size_t bytes) {
-  if (bytes > 160 * 1024) return SCAE_ERR_UNSUPPORTED;
-  if (bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  return SCAE_OK;
-}
-
 }  // namespace
+
+namespace scae_k1 {
+int check_decoder_desc(const scae_decoder_desc *d) { return check_desc(d); }
+}  // namespace scae_k1
 
 extern "C" int scae_template_render_fwd_f32(const scae_decoder_desc *d,
                                             float *transformed_templates,

@@ -28,6 +28,42 @@ __device__ __forceinline__ void tex_pos(const float *a, float xn, float yn, int 
 __host__ __device__ inline int pad_w(int tw) { return tw + 4; }
 __host__ __device__ inline int pad_elems(int th, int tw) { return (th + 4) * (tw + 4); }
 
+// taps of one sampling position inside a padded plane
+struct PTaps {
+  int base;      // offset of tap (y0, x0) inside a padded plane
+  float fx, fy;  // fractional position
+  float xn, yn;  // normalised output-pixel coordinates
+};
+
+// stage `n` dense (th x tw) planes from global memory as padded planes (NTHREADS
+// threads of the workgroup; the caller synchronises afterwards)
+template <int NTHREADS>
+__device__ __forceinline__ void stage_padded(float *dst, const float *src, int n, int th, int tw) {
+  const int psz = pad_elems(th, tw), pw = pad_w(tw);
+  // zero everything (16-byte stores where dst allows), then one thread per texel
+  // row: a single division per row
+  const int total = n * psz, n4 = (((size_t)dst & 15) == 0) ? total >> 2 : 0;
+  for (int i = threadIdx.x; i < n4; i += NTHREADS)
+    reinterpret_cast<float4 *>(dst)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int i = 4 * n4 + threadIdx.x; i < total; i += NTHREADS) dst[i] = 0.f;
+  __syncthreads();
+  if (!src) return;
+  if (n * th >= NTHREADS) {  // many planes: a thread per texel row (one division per row)
+    for (int row = threadIdx.x; row < n * th; row += NTHREADS) {
+      const int pl = row / th, y = row - pl * th;
+      const float *sp = src + (size_t)row * tw;
+      float *dp = dst + pl * psz + (y + 2) * pw + 2;
+      for (int x = 0; x < tw; ++x) dp[x] = sp[x];
+    }
+  } else {  // few planes: a thread per texel
+    const int tsz = th * tw;
+    for (int i = threadIdx.x; i < n * tsz; i += NTHREADS) {
+      const int pl = i / tsz, e = i - pl * tsz, y = e / tw, x = e - y * tw;
+      dst[pl * psz + (y + 2) * pw + x + 2] = src[i];
+    }
+  }
+}
+
 // template set of image b: consecutive groups of `template_repeat` images share one
 // (stacked_capsule_auto_encoder.py:188-195 decodes every object capsule's votes with the
 // image's templates: B*O virtual images, B template sets)
@@ -54,6 +90,21 @@ __device__ __forceinline__ Scalars load_scalars(const scae_decoder_desc &d) {
   return s;
 }
 
+
+// dynamic LDS of a K1 kernel: refused beyond a CU's 160 KB, opted in beyond 48 KB
+template <typename KernelT>
+int set_lds(KernelT kernel, size_t bytes) {
+  if (bytes > 160 * 1024) return SCAE_ERR_UNSUPPORTED;
+  if (bytes > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return (int)e;
+  }
+  return SCAE_OK;
+}
+
+// render_gmm.hip: the argument check every K1 entry point starts with
+int check_decoder_desc(const scae_decoder_desc *d);
 
 // Pixel tiling of the fused likelihood forward (and of the per-tile log-prob sums it
 // hands to the loss tail): `tiles` workgroups per image of `ppb` consecutive pixels each.

@@ -6,7 +6,9 @@ Two flavours share the reference's class name and methods:
     the generic one-lane-per-pixel mixture kernels;
   * built by ``TemplateBasedImageDecoder`` -> additionally carries the compact
     decoder inputs, and ``log_prob`` takes the fused render+mixture kernel
-    (K1) that never reads the (B,K,C,H,W) tensors back from HBM.
+    (K1) that never reads the (B,K,C,H,W) tensors back from HBM; while those
+    tensors are still unrendered (``lazy_render``) and no gradient is wanted,
+    ``mode`` / ``mean`` come from the compact inputs too.
 """
 import math
 
@@ -71,8 +73,26 @@ class GaussianMixture:
         """distributions.py:34-35."""
         return torch.log_softmax(self.mixing_logits, 1)
 
+    def _fused_image(self):
+        """True when ``mode()`` / ``mean()`` may come from the fused
+        render-and-mode kernel: the mixture was built by the image decoder, its
+        rendered tensors have not been made yet (there is nothing to reuse and
+        the call leaves them unmade), and no gradient can be asked of the
+        result -- the fused kernel is forward only."""
+        inputs = self._decoder_inputs
+        if inputs is None or not callable(self._mixing_logits) or \
+                not callable(getattr(self.dist, "_loc", None)):
+            return False
+        rendered = getattr(self, "_rendered", None)
+        if rendered is not None and rendered.out is not None:
+            return False
+        return not (torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in inputs.tensors()))
+
     def mean(self):
         """distributions.py:37-39."""
+        if self._fused_image():
+            return ops.render_gmm_mode(self._decoder_inputs, mean=True)
         return ops.gmm_mean(self._loc5(), self._ml5()).view(self._out_shape())
 
     def log_prob(self, x):
@@ -116,6 +136,26 @@ class GaussianMixture:
             soft = torch.softmax(mlp, 1)
             mask = (hard - soft).detach() + soft
             return torch.sum(mask * loc, 1)
+        if self._fused_image():
+            inputs = self._decoder_inputs
+            if maximum and inputs.templates_alpha is not None and \
+                    inputs.templates.shape[2] > 1:
+                # one logit channel for C > 1: the reference's in-place add
+                # cannot broadcast (distributions.py:65), as in ops.gmm_mode
+                K, (H, W) = inputs.templates.shape[1] + 1, inputs.output_size
+                B, C = inputs.pose.shape[0], inputs.templates.shape[2]
+                raise RuntimeError(f"output with shape {[B, K, 1, H, W]} "
+                                   f"doesn't match the broadcast shape "
+                                   f"{[B, K, C, H, W]}")
+            scale = self.dist.scale
+            if maximum and torch.is_tensor(scale) and scale.numel() != 1:
+                # what the materialising route's _sigma() refuses (a non-tensor
+                # scale is one number; asking _sigma() for it would render)
+                raise ops.ScaeHipError("GaussianMixture kernels take one scalar "
+                                       "scale shared by all components")
+            # (``maximum`` adds the density of every component at its own mean:
+            # one constant under the shared scalar scale, the winner stays)
+            return ops.render_gmm_mode(inputs)
         return ops.gmm_mode(self._loc5(), self._ml5(), self._sigma(),
                             maximum).view(self._out_shape())
 

@@ -391,6 +391,59 @@ class EvalStep:
         with self._eval_mode():
             return self.model(self.image.clone())
 
+    def validation_images(self, result=None, n=8):
+        """The three image sheets validation_epoch_end logs (base_experiment.py:152-182),
+        each a (3, Hs, Ws) fp32 device tensor for ``add_image``:
+
+        'recons': rows of the first ``min(batch_size, n)`` images -- the input, the mode of
+          ``rec`` and, on a model built with ``reconstruct_alternatives``, of ``bottom_up_rec``
+          and ``top_down_rec``;
+        'templates': the M templates of image 0, ``int(sqrt(M))`` per row;
+        'transformed_templates': the M + 1 rendered components of image 0, same layout.
+
+        ``result``: a forward result of the staged batch (``validation_step(...,
+        batch_idx=0)['result']``); default: one eager forward of the staged batch.  The modes
+        come from the fused render-and-mode kernel for the ``n`` images alone and the one
+        image's components from a descriptor of that image: nothing of the size of the batch's
+        (B, M+1, C, H, W) tensors is made, and ``result`` stays unrendered.  Neither the
+        accumulator nor the captured step is touched.
+
+        The one-image render picks its kernel form from its own descriptor (B = 1).  Where
+        the batch's render cannot take the quad-store form (its LDS bound: three-channel
+        templates at B >= 512), 'transformed_templates' can differ in the last bit from
+        ``result.transformed_templates[0]``; the other two sheets do not depend on B."""
+        if not self.cuda:
+            raise ops.ScaeHipError("validation_images runs on the library's kernels: the "
+                                   "model is on the CPU")
+        if not isinstance(n, int) or isinstance(n, bool) or n <= 0:
+            raise ValueError(f"n must be a positive int, got {n!r}")
+        res = self._eager_result() if result is None else result
+        n = min(self.batch_size, n)
+        with torch.no_grad():
+            # (the reference's validation_step stores the batch as result.image)
+            image = dict.get(res, "image")
+            rows = [(self.image if image is None else image)[:n]]
+            recs = [res["rec"]]
+            if getattr(self.model, "reconstruct_alternatives", False):
+                recs += [res["bottom_up_rec"], res["top_down_rec"]]
+            for rec in recs:
+                inputs = rec.pdf._decoder_inputs
+                rows.append(ops.render_gmm_mode(inputs, first=0, count=n))
+            sheets = {"recons": ops.image_sheet(rows, nrow=n, padding=1, pad_value=0.0)}
+            templates = res["templates"][0].detach()
+            nrow = int(templates.shape[0] ** 0.5)
+            sheets["templates"] = ops.image_sheet([templates], nrow=nrow, padding=1,
+                                                  pad_value=0.0)
+            inputs = res["rec"].pdf._decoder_inputs
+            one = ops.DecoderInputs(inputs.output_size, **{
+                f: (getattr(inputs, f)[:1] if f in ("templates", "pose", "presence", "bg_image")
+                    and getattr(inputs, f) is not None else getattr(inputs, f))
+                for f in ops.DecoderInputs.FIELDS})
+            components = ops.render_templates(one)[0][0]
+            sheets["transformed_templates"] = ops.image_sheet([components], nrow=nrow,
+                                                              padding=1, pad_value=0.0)
+        return sheets
+
     def validation_step(self, image, label, batch_idx=None):
         """-> {'val_loss', 'accuracy'} as device tensors the next call overwrites
         (base_experiment.py:128-143); with ``batch_idx == 0`` also 'result'."""

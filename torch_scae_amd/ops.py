@@ -19,7 +19,7 @@ from .step_plan import StepPlan, current as _plan
 __all__ = ["geometric_transform", "qkv_attention", "set_encoder", "grouped_mlp", "seed_attention", "seed_attention_supported", "seed_fold", "seed_fold_supported", "loss_tail", "loss_tail_scalar", "loss_tail_supported", "capsule_votes",
            "capsule_likelihood", "colored_templates", "template_color_supported", "attention_conv_pool", "attention_pool_supported", "capsule_head", "part_encoder", "conv_stack", "conv_stack_supported",
            "uniform", "reset_noise", "pack_params", "render_templates", "render_gmm_log_prob", "render_gmm_log_prob_sums",
-           "gmm_log_prob", "gmm_mean", "gmm_mode", "ScaeHipError"]
+           "gmm_log_prob", "gmm_mean", "gmm_mode", "render_gmm_mode", "image_sheet", "ScaeHipError"]
 
 
 def _need_hip(*tensors):
@@ -3456,6 +3456,79 @@ def render_gmm_log_prob(inputs: DecoderInputs, x):
         raise ScaeHipError("fused log_prob does not differentiate w.r.t. its "
                            "target; use the materialised mixture for that")
     return _RenderGmmLogProb.apply(inputs.output_size, x, *inputs.tensors())
+
+
+def render_gmm_mode(inputs: DecoderInputs, mean=False, first=0, count=None):
+    """``mode()`` (or ``mean()``) of the decoder's mixture straight from its
+    compact inputs, for images [first, first + count) -> (count, C, H, W): the
+    bits of ``gmm_mode(*render_templates(inputs), ...)`` without the two
+    (B, M+1, ., H, W) tensors.  Forward only: nothing here is differentiable."""
+    t = _prep_decoder(inputs.tensors())
+    d, (B, M, C, th, tw, H, W) = _make_desc(t, inputs.output_size)
+    count = B - first if count is None else count
+    if not (isinstance(first, int) and isinstance(count, int)
+            and 0 <= first and count > 0 and first + count <= B):
+        raise ValueError(f"images [{first}, {first}+{count}) are not a slice of "
+                         f"the {B} this decoder call holds")
+    out = torch.empty(count, C, H, W, device=t[0].device, dtype=t[0].dtype)
+    _lib.call("scae_render_gmm_mode_f32", ctypes.byref(d), _p(out),
+              1 if mean else 0, first, count, _stream(t[0]))
+    return out
+
+
+# ----------------------------------------------------------------------------
+# image sheets (what validation_epoch_end logs, base_experiment.py:152-182)
+# ----------------------------------------------------------------------------
+def image_sheet_shape(N, H, W, nrow, padding):
+    """(xmaps, ymaps, Hs, Ws) of a sheet of N (., H, W) images."""
+    xmaps = min(nrow, N)
+    ymaps = -(-N // xmaps)
+    if N == 1:
+        return xmaps, ymaps, H, W
+    return (xmaps, ymaps, ymaps * (H + padding) + padding,
+            xmaps * (W + padding) + padding)
+
+
+def image_sheet(sources, nrow, padding=1, pad_value=0.0):
+    """1 to 4 tensors (N_i, C, H, W), C in {1, 3}, taken as one batch of
+    N = sum N_i images in order, laid ``nrow`` per row into a (3, Hs, Ws) fp32
+    sheet with ``padding`` pixels of ``pad_value`` around every image (a single
+    image is returned as it is; one channel is repeated to three).  Device
+    tensors take one launch of the sheet kernel; CPU tensors the same layout in
+    torch ops."""
+    sources = [sources] if torch.is_tensor(sources) else list(sources)
+    if not 1 <= len(sources) <= 4:
+        raise ValueError("an image sheet takes 1 to 4 source tensors")
+    if not (isinstance(nrow, int) and nrow > 0 and isinstance(padding, int)
+            and padding >= 0):
+        raise ValueError("nrow must be a positive int, padding a non-negative one")
+    if any(s.dim() != 4 or s.shape[0] == 0 for s in sources):
+        raise ValueError("every source must be a non-empty (N, C, H, W) tensor")
+    C, H, W = sources[0].shape[1:]
+    if C not in (1, 3):
+        raise ValueError(f"images of 1 or 3 channels expected, got {C}")
+    if any(tuple(s.shape[1:]) != (C, H, W) or s.device != sources[0].device
+           or s.dtype != torch.float32 for s in sources):
+        raise ValueError("the sources must share (C, H, W), device and fp32")
+    N = sum(s.shape[0] for s in sources)
+    xmaps, ymaps, Hs, Ws = image_sheet_shape(N, H, W, nrow, padding)
+    if not sources[0].is_cuda:
+        t = torch.cat(sources, 0).expand(N, 3, H, W)
+        if N == 1:
+            return t[0].clone()
+        sheet = torch.full((3, Hs, Ws), float(pad_value), dtype=torch.float32)
+        for k in range(N):
+            y = (k // xmaps) * (H + padding) + padding
+            x = (k % xmaps) * (W + padding) + padding
+            sheet[:, y:y + H, x:x + W] = t[k]
+        return sheet
+    sources = [_c(s.detach()) for s in sources]
+    sheet = torch.empty(3, Hs, Ws, device=sources[0].device, dtype=torch.float32)
+    ptrs = (ctypes.c_void_p * len(sources))(*[s.data_ptr() for s in sources])
+    counts = (ctypes.c_int * len(sources))(*[s.shape[0] for s in sources])
+    _lib.call("scae_image_sheet_f32", len(sources), ptrs, counts, C, H, W, nrow,
+              padding, float(pad_value), _p(sheet), _stream(sheet))
+    return sheet
 
 
 # ----------------------------------------------------------------------------

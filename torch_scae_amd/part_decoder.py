@@ -164,9 +164,11 @@ class TemplateBasedImageDecoder(nn.Module):
                 dict.__setitem__(d, "mixing_logits", rendered.get(1))
                 d["_lazy"].clear()
 
-            out = LazyAttrDict(pdf=GaussianMixture(
+            pdf = GaussianMixture(
                 _NormalView(lambda: rendered.get(0), scale),
-                lambda: rendered.get(1), _decoder_inputs=inputs))
+                lambda: rendered.get(1), _decoder_inputs=inputs)
+            pdf._rendered = rendered    # (mode() / mean() ask: made yet?)
+            out = LazyAttrDict(pdf=pdf)
             out["_lazy"] = dict(transformed_templates=fill, mixing_logits=fill)
             return out
         transformed_templates, mixing_logits = ops.render_templates(inputs)
