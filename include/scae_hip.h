@@ -1212,6 +1212,41 @@ typedef struct scae_eval_sink {
   int64_t cursor;
   int64_t overflow;
 } scae_eval_sink;
+/* The evaluation records: DEVICE memory that a captured launch reaches by its address, like
+ * the feature sink.  Batch rows [cursor, cursor + B) of a (capacity, SCAE_EVAL_RECORD_FLOATS)
+ * fp32 matrix receive one record per image, written by the batch's last launch:
+ *   [0] label as a float (-1 without labels)
+ *   [1] prior-head class  [2] posterior-head class: argmax over the head's class probabilities
+ *       as torch.argmax takes it (first maximal index, NaN maximal), the rule of the accuracies
+ *   [3] [4] the two heads' probability of their own predicted class
+ *   [5] [6] the two heads' probability of the label's class (0 without labels, or for a label
+ *       outside [0, ncls))
+ *   [7] the image's reconstruction log-likelihood, rec_ll_per_pixel.view(B, -1).sum(-1)[b]: its
+ *       tile sums added in tile order (or, from a per-pixel map, one wave's strided sum)
+ *   [8] the image's capsule log-likelihood sum_m lpp[b, m], summed as the loss tail sums it.
+ * Without class probabilities (ncls = 0) entries [1..6] are -1, -1, 0, 0, 0, 0.
+ * confusion is a (2, ncls, ncls) int64 matrix indexed [head, label, predicted], head 0 the
+ * prior and head 1 the posterior: the batch's two histograms are built on chip and added by
+ * ONE workgroup in stream order, one writer per cell and no global atomics, so repeated runs
+ * give the same counts.  Images without a label, or with one outside [0, ncls), are not
+ * counted.  ncls here must equal the launch's ncls, or nothing is counted.
+ * labelled 0: the labels the launches carry are placeholders (a step always stages some) --
+ * the rows are written as without labels and nothing is counted.
+ * A row at or beyond capacity is dropped, is not counted either (confusion is always the
+ * histogram of the rows written) and sets overflow; cursor advances by B after everything
+ * else (ONE thread, in stream order).  capacity 0: the records are off -- nothing is written
+ * and the cursor stays. */
+#define SCAE_EVAL_RECORD_FLOATS 9
+#define SCAE_EVAL_RECORDS_MAX_CLASSES 64
+typedef struct scae_eval_records {
+  float *rows;
+  int64_t capacity;
+  int64_t cursor;
+  int64_t overflow;
+  int64_t *confusion;
+  int64_t ncls;
+  int64_t labelled;
+} scae_eval_records;
 #define SCAE_TRAIN_LOG_ROW 19
 typedef struct scae_train_log_desc {
   float *rows;      /* (capacity, SCAE_TRAIN_LOG_ROW) ring */
@@ -1329,6 +1364,31 @@ int scae_eval_tail_sink_f32(const float *lpp, const float *posterior, const floa
                             int post_type, int sparsity_on, const float *weights5,
                             float within_const, const float *prior_prob, const float *post_prob,
                             double *acc, float *batch3, scae_eval_sink *sink, void *stream);
+/* The same, also writing the batch's evaluation records (scae_eval_records, nullable like the
+ * sink): the combine workgroup, which reads every image's class probabilities, tile sums
+ * (extras->rec_sums as (B, n_rec / B); column [7] is zero without them) and per-image
+ * workspace entry, writes the rows and the confusion counts before the combine and advances
+ * the records' cursor last.  out12, acc and batch3 get the bits scae_eval_tail_sink_f32 gives.
+ * At most SCAE_EVAL_RECORDS_MAX_CLASSES classes (the tail itself takes 32). */
+int scae_eval_tail_records_f32(const float *lpp, const float *posterior,
+                               const float *caps_presence, const float *cls_w,
+                               const float *cls_b, const int64_t *label,
+                               const scae_loss_extras *extras, float *out12, float *workspace,
+                               int B, int O, int M, int ncls, int n_classes_cfg, int prior_type,
+                               int post_type, int sparsity_on, const float *weights5,
+                               float within_const, const float *prior_prob,
+                               const float *post_prob, double *acc, float *batch3,
+                               scae_eval_sink *sink, scae_eval_records *records, void *stream);
+/* The records of one batch and the cursor's advance as a launch of its own, for a model outside
+ * the fused tail.  prior_prob / post_prob (B, ncls) nullable together (ncls = 0), label (B)
+ * nullable, lpp (B, M) nullable (column [8] zero).  The reconstruction term comes from
+ * rec_sums (B, n_rec), added in tile order, or else from rec_pixels (B, n_rec), a per-pixel
+ * log-likelihood map that one wave per image sums; both NULL: column [7] zero.  One
+ * workgroup.  SCAE_ERR_UNSUPPORTED beyond SCAE_EVAL_RECORDS_MAX_CLASSES classes. */
+int scae_eval_records_f32(const float *prior_prob, const float *post_prob, const int64_t *label,
+                          const float *lpp, const float *rec_sums, const float *rec_pixels,
+                          int B, int ncls, int M, int n_rec, scae_eval_records *records,
+                          void *stream);
 /* Accuracies + accumulation only, for a loss other launches computed (a model outside the
  * fused tail: recon_mse_weight > 0, part_caps_sparsity_weight > 0, more than 32 classes):
  * loss (1), out12 (12, nullable), prior_prob / post_prob (B, ncls) and label (nullable

@@ -359,6 +359,9 @@ SIGNATURES = {
     + [POINTER(ScaledSum), c_int, P, P],
     "scae_eval_tail_sink_f32": [P] * 6 + [POINTER(LossExtras), P, P] + [c_int] * 8
     + [POINTER(c_float), c_float] + [P] * 6,
+    "scae_eval_tail_records_f32": [P] * 6 + [POINTER(LossExtras), P, P] + [c_int] * 8
+    + [POINTER(c_float), c_float] + [P] * 7,
+    "scae_eval_records_f32": [P] * 6 + [c_int] * 4 + [P, P],
     "scae_eval_accumulate_f32": [P] * 5 + [c_int] * 2 + [P] * 3,
     "scae_train_log_f32": [P] * 3 + [POINTER(TrainLogDesc), c_int, P],
     "scae_eval_features_f32": [P, P, c_int, c_int, c_int, P, P],
@@ -392,6 +395,10 @@ EVAL_ACC_DOUBLES = 17        # SCAE_EVAL_ACC_DOUBLES: the accumulator of scae_ev
 TRAIN_LOG_ROW = 19           # SCAE_TRAIN_LOG_ROW: one row of scae_train_log_desc's ring
 KMEANS_STATE_INTS = 4        # SCAE_KMEANS_STATE_INTS: per restart of scae_kmeans_desc's state
 EVAL_SINK_INT64S = 4         # struct scae_eval_sink: rows, capacity, cursor, overflow
+# struct scae_eval_records: rows, capacity, cursor, overflow, confusion, ncls, labelled
+EVAL_RECORDS_INT64S = 7
+EVAL_RECORD_FLOATS = 9       # SCAE_EVAL_RECORD_FLOATS: one row of scae_eval_records
+EVAL_RECORDS_MAX_CLASSES = 64   # SCAE_EVAL_RECORDS_MAX_CLASSES
 FLAT_OPT_STATE_INTS = 2112   # SCAE_FLAT_OPT_STATE_INTS: the step_state of scae_flat_opt_*
 GRAD_SQ_MAX_PARTIALS = 4096  # SCAE_GRAD_SQ_MAX_PARTIALS: scae_grad_sq_partials_*
 ABI_VERSION = 3     # SCAE_ABI_VERSION of the include/scae_hip.h this binding mirrors

@@ -29,6 +29,12 @@ ACC_DOUBLES = 17
 EVAL_NOISE_SALT = 0x4556414C53544550 & ((1 << 63) - 1)
 EVAL_TAIL_NOISE_SALT = 0x4556414C5441494C & ((1 << 63) - 1)
 
+# one row of predict()'s records (include/scae_hip.h, SCAE_EVAL_RECORD_FLOATS)
+RECORD_FLOATS = 9
+RECORD_COLUMNS = {"label": 0, "prior_class": 1, "posterior_class": 2, "prior_conf": 3,
+                  "posterior_conf": 4, "prior_label_prob": 5, "posterior_label_prob": 6,
+                  "rec_ll": 7, "log_prob": 8}
+
 
 def means(sums):
     """{key: fp32 mean} of an accumulator (fp64, any device): sum / number of batches --
@@ -56,6 +62,67 @@ def out12_from_log(loss, log):
                         get("posterior_between_sparsity_loss"), get("prior_cls_xe"),
                         get("posterior_cls_xe"), -rec_loss, rec_loss, lp_loss,
                         get("cpr_dynamic_reg_loss")])
+
+
+def records_host(res, image, label, labelled=True):
+    """The records of one batch (csrc/eval_tail.hip, records_body) for a model on the CPU, in
+    torch: (B, RECORD_FLOATS).  ``res`` gives the class probabilities (or neither), the
+    reconstruction mixture ``rec.pdf`` and ``_log_prob_per_point`` where the model has them."""
+    B = image.shape[0]
+    rows = torch.zeros(B, RECORD_FLOATS)
+    rows[:, 0:3] = -1.0
+    prior, post = getattr(res, "prior_cls_prob", None), getattr(res, "posterior_cls_prob", None)
+    labelled = labelled and label is not None
+    if labelled:
+        rows[:, 0] = label.to(torch.float32)
+    if prior is not None and post is not None:
+        ncls = prior.shape[-1]
+        for j, p in enumerate((prior.detach().float(), post.detach().float())):
+            cls = p.argmax(-1)
+            rows[:, 1 + j] = cls.to(torch.float32)
+            rows[:, 3 + j] = p.gather(1, cls[:, None])[:, 0]
+            if labelled:
+                ok = (label >= 0) & (label < ncls)
+                at = p.gather(1, label.clamp(0, ncls - 1)[:, None])[:, 0]
+                rows[:, 5 + j] = torch.where(ok, at, torch.zeros_like(at))
+    rec = getattr(res, "rec", None)
+    if rec is not None:
+        rows[:, 7] = rec.pdf.log_prob(image).detach().reshape(B, -1).sum(-1)
+    lpp = getattr(res, "_log_prob_per_point", None)
+    if lpp is not None:
+        rows[:, 8] = lpp.detach().sum(-1)
+    return rows
+
+
+def confusion_of(records, ncls):
+    """(2, ncls, ncls) int64 [head, label, predicted] counts of ``records``' rows (any device);
+    rows whose label lies outside [0, ncls) are not counted."""
+    lab = records[:, 0].to(torch.int64)
+    ok = (lab >= 0) & (lab < ncls)
+    out = []
+    for j in (1, 2):
+        cell = lab[ok] * ncls + records[ok, j].to(torch.int64)
+        out.append(torch.bincount(cell, minlength=ncls * ncls).view(ncls, ncls))
+    return torch.stack(out)
+
+
+def classification_report(confusion):
+    """Per-class support, recall and precision and the example-weighted accuracy of each head,
+    from a (2, ncls, ncls) [head, label, predicted] matrix (one read when it is on a device):
+    {"support" (ncls,) int64, "recall" (2, ncls), "precision" (2, ncls), "accuracy" (2,),
+    "predicted" (2, ncls) int64}, fp64 on the host.  A class without examples has recall 0, a
+    class never predicted precision 0, an empty matrix accuracy 0: no NaN."""
+    c = confusion.detach().to("cpu", torch.float64)
+    if c.dim() != 3 or c.shape[0] != 2 or c.shape[1] != c.shape[2]:
+        raise ValueError(f"confusion must be (2, ncls, ncls), got {tuple(confusion.shape)}")
+    hit = c.diagonal(dim1=1, dim2=2)
+    support, predicted = c.sum(2), c.sum(1)
+    recall = torch.where(support > 0, hit / support.clamp(min=1), torch.zeros_like(hit))
+    precision = torch.where(predicted > 0, hit / predicted.clamp(min=1), torch.zeros_like(hit))
+    total = support.sum(1)
+    accuracy = torch.where(total > 0, hit.sum(1) / total.clamp(min=1), torch.zeros_like(total))
+    return {"support": support[0].to(torch.int64), "recall": recall, "precision": precision,
+            "accuracy": accuracy, "predicted": predicted.to(torch.int64)}
 
 
 def accumulate_host(acc, loss, out12, prior, post, label):
@@ -152,6 +219,8 @@ class EvalStep:
         self._tail_step = None   # evaluate()'s remainder batch
         self._cap_sink = None    # the feature sink the captured launches carry
         self._cpu_rows = None    # encode() on the CPU: the batches' (B, 2, O) rows
+        self._cap_records = None    # the records the captured launches carry
+        self._cpu_records = None    # predict() on the CPU: (labelled, the batches' rows)
         self._zero_labels = None
 
     # -- the batch ----------------------------------------------------------
@@ -186,6 +255,9 @@ class EvalStep:
             if self._cpu_rows is not None:
                 self._cpu_rows.append(torch.stack(
                     [res.caps_presence, res.posterior_mixing_prob.sum(-1)], 1))
+            if self._cpu_records is not None:
+                self._cpu_records[1].append(records_host(res, self.image, label,
+                                                         self._cpu_records[0]))
             probs = (res.prior_cls_prob, res.posterior_cls_prob) if label is not None \
                 else (None, None)
             self.batch_acc.copy_(accumulate_host(self.acc, loss, out12_from_log(loss, log),
@@ -209,6 +281,17 @@ class EvalStep:
             # (the class probabilities did not ride in the loss tail: the rows on their own)
             with plan.active():
                 epi.sink.launch_alone(res.caps_presence, res["_posterior_full"])
+        if epi.records is not None and not epi.fused:
+            # (no fused epilogue to write them: the records' own launch, the reconstruction
+            # term from the decoder's tile sums or, without compact inputs, its per-pixel map)
+            with plan.active():
+                probs = (res.prior_cls_prob, res.posterior_cls_prob) \
+                    if label is not None else (None, None)
+                sums = res.rec.pdf.log_prob_tile_sums(self.image)
+                pixels = res.rec.pdf.log_prob(self.image) if sums is None else None
+                epi.records.launch_alone(*probs, label, res["_log_prob_per_point"],
+                                         rec_sums=sums, rec_pixels=pixels)
+            epi.records_alone = True
         if torch.cuda.is_current_stream_capturing():
             # the captured loss lives in the graph's pool at a fixed address
             self.loss = loss.detach()
@@ -309,6 +392,7 @@ class EvalStep:
                     lib.scae_launch_list_free(klist)
         self._home = self._storage()
         self._cap_sink = self.epi.sink
+        self._cap_records = self.epi.records
         self._refresh_prologue()
 
     def _graph_is_only_launches(self, n_launches):
@@ -357,7 +441,8 @@ class EvalStep:
 
     def _stale(self):
         return self.graph is None or self._home != self._storage() or \
-            self._cap_sink is not self.epi.sink
+            self._cap_sink is not self.epi.sink or \
+            self._cap_records is not self.epi.records
 
     def __call__(self, image, label):
         """One evaluation batch: stage, run (replay), accumulate.  -> the batch loss."""
@@ -676,3 +761,125 @@ class EvalStep:
         return {"prior": feats[:, 0], "posterior": feats[:, 1], "label": label,
                 "means": means(sums), "rows": written, "overflow": overflow,
                 "features": feats}
+
+    # -- per-example predictions and confusion matrices ----------------------------------------
+    def _attach_records(self, records):
+        """Aim this step's batches at ``records`` (off while the capture's warm-ups run)."""
+        self.epi.records = records
+        if self.use_graph:
+            self.capture()
+
+    def predict(self, images, labels=None, out=None):
+        """One record per image of a whole split, both heads' confusion matrices and the
+        split's evaluation means: every full batch replayed as ``evaluate`` runs it, the
+        remainder through the cached tail step, the records written on the way by the launch
+        that ends each batch (the fused epilogue's combine workgroup; for a model outside the
+        fused tail one launch of its own per batch).  ``images`` may be a data.DatasetView:
+        its rows come out in ``view.materialise()`` order and the view moves on to its next
+        epoch, as with ``evaluate`` and ``encode``.
+
+        -> {"records": (N, 9) fp32 device tensor, one row per image --
+              [0] label (-1 without labels)
+              [1] prior-head class  [2] posterior-head class (``torch.argmax``'s rule)
+              [3] [4] the heads' probability of their own predicted class
+              [5] [6] the heads' probability of the label's class (0 without labels)
+              [7] the image's reconstruction log-likelihood (``rec_ll``'s per-image term)
+              [8] the image's capsule log-likelihood (``log_prob``'s per-image term);
+            "label", "prior_class", "posterior_class", "prior_conf", "posterior_conf",
+            "prior_label_prob", "posterior_label_prob", "rec_ll", "log_prob": views of those
+            columns; "label_int", "prior_class_int", "posterior_class_int": the three as int64;
+            "confusion": (2, ncls, ncls) int64 device tensor indexed [head, label, predicted],
+            head 0 the prior and 1 the posterior (``classification_report`` reads it);
+            "means" (``evaluate``'s); "rows" (rows written); "overflow"}.
+        ``out``: an (R, 9) fp32 device buffer to write into (default: N rows); rows at or beyond
+        R are dropped, are not counted in ``confusion`` either, and ``overflow`` is True.
+        Without labels the step's loss sees zeros: the accuracies in ``means`` mean nothing,
+        ``confusion`` stays zero and means nothing either.  A model without classes gives
+        classes -1, probabilities 0 and an empty ``confusion``."""
+        from .data import DatasetView
+        if world()[1] > 1:
+            raise ValueError("predict gathers one process's rows: world > 1 is not supported")
+        ncls = getattr(self.model, "n_classes", None) or 0
+        view = images if isinstance(images, DatasetView) else None
+        if view is not None:
+            if not self.cuda:
+                raise ValueError("predicting a device-resident dataset needs a device step")
+            ds = view.dataset
+            if (ds.C, ds.H, ds.W) != self.image_shape:
+                raise ValueError(f"the view gives ({ds.C}, {ds.H}, {ds.W}) images, the step "
+                                 f"takes {self.image_shape}")
+            N = view.n
+        else:
+            N = images.shape[0]
+            if N == 0 or (labels is not None and labels.shape[0] != N):
+                raise ValueError("images and labels must hold the same number (> 0) of "
+                                 "examples")
+        labelled = view is not None or labels is not None
+        if out is None:
+            out = torch.empty(N, RECORD_FLOATS, device=self.device)
+        elif out.dim() != 2 or out.shape[1] != RECORD_FLOATS or \
+                out.dtype != torch.float32 or out.device != self.device or \
+                not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous (R, {RECORD_FLOATS}) fp32 tensor on "
+                             f"{self.device}")
+        confusion = torch.zeros(2, ncls, ncls, dtype=torch.int64, device=self.device)
+        B = self.batch_size
+        full, rem = divmod(N, B)
+        tail = self._tail(rem) if rem else None
+        steps = [self] + ([tail] if tail is not None else [])
+        if self.cuda:
+            if self.epi.records is None:
+                self.epi.records = ops.EvalRecords(self.device)
+            records = self.epi.records
+            records.off()
+            for st in steps:
+                st._attach_records(records)
+            records.point(out, confusion, labelled)
+        else:
+            for st in steps:
+                st._cpu_records = (labelled, [])
+        try:
+            self.reset()
+            if view is not None:
+                epoch = view.epoch
+                for i in range(full):
+                    self._run(lambda: self._stage_source(view, epoch, i * B))
+                if tail is not None:
+                    tail._run(lambda: tail._stage_source(view, epoch, full * B, rank=0,
+                                                         standalone=True))
+                view.epoch, view.cursor = epoch + 1, 0
+            else:
+                for i in range(full):
+                    self(images[i * B:(i + 1) * B], self._labels_for(labels, i * B,
+                                                                     (i + 1) * B))
+                if tail is not None:
+                    tail(images[full * B:], self._labels_for(labels, full * B, N))
+            sums = self.acc.clone()
+            if tail is not None:
+                sums += tail.acc
+                tail.reset()
+            self.reset()
+            if self.cuda:
+                cursor, overflow = records.status()
+                written = min(cursor, out.shape[0])
+            else:
+                got = torch.cat([r for st in steps for r in st._cpu_records[1]])
+                written = min(N, out.shape[0])
+                out[:written].copy_(got[:written])
+                overflow = N > out.shape[0]
+                if labelled and ncls:
+                    confusion = confusion_of(out[:written], ncls)
+        finally:
+            if self.cuda:
+                records.off()
+            else:
+                for st in steps:
+                    st._cpu_records = None
+        rows = out[:written]
+        res = {"records": rows, "confusion": confusion, "means": means(sums),
+               "rows": written, "overflow": overflow}
+        for name, j in RECORD_COLUMNS.items():
+            res[name] = rows[:, j]
+        for name in ("label", "prior_class", "posterior_class"):
+            res[name + "_int"] = res[name].to(torch.int64)
+        return res

@@ -3016,10 +3016,19 @@ class EvalEpilogue:
         self._keep = None       # what the last launch points into
         self.sink = None        # EvalSink the batch's classifier inputs go to (or None)
         self.sink_written = False   # the last forward's fused launches fed the sink
+        self.records = None     # EvalRecords the batch's per-image records go to (or None)
+        self.records_alone = False  # the last records launch was the stand-alone one
 
     def fused_launch(self, tail, prior, post, keep, stream_ref):
         _need_hip(prior, post)
-        if self.sink_written:
+        if self.records is not None:
+            # (the same launch: the combine workgroup writes the batch's records as well)
+            sink = ctypes.c_void_p(self.sink.ptr) if self.sink_written else None
+            _lib.call("scae_eval_tail_records_f32", *tail, _p(prior), _p(post), _p(self.acc),
+                      _p(self.batch3), sink, ctypes.c_void_p(self.records.ptr),
+                      _stream(stream_ref))
+            self.records_alone = False
+        elif self.sink_written:
             _lib.call("scae_eval_tail_sink_f32", *tail, _p(prior), _p(post), _p(self.acc),
                       _p(self.batch3), ctypes.c_void_p(self.sink.ptr), _stream(stream_ref))
         else:
@@ -3080,6 +3089,68 @@ class EvalSink:
         _lib.call("scae_eval_features_f32", _p(cp), _p(post), B, O1 - 1, M,
                   ctypes.c_void_p(self.ptr), _stream(cp))
         self._keep = (cp, post)
+
+
+class EvalRecords:
+    """The evaluation records (include/scae_hip.h, scae_eval_records): a device descriptor
+    that captured launches reach by its address.  ``point(rows, confusion, labelled)`` aims it
+    at an (N, 9) fp32 output and a (2, ncls, ncls) int64 matrix indexed [head, label,
+    predicted], with the cursor at 0 (``labelled=False``: the labels the step stages are
+    placeholders); ``off()`` sets the capacity to 0 (nothing written, the cursor stays);
+    ``status()`` reads (cursor, overflow) in one transfer.  ``launch_alone``: the records of a
+    batch that did not end in the fused epilogue, and the cursor's advance."""
+
+    def __init__(self, device):
+        self.desc = torch.zeros(_lib.EVAL_RECORDS_INT64S, device=device, dtype=torch.int64)
+        self.ptr = self.desc.data_ptr()
+        self.rows = self.confusion = None
+
+    def point(self, rows, confusion=None, labelled=True):
+        R = _lib.EVAL_RECORD_FLOATS
+        dev = self.desc.device
+        if rows is not None:
+            if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != R \
+                    or not rows.is_contiguous() or rows.device != dev:
+                raise ValueError(f"records rows must be a contiguous (N, {R}) fp32 tensor on "
+                                 "the records' device")
+            if confusion is not None and (
+                    confusion.dtype != torch.int64 or confusion.dim() != 3
+                    or confusion.shape[0] != 2 or confusion.shape[1] != confusion.shape[2]
+                    or not confusion.is_contiguous() or confusion.device != dev):
+                raise ValueError("confusion must be a contiguous (2, ncls, ncls) int64 tensor "
+                                 "on the records' device")
+        else:
+            confusion = None
+        self.rows, self.confusion = rows, confusion
+        self.desc.copy_(torch.tensor(
+            [0 if rows is None else rows.data_ptr(), 0 if rows is None else rows.shape[0], 0, 0,
+             0 if confusion is None else confusion.data_ptr(),
+             0 if confusion is None else confusion.shape[1], int(bool(labelled))],
+            dtype=torch.int64))
+
+    def off(self):
+        self.point(None)
+
+    def status(self):
+        v = self.desc[2:4].cpu()
+        return int(v[0]), bool(v[1])
+
+    def launch_alone(self, prior, post, label, lpp, rec_sums=None, rec_pixels=None):
+        """prior / post (B, ncls) or None, label (B) int64 or None, lpp (B, M), and the
+        reconstruction term as tile sums (B, tiles) or as a per-pixel map (B, ...)."""
+        _need_hip(prior, post, lpp, rec_sums, rec_pixels)
+        prior, post, label, lpp = (_c(t.detach()) if t is not None else None
+                                   for t in (prior, post, label, lpp))
+        rec = rec_sums if rec_sums is not None else rec_pixels
+        rec = _c(rec.detach()).flatten(1) if rec is not None else None
+        B, M = lpp.shape
+        ncls = 0 if prior is None else prior.shape[-1]
+        lab = None if label is None else ctypes.c_void_p(label.data_ptr())
+        _lib.call("scae_eval_records_f32", _p(prior), _p(post), lab, _p(lpp),
+                  _p(rec if rec_sums is not None else None),
+                  _p(rec if rec_sums is None else None), B, ncls, M,
+                  0 if rec is None else rec.shape[1], ctypes.c_void_p(self.ptr), _stream(lpp))
+        self._keep = (prior, post, label, lpp, rec)
 
 
 # The training log's row (include/scae_hip.h, SCAE_TRAIN_LOG_ROW) by SCAE.loss's log keys:
