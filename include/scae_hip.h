@@ -944,7 +944,32 @@ int scae_step_prologue_first_f32(float *dst_image, const float *src_image, int64
  *   wrap 1 (a drop_last=False epoch's short last step, DistributedSampler's padding): a
  *   position p >= n reads view row perm(p - n) -- the epoch's first examples again -- while
  *   its shift is still drawn from p itself; then position + (rank + 1) * B <= 2n instead.
- *   wrap 0 (ctypes' zero): no position may reach n. */
+ *   wrap 0 (ctypes' zero): no position may reach n.
+ *   affine non-NULL: the rest of the reference's transform -- RandomAffine(degrees, translate,
+ *   scale, shear) with nearest-neighbour resampling, as Pillow's fixed-point AFFINE path
+ *   samples it.  Row p of `affine` (affine_rows, 6) int32 holds position p's inverse map
+ *   k0..k5 in 16.16 fixed point; the host builds the table once per epoch
+ *   (data.affine_coefficients) and this launch only reads it:
+ *     one Philox draw (the generator's key schedule, 10 rounds, key = seed) at counter
+ *     (p, epoch_lo, epoch_hi, TAG_AFFINE); its words 0..3 >> 8 are 24-bit r for angle, scale,
+ *     shear-x, shear-y, value = lo + (hi - lo) * r / 2^24 in fp64 (degrees; scale 1 and
+ *     shear 0 where not asked for); (ty, tx) = the shift (dy, dx) above, acting on the
+ *     padded (H, W) image; under wrap the draw uses the unwrapped p, as the shift does;
+ *     with rot, sx, sy in radians and (cx, cy) = (W * 0.5, H * 0.5), in fp64:
+ *       a = cos(rot - sy) / cos(sy)     b = -cos(rot - sy) * tan(sx) / cos(sy) - sin(rot)
+ *       c = sin(rot - sy) / cos(sy)     d = -sin(rot - sy) * tan(sx) / cos(sy) + cos(rot)
+ *       M = [d, -b, 0, -c, a, 0] / scale
+ *       M[2] += M[0] * (-cx - tx) + M[1] * (-cy - ty) + cx
+ *       M[5] += M[3] * (-cx - tx) + M[4] * (-cy - ty) + cy
+ *     (torchvision's _get_inverse_affine_matrix); FIX(v) = floor(v * 65536 + 0.5),
+ *       k0, k1, k3, k4 = FIX(M[0]), FIX(M[1]), FIX(M[3]), FIX(M[4])
+ *       k2 = FIX(M[2] + M[0] * 0.5 + M[1] * 0.5)    k5 = FIX(M[5] + M[3] * 0.5 + M[4] * 0.5)
+ *   Sampling is pure integers (int64, arithmetic shifts): for pixel (i, j) of the padded image
+ *     xin = (k2 + k1 * i + k0 * j) >> 16      yin = (k5 + k4 * i + k3 * j) >> 16
+ *     out[b, c, i, j] = x[row, c, yin - (H - h)/2, xin - (W - w)/2] inside the example, else 0
+ *   (degrees = 0 without scale and shear gives the bits of affine = NULL); `translate` is
+ *   not read then -- the table holds the shift.  position + (rank + 1) * B <= affine_rows.
+ *   affine NULL (ctypes' zero): translation alone, as above. */
 typedef struct scae_batch_source_desc {
   const void *images;     /* (rows, C, h, w) uint8 (image_u8 = 1) or fp32 in [0, 1] */
   const void *labels;     /* (rows) uint8 (label_u8 = 1) or int64; nullable without labels out */
@@ -958,6 +983,8 @@ typedef struct scae_batch_source_desc {
   int64_t epoch, position;
   int rank, world;
   int wrap;               /* 1: positions in [n, 2n) read rows of p - n (see above) */
+  const int32_t *affine;  /* (affine_rows, 6) k0..k5 of each epoch position, nullable */
+  int64_t affine_rows;    /* positions the table covers */
 } scae_batch_source_desc;
 /* The rank's batch of B from `src` into dst_image (B, C, H, W) fp32 and dst_label (B) int64
  * (nullable), one launch. */

@@ -148,7 +148,8 @@ class BatchSourceDesc(Structure):
         [(n, c_int) for n in ("image_u8", "label_u8", "C", "h", "w", "H", "W",
                               "shuffle", "translate")] + \
         [("seed", c_uint64), ("epoch", c_int64), ("position", c_int64),
-         ("rank", c_int), ("world", c_int), ("wrap", c_int)]
+         ("rank", c_int), ("world", c_int), ("wrap", c_int),
+         ("affine", P), ("affine_rows", c_int64)]
 
 
 class SeedFoldGrads(Structure):

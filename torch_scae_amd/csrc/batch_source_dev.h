@@ -17,12 +17,19 @@
 // Shifts: two 24-bit uniforms r of one Philox draw keyed by seed at counter (p, epoch, tag);
 // shift = round half to even of 2*pad*r / 2^24 - pad, in integers (torchvision's
 // round(U(-pad, pad))), pad = (H - h) / 2 per axis; translate = 0: no shift.
+// affine != NULL: the example is resampled through position p's inverse affine map instead
+// (rotation, scale, shear and the shift above: RandomAffine with nearest-neighbour sampling).
+// Its six 16.16 fixed-point coefficients are row p of a table the host builds once per epoch
+// (include/scae_hip.h has the definition; data.affine_coefficients computes it in fp64); the
+// device only reads them and samples in integers, so every copy of an image holds the same
+// bits as data.affine_warp's.
 #pragma once
 #include "common.h"
 #include "noise_dev.h"
 
 namespace scae_src {
 constexpr uint32_t TAG_PERM = 0x5045524Du, TAG_SHIFT = 0x53484654u;
+// (data.py draws the affine parameters on the host at TAG_AFFINE = 0x4146464E)
 constexpr int FEISTEL_ROUNDS = 4, F_PHILOX_ROUNDS = 3, KEY_PHILOX_ROUNDS = 10;
 
 // Philox4x32 with the generator's key schedule (noise_dev.h), `rounds` rounds
@@ -37,6 +44,7 @@ __device__ __forceinline__ void philox(uint32_t (&c)[4], uint32_t k0, uint32_t k
 struct Draw {
   int64_t row;     // dataset row (-1: outside the dataset -- zeros)
   int top, left;   // placement of the example's (0, 0) in the padded image
+  int k[6];        // (affine) xin = (k2 + k1 i + k0 j) >> 16, yin = (k5 + k4 i + k3 j) >> 16
 };
 
 __device__ __forceinline__ int shift_of(uint32_t r24, int pad) {
@@ -85,6 +93,8 @@ __device__ __forceinline__ Draw draw(const scae_batch_source_desc &s, int64_t p)
   const uint32_t ry = (uint32_t)__shfl((int)c[0], 4) >> 8, rx = (uint32_t)__shfl((int)c[1], 4) >> 8;
   d.top = ph + (s.translate ? shift_of(ry, ph) : 0);
   d.left = pw + (s.translate ? shift_of(rx, pw) : 0);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) d.k[i] = s.affine ? s.affine[p * 6 + i] : 0;   // (p < affine_rows)
   return d;
 }
 
@@ -97,6 +107,21 @@ __device__ __forceinline__ Draw gather_image(const scae_batch_source_desc &s, in
   const uint8_t *img8 = static_cast<const uint8_t *>(s.images);
   const float *imgf = static_cast<const float *>(s.images);
   const size_t base = d.row < 0 ? 0 : (size_t)d.row * s.C * hw;
+  if (s.affine) {   // nearest-neighbour through the inverse map, in integers
+    const int ph = (s.H - s.h) / 2, pw = (s.W - s.w) / 2;
+    for (int e = threadIdx.x; e < count; e += 256) {
+      const int ch = e / HW, rr = e - ch * HW, i = rr / s.W, j = rr - i * s.W;
+      const int64_t sj = ((d.k[2] + (int64_t)d.k[1] * i + (int64_t)d.k[0] * j) >> 16) - pw;
+      const int64_t si = ((d.k[5] + (int64_t)d.k[4] * i + (int64_t)d.k[3] * j) >> 16) - ph;
+      float v = 0.f;
+      if (d.row >= 0 && si >= 0 && si < s.h && sj >= 0 && sj < s.w) {
+        const size_t off = base + (size_t)ch * hw + (size_t)si * s.w + (size_t)sj;
+        v = s.image_u8 ? __fdiv_rn((float)img8[off], 255.0f) : imgf[off];   // ToTensor
+      }
+      dst[e] = v;
+    }
+    return d;
+  }
   for (int e = threadIdx.x; e < count; e += 256) {
     const int ch = e / HW, rr = e - ch * HW, i = rr / s.W, j = rr - i * s.W;
     const int si = i - d.top, sj = j - d.left;
@@ -127,6 +152,8 @@ inline int check(const scae_batch_source_desc *s, int B) {
   SCAE_REQUIRE(a.wrap == 0 || a.wrap == 1);
   SCAE_REQUIRE(a.position + (int64_t)(a.rank + 1) * B <= (a.wrap ? 2 * a.n : a.n));
   SCAE_REQUIRE((a.image_u8 == 0 || a.image_u8 == 1) && (a.label_u8 == 0 || a.label_u8 == 1));
+  SCAE_REQUIRE(a.affine ? a.position + (int64_t)(a.rank + 1) * B <= a.affine_rows
+                        : a.affine_rows == 0);
   if (a.C > 4) return SCAE_ERR_UNSUPPORTED;
   return 0;
 }

@@ -21,7 +21,10 @@ a few hundred steps)
 with the transform applied on the device: a training step gathers its batch
 in its prologue launch (csrc/batch_source_dev.h, ``TrainStep.step_from``).
 Every view also has a CPU path that computes the same order and shifts in
-integer torch ops."""
+integer torch ops.  A view's ``affine=`` adds the transform's other arguments
+(``degrees``, ``scale``, ``shear``) with nearest-neighbour resampling:
+``affine_coefficients`` draws them and builds each position's fixed-point
+inverse map on the host, ``affine_warp`` is the CPU path of the sampling."""
 import gzip
 import math
 
@@ -103,7 +106,7 @@ def stroke_batches(n_batches, batch, image_shape, seed=0, device="cpu",
 # The draws of csrc/batch_source_dev.h in integer torch ops (int64 tensors holding uint32
 # values): Philox4x32 with the device generator's constants and key schedule (noise_dev.h).
 _M32 = 0xFFFFFFFF
-_TAG_PERM, _TAG_SHIFT = 0x5045524D, 0x53484654
+_TAG_PERM, _TAG_SHIFT, _TAG_AFFINE = 0x5045524D, 0x53484654, 0x4146464E
 _FEISTEL_ROUNDS, _F_PHILOX_ROUNDS, _KEY_PHILOX_ROUNDS = 4, 3, 10
 
 
@@ -180,6 +183,124 @@ def translate_shifts(positions, epoch, seed, pads):
     return torch.stack([shift_rule(c[0] >> 8, pads[0]), shift_rule(c[1] >> 8, pads[1])], 1)
 
 
+def _range(v, name, symmetric=False):
+    """(lo, hi) floats of a range argument; a number d means (-d, d) where ``symmetric``."""
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        if not symmetric:
+            raise ValueError(f"{name}: a (lo, hi) pair expected, got {v!r}")
+        if v < 0:
+            raise ValueError(f"{name}: a single number must be non-negative, got {v!r}")
+        v = (-v, v)
+    try:
+        lo, hi = (float(x) for x in v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: a (lo, hi) pair expected, got {v!r}") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+        raise ValueError(f"{name}: finite lo <= hi expected, got {v!r}")
+    return lo, hi
+
+
+def affine_ranges(affine):
+    """``affine = dict(degrees=d | (lo, hi), scale=(lo, hi) | None, shear=s | (lo, hi) |
+    (xlo, xhi, ylo, yhi) | None)`` -- torchvision's RandomAffine arguments; a number d means
+    (-d, d), a missing scale 1, a missing shear 0 -- validated and normalised to
+    ``dict(degrees=(lo, hi), scale=(lo, hi), shear=(xlo, xhi, ylo, yhi))`` of floats.
+    None stays None.  ValueError on anything else."""
+    if affine is None:
+        return None
+    if not isinstance(affine, dict) or set(affine) - {"degrees", "scale", "shear"}:
+        raise ValueError(f"affine: a dict of degrees / scale / shear expected, got {affine!r}")
+    deg = _range(affine.get("degrees", 0.0), "degrees", symmetric=True)
+    scale = affine.get("scale")
+    scale = (1.0, 1.0) if scale is None else _range(scale, "scale")
+    if scale[0] <= 0:
+        raise ValueError(f"scale: positive values expected, got {scale!r}")
+    shear = affine.get("shear")
+    if shear is None:
+        shear = (0.0, 0.0, 0.0, 0.0)
+    elif isinstance(shear, (int, float)) or len(shear) == 2:
+        shear = _range(shear, "shear", symmetric=True) + (0.0, 0.0)
+    elif len(shear) == 4:
+        shear = _range(shear[:2], "shear") + _range(shear[2:], "shear")
+    else:
+        raise ValueError(f"shear: 1, 2 or 4 values expected, got {shear!r}")
+    return {"degrees": deg, "scale": scale, "shear": shear}
+
+
+def affine_coefficients(positions, epoch, seed, pads, size, affine, translate=True):
+    """(len, 6) int64 k0..k5 of epoch positions: each position's inverse affine map in 16.16
+    fixed point, as Pillow's nearest-neighbour AFFINE path holds it (include/scae_hip.h,
+    scae_batch_source_desc, has the definition).  One Philox draw keyed by ``seed`` at
+    counter (position, epoch, TAG_AFFINE) gives 24-bit r for angle, scale, shear-x and
+    shear-y, value = lo + (hi - lo) r / 2^24 in the ranges of ``affine`` (``affine_ranges``
+    form or its input); the translation is ``translate_shifts`` of the same position
+    (``translate``; else none) on the padded image of ``size`` = (H, W); the matrix is
+    torchvision's ``_get_inverse_affine_matrix`` about (W / 2, H / 2) in fp64 and
+    FIX(v) = floor(v 65536 + 0.5).  Every value is a function of (seed, epoch, position)
+    alone.  ValueError where a coefficient leaves int32 (a scale too small, a shear too
+    close to 90 degrees)."""
+    a = affine_ranges(affine)
+    p = torch.as_tensor(positions, dtype=torch.int64)
+    H, W = size
+    c = _philox([p & _M32, _word(epoch, p), _word(epoch >> 32, p), _word(_TAG_AFFINE, p)],
+                seed & _M32, (seed >> 32) & _M32, _KEY_PHILOX_ROUNDS)
+
+    def value(word, lo, hi):
+        return lo + (hi - lo) * (word >> 8).to(torch.float64) / float(1 << 24)
+    rad = math.pi / 180.0                     # (math.radians' factor)
+    rot = value(c[0], *a["degrees"]) * rad
+    scale = value(c[1], *a["scale"])
+    sx = value(c[2], *a["shear"][:2]) * rad
+    sy = value(c[3], *a["shear"][2:]) * rad
+    shifts = translate_shifts(p, epoch, seed, pads) if translate \
+        else torch.zeros(p.numel(), 2, dtype=torch.int64)
+    ty, tx = shifts[:, 0].to(torch.float64), shifts[:, 1].to(torch.float64)
+    cx, cy = W * 0.5, H * 0.5
+    ma = torch.cos(rot - sy) / torch.cos(sy)
+    mb = -torch.cos(rot - sy) * torch.tan(sx) / torch.cos(sy) - torch.sin(rot)
+    mc = torch.sin(rot - sy) / torch.cos(sy)
+    md = -torch.sin(rot - sy) * torch.tan(sx) / torch.cos(sy) + torch.cos(rot)
+    m0, m1, m3, m4 = md / scale, -mb / scale, -mc / scale, ma / scale
+    m2 = m0 * (-cx - tx) + m1 * (-cy - ty) + cx
+    m5 = m3 * (-cx - tx) + m4 * (-cy - ty) + cy
+    k = torch.stack([m0, m1, m2 + m0 * 0.5 + m1 * 0.5, m3, m4, m5 + m3 * 0.5 + m4 * 0.5], 1)
+    k = torch.floor(k * 65536.0 + 0.5)
+    if not bool((torch.isfinite(k) & (k.abs() < float(1 << 31))).all()):
+        raise ValueError("affine: a coefficient does not fit 16.16 fixed point in int32 "
+                         "(scale too small or shear too close to 90 degrees)")
+    return k.to(torch.int64)
+
+
+def affine_warp(images, coeffs, out_size):
+    """images (B, C, h, w) uint8 or float, ``coeffs`` (B, 6) integer k0..k5
+    (``affine_coefficients``) -> (B, C, H, W) float32: the example, zero-padded to
+    ``out_size`` = (H, W), resampled through its inverse map with nearest-neighbour sampling
+    in pure integers -- pixel (i, j) reads padded-image pixel (yin, xin) =
+    ((k5 + k4 i + k3 j) >> 16, (k2 + k1 i + k0 j) >> 16), zero outside the example --
+    then ToTensor's division for uint8.  The CPU path of the device gather's affine form."""
+    B, C, h, w = images.shape
+    H, W = out_size
+    if H < h or W < w:
+        raise ValueError("output smaller than the images")
+    k = torch.as_tensor(coeffs).to(images.device, torch.int64)
+    if tuple(k.shape) != (B, 6):
+        raise ValueError(f"coeffs ({B}, 6) expected, got {tuple(k.shape)}")
+    x = images.to(torch.float32)
+    if not images.dtype.is_floating_point:
+        x = x / 255.0                         # ToTensor
+    ph, pw = (H - h) // 2, (W - w) // 2
+    k = k.view(B, 6, 1, 1)
+    i = torch.arange(H, device=images.device).view(1, H, 1)
+    j = torch.arange(W, device=images.device).view(1, 1, W)
+    jj = ((k[:, 2] + k[:, 1] * i + k[:, 0] * j) >> 16) - pw            # (B,H,W)
+    ii = ((k[:, 5] + k[:, 4] * i + k[:, 3] * j) >> 16) - ph
+    valid = (ii >= 0) & (ii < h) & (jj >= 0) & (jj < w)
+    flat = ii.clamp(0, h - 1) * w + jj.clamp(0, w - 1)
+    out = torch.gather(x.reshape(B, C, h * w), 2,
+                       flat.view(B, 1, H * W).expand(B, C, H * W))
+    return (out.view(B, C, H, W) * valid.unsqueeze(1)).contiguous()
+
+
 class ResidentDataset:
     """A dataset held in device memory once: ``images`` (N, C, h, w) or (N, h, w), uint8
     (pixels / 255, as ToTensor) or floating in [0, 1] (kept as fp32); ``labels`` (N,) uint8 or
@@ -219,15 +340,17 @@ class ResidentDataset:
     def __len__(self):
         return self.n
 
-    def view(self, shuffle=False, translate=True, seed=0, rank=0, world=1, drop_last=True):
+    def view(self, shuffle=False, translate=True, seed=0, rank=0, world=1, drop_last=True,
+             affine=None):
         """The whole dataset as one view (``DatasetView``)."""
-        return DatasetView(self, None, shuffle, translate, seed, rank, world, drop_last)
+        return DatasetView(self, None, shuffle, translate, seed, rank, world, drop_last,
+                           affine)
 
     def split(self, lengths, generator=None, **view_args):
         """Views over the rows ``torch.utils.data.random_split(range(N), lengths,
         generator)`` gives (``torch.randperm(N, generator=generator)`` cut in turn); lengths
         are integers summing to N.  ``view_args`` (shuffle, translate, seed, rank, world,
-        drop_last) apply to every view; a view's attributes can be changed afterwards."""
+        drop_last, affine) apply to every view; a view's attributes can be changed afterwards."""
         lengths = [int(v) for v in lengths]
         if sum(lengths) != self.n or any(v <= 0 for v in lengths):
             raise ValueError("lengths must be positive and sum to the dataset's size")
@@ -257,11 +380,24 @@ class DatasetView:
     spe*world*B + k*b, and a position p >= n reads the row of p - n (the epoch's first
     examples again, as DistributedSampler pads) with a shift drawn from p itself.  A
     ``TrainStep`` runs that step on its remainder step of batch b.
+
+    ``affine`` (``dict(degrees=, scale=, shear=)``, ``affine_ranges``): the other arguments
+    of the reference's ``RandomAffine`` -- every example is resampled, nearest neighbour,
+    through a rotation / scale / shear about the padded image's centre drawn per epoch
+    position, composed with the shift above (``affine_coefficients``; the shift acts on the
+    padded image, so unlike without ``affine`` it can augment an unpadded 32 x 32 dataset
+    too).  ``degrees=0`` alone gives the bits of ``affine=None``.  The positions' fixed-point
+    coefficients are built on the host and uploaded once per (view, epoch) -- (positions, 6)
+    int32, about 1.4 MB for 60 000 examples, this epoch's table and the previous one kept
+    alive for launches still in flight -- so the first device read of an epoch pays one
+    host-to-device copy, and every other step of the epoch stays "prologue launch + replay,
+    no torch operator, no copy".  An affinely warped test view (affNIST-style viewpoint
+    checks) is ``ds.view(translate=False, affine=...)``.
     ``epoch`` / ``cursor`` (steps taken in the epoch) advance with ``TrainStep.step_from``;
     ``state_dict`` carries them so that a resumed run continues in the same order."""
 
     def __init__(self, dataset, index=None, shuffle=False, translate=True, seed=0, rank=0,
-                 world=1, drop_last=True):
+                 world=1, drop_last=True, affine=None):
         self.dataset = dataset
         if index is not None:
             index = torch.as_tensor(index).to("cpu", torch.int64).contiguous()
@@ -280,6 +416,8 @@ class DatasetView:
         self.drop_last = bool(drop_last)
         if not self.drop_last and self.n < self.world:
             raise ValueError(f"{self.n} examples cannot give each of {self.world} ranks one")
+        self.affine = affine_ranges(affine)
+        self._tables = {}               # (device coefficient tables: ``_affine_table``)
         self.epoch = self.cursor = 0
 
     def __len__(self):
@@ -326,11 +464,21 @@ class DatasetView:
     def indices_and_shifts(self, epoch, step, batch):
         return self.rows_and_shifts(epoch, self.positions(step, batch))
 
+    def coefficients(self, epoch, positions):
+        """(len, 6) int64 inverse-map coefficients of epoch positions (``affine`` views; a
+        position p >= n keeps p for its draw, as for its shift) -- the CPU path."""
+        ds = self.dataset
+        return affine_coefficients(positions, epoch, self.seed, ds.pads, (ds.H, ds.W),
+                                   self.affine, self.translate)
+
     def _cpu_batch(self, epoch, positions):
         rows, shifts = self.rows_and_shifts(epoch, positions)
         ds = self.dataset
         src = ds.images[rows.to(ds.device)].cpu()
-        image = pad_and_translate(src, (ds.H, ds.W), shifts=shifts)
+        if self.affine is not None:
+            image = affine_warp(src, self.coefficients(epoch, positions), (ds.H, ds.W))
+        else:
+            image = pad_and_translate(src, (ds.H, ds.W), shifts=shifts)
         return image, ds.labels[rows.to(ds.device)].cpu().to(torch.int64)
 
     def batch(self, epoch, step, batch):
@@ -345,9 +493,30 @@ class DatasetView:
         return self._cpu_batch(self.epoch if epoch is None else epoch, torch.arange(self.n))
 
     # -- the device side --------------------------------------------------------------------
+    def _affine_table(self, epoch):
+        """The epoch's (positions, 6) int32 coefficient table on the device: every position
+        a step of the epoch can read -- n, plus the world - 1 a short step's padding can add
+        without ``drop_last``.  Built by the CPU path and uploaded on first use; the two
+        most recent tables stay alive (launches reading the previous epoch's may still be
+        in flight)."""
+        ds = self.dataset
+        count = self.n + (0 if self.drop_last else self.world - 1)
+        key = (int(epoch), self.seed, self.translate, count,
+               tuple(sorted(self.affine.items())))
+        table = self._tables.get(key)
+        if table is None:
+            table = self.coefficients(epoch, torch.arange(count)).to(torch.int32) \
+                .contiguous().to(ds.device)
+            while len(self._tables) >= 2:
+                del self._tables[next(iter(self._tables))]
+            self._tables[key] = table
+        return table
+
     def desc(self, epoch, position, rank=None):
         """struct scae_batch_source_desc of this rank's batch at epoch position
-        ``position`` (of the step's global batch)."""
+        ``position`` (of the step's global batch).  An ``affine`` view's descriptor points
+        at the epoch's coefficient table (uploaded here the first time the epoch is
+        asked for)."""
         from . import _lib
         ds = self.dataset
         d = _lib.BatchSourceDesc()
@@ -361,6 +530,9 @@ class DatasetView:
         d.seed, d.epoch, d.position = self.seed, int(epoch), int(position)
         d.rank, d.world = self.rank if rank is None else rank, self.world
         d.wrap = int(not self.drop_last)
+        if self.affine is not None:
+            table = self._affine_table(epoch)
+            d.affine, d.affine_rows = table.data_ptr(), table.shape[0]
         return d
 
     def check(self, batch, image_shape):
@@ -413,7 +585,9 @@ class DatasetView:
         ``steps_per_epoch(B)`` is a short step still to come."""
         return {"epoch": self.epoch, "cursor": self.cursor, "seed": self.seed,
                 "shuffle": self.shuffle, "translate": self.translate, "n": self.n,
-                "rank": self.rank, "world": self.world, "drop_last": self.drop_last}
+                "rank": self.rank, "world": self.world, "drop_last": self.drop_last,
+                "affine": None if self.affine is None else
+                {k: list(v) for k, v in self.affine.items()}}
 
     def load_state_dict(self, sd):
         if sd.get("n", self.n) != self.n or sd.get("world", self.world) != self.world:
@@ -422,6 +596,8 @@ class DatasetView:
         self.shuffle = bool(sd.get("shuffle", self.shuffle))
         self.translate = bool(sd.get("translate", self.translate))
         self.drop_last = bool(sd.get("drop_last", self.drop_last))
+        if "affine" in sd:
+            self.affine = affine_ranges(sd["affine"])
         self.epoch, self.cursor = int(sd["epoch"]), int(sd["cursor"])
 
 
