@@ -233,6 +233,7 @@ def test_capsule_likelihood_no_presence_vs_golden():
     (3, 130, 100),    # the largest capsule product the factory admits
 ])
 def test_capsule_likelihood_vs_oracle_cfg2(B, Oc, M):
+    """Three of the eight gradient paths, benign inputs, fp32 oracle: the rest is test_capsule_likelihood_vs_fp64.py."""
     from torch_scae_amd.object_decoder import CapsuleLikelihood
     g = torch.Generator().manual_seed(77)
     ins = dict(vote=torch.randn(B, Oc, M, 6, generator=g),
