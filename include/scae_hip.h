@@ -1661,6 +1661,65 @@ int scae_kmeans_assign_f32(const float *x, int64_t N, int F, int k, const float 
 int scae_kmeans_contingency(const int64_t *cluster_ids, const int64_t *labels, int64_t N, int k,
                             int ncls, int *table, int *outside, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Linear probe (csrc/linear_probe.hip): multinomial logistic regression with L2 on the weights
+ * (not the bias) on standardised features z = (x - mean) * scale with a trailing 1, R values of
+ * l2 solved side by side.  Objective per problem, V of shape (C, F + 1):
+ *   J(V) = (1/N) sum_n [logsumexp_c(V_c . z_n) - V_{y_n} . z_n] + (l2/2) sum_{c, f<F} V_{c,f}^2
+ * FISTA with gradient restart from the state (W, V, t): g = grad J(V); W' = V - step g; if
+ * sum g (W' - W) > 0 (fp64) t = 1; t' = (1 + sqrt(1 + 4 t^2)) / 2; V = W' + ((t - 1)/t')
+ * (W' - W); W = W', t = t'.  The iteration that measures max|g| <= tol ends its problem as
+ * converged with W = V (the point the gradient belongs to, no step taken); a problem also ends
+ * after max_iter iterations.  No float atomics, fixed-order sums.
+ * ------------------------------------------------------------------------ */
+#define SCAE_PROBE_MAX_F 256
+#define SCAE_PROBE_MAX_C 256
+#define SCAE_PROBE_MAX_CF 16384    /* C * (F + 1): one problem's V in LDS */
+#define SCAE_PROBE_MAX_R 16
+#define SCAE_PROBE_STATE_INTS 4    /* per problem: done, iterations, converged, restarts */
+int scae_probe_supported(int F, int C, int R);
+/* the row groups of the moments and gradient launches: whole 64-row tiles, a contiguous row
+ * range each; a function of (N, F) alone (0 for arguments out of range) */
+int scae_probe_groups(int64_t N, int F);
+/* the workgroups (= cross-entropy partials) of a prediction launch over N rows */
+int scae_probe_predict_blocks(int64_t N);
+/* moments (F + 1, F + 1) fp64 = [x 1]^T [x 1] of x (N, F): per-group partials in part
+ * (scae_probe_groups(N, F), (F + 1)^2), added in group order.  With y, *outside += the labels
+ * outside [0, C) (an integer count). */
+int scae_probe_moments_f64(const float *x, const int64_t *y, int64_t N, int F, int C,
+                           double *part, double *moments, int *outside, void *stream);
+typedef struct scae_probe_desc {
+  const float *x;        /* (N, F) raw features */
+  const int64_t *y;      /* (N) labels in [0, C) */
+  int64_t N;
+  int F, C, R;           /* features, classes, problems */
+  int G;                 /* scae_probe_groups(N, F) */
+  int max_iter;
+  const float *mean;     /* (F) */
+  const float *scale;    /* (F): 1 / standard deviation, 0 for a constant column */
+  const double *l2;      /* (R) */
+  const double *step;    /* (R): 1 / L */
+  const double *tol;     /* (R) */
+  float *W, *V;          /* (R, C, F + 1): the state in, the result out */
+  float *grad;           /* (R, C, F + 1): grad J(V) of the last iteration */
+  double *t;             /* (R): the momentum scalar, 1 at the start */
+  float *part_grad;      /* (R, G, C (F + 1)) */
+  double *part_loss;     /* (R, G) */
+  double *history;       /* (R, max_iter, 3): J(V), max|g|, restarted, one row per iteration */
+  int *state;            /* R * SCAE_PROBE_STATE_INTS + 1 zeros; the last int counts the
+                          * problems that have stopped (the host's one read per chunk) */
+} scae_probe_desc;
+/* n_iters iterations of every running problem, two launches each: the gradient partials of
+ * all problems from one pass over x, then per problem the fixed-order reduction, the update,
+ * a history row and the stop decision.  A stopped problem's state is left untouched. */
+int scae_probe_fit_f32(const scae_probe_desc *d, int n_iters, void *stream);
+/* pred (N) = arg max_c of weight (C, F) . x + bias (C), ties to the lowest class; log_prob (N)
+ * the row's log-probability of that class.  With y: *mean_ce = the fp64 mean of the rows'
+ * cross-entropy, from part_ce (scae_probe_predict_blocks(N)) partials added in block order. */
+int scae_probe_predict_f32(const float *x, int64_t N, int F, int C, const float *weight,
+                           const float *bias, const int64_t *y, int64_t *pred, float *log_prob,
+                           double *part_ce, double *mean_ce, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,14 @@ class KMeansDesc(Structure):
                 ("part_inertia", P), ("state", P), ("inertia", P)]
 
 
+class ProbeDesc(Structure):
+    """struct scae_probe_desc"""
+    _fields_ = [("x", P), ("y", P), ("N", c_int64), ("F", c_int), ("C", c_int), ("R", c_int),
+                ("G", c_int), ("max_iter", c_int), ("mean", P), ("scale", P), ("l2", P),
+                ("step", P), ("tol", P), ("W", P), ("V", P), ("grad", P), ("t", P),
+                ("part_grad", P), ("part_loss", P), ("history", P), ("state", P)]
+
+
 class SeedFoldDesc(Structure):
     """struct scae_seed_fold_desc"""
     _fields_ = [(n, P) for n in (
@@ -372,6 +380,12 @@ SIGNATURES = {
     "scae_kmeans_pp_f32": [P, c_int64, c_int, c_int, c_int, c_uint32, P, P, P, P],
     "scae_kmeans_assign_f32": [P, c_int64, c_int, c_int, P, P, P],
     "scae_kmeans_contingency": [P, P, c_int64, c_int, c_int, P, P, P],
+    "scae_probe_supported": [c_int] * 3,
+    "scae_probe_groups": [c_int64, c_int],
+    "scae_probe_predict_blocks": [c_int64],
+    "scae_probe_moments_f64": [P, P, c_int64, c_int, c_int, P, P, P, P],
+    "scae_probe_fit_f32": [POINTER(ProbeDesc), c_int, P],
+    "scae_probe_predict_f32": [P, c_int64, c_int, c_int] + [P] * 8,
     "scae_template_render_fwd_f32": [POINTER(DecoderDesc), P, P, P],
     "scae_render_gmm_logprob_fwd_f32": [POINTER(DecoderDesc), P, P, P, P, P],
     "scae_render_gmm_bwd_f32": [POINTER(DecoderDesc)] + [P] * 12 + [P],
@@ -395,6 +409,7 @@ _RESTYPES = {"scae_error_string": c_char_p,
 EVAL_ACC_DOUBLES = 17        # SCAE_EVAL_ACC_DOUBLES: the accumulator of scae_eval_*
 TRAIN_LOG_ROW = 19           # SCAE_TRAIN_LOG_ROW: one row of scae_train_log_desc's ring
 KMEANS_STATE_INTS = 4        # SCAE_KMEANS_STATE_INTS: per restart of scae_kmeans_desc's state
+PROBE_STATE_INTS = 4         # SCAE_PROBE_STATE_INTS: per problem of scae_probe_desc's state
 EVAL_SINK_INT64S = 4         # struct scae_eval_sink: rows, capacity, cursor, overflow
 # struct scae_eval_records: rows, capacity, cursor, overflow, confusion, ncls, labelled
 EVAL_RECORDS_INT64S = 7
