@@ -325,7 +325,7 @@ def test_replayed_forms_compute_the_eager_steps_gradients(replay):
             assert step._form == "update" and not torch.equal(step.flat.flat_param, before), i
             assert float(step.opt.acc.abs().max()) == 0.0
             host = None
-    assert step._other_form is not None and step._other_form["graph"] is not None
+    assert step._other_cap is not None and step._other_cap.graph is not None
     assert step.optimizer_steps == 2 and int(step.opt.step_state[0]) == 2
 
 
@@ -396,7 +396,7 @@ def test_k1_is_the_default_step():
         for img, lab in data:
             step(img, lab)
         torch.cuda.synchronize()
-        assert step.opt.acc is None and step._other_form is None
+        assert step.opt.acc is None and step._other_cap is None
         outs.append((step.flat.flat_param.clone(), step.opt.square_avg.clone(),
                      step.opt.buf.clone(), _launch_count(step)))
     for a, b in zip(*outs):

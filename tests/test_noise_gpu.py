@@ -415,7 +415,7 @@ def test_accumulate_and_update_forms_share_one_counter():
             step(x, y)
             noise, state = _noise_of(step)
             _check(noise, seed, _read(state)[1] - 1, CFG2_N, "a capturing batch")
-        assert step._other_form is not None and step._other_form["graph"] is not None
+        assert step._other_cap is not None and step._other_cap.graph is not None
         assert len(step.plan.noise) == 1         # one generator state for both forms
         i0 = _read(state)[1]
         assert i0 == count.of(state)

@@ -25,6 +25,7 @@ import torch
 
 from . import _lib
 from .data import _M32, _philox
+from .ops import _p as _P, _stream   # (probe.py takes them from here too)
 
 MAX_K, MAX_F, MAX_KF = 256, 256, 16384   # SCAE_KMEANS_MAX_K / _F / _KF
 _TAG_KMPP = 0x4B4D5050
@@ -162,14 +163,6 @@ def kmeans_host(x, k, n_init=10, max_iter=300, seed=0, init="k-means++", check_e
 
 
 # -- the device path ------------------------------------------------------------------------------
-def _P(t):
-    return ctypes.c_void_p(0 if t is None else t.data_ptr())
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def kmeans(x, k, n_init=10, max_iter=300, seed=0, init="k-means++", check_every=8):
     """Lloyd's k-means of ``n_init`` restarts of the rows of ``x`` (N, F) fp32.  ``init``:
     "k-means++" (seeded by ``seed``) or a (k, F) / (n_init, k, F) tensor (its first dimension

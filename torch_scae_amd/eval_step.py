@@ -11,6 +11,7 @@ import contextlib
 import torch
 
 from . import ops
+from . import replay as _replay   # (``replay`` is the steps' constructor argument)
 from .data_parallel import all_reduce_sums, world
 
 # the accumulator (include/scae_hip.h, SCAE_EVAL_ACC_DOUBLES): [0] batches, then the sums
@@ -209,11 +210,8 @@ class EvalStep:
         self.image = torch.zeros(batch_size, *image_shape, device=self.device)
         self.label = torch.zeros(batch_size, dtype=torch.long, device=self.device)
         self.loss = torch.zeros((), device=self.device)
-        self.graph = None
-        self.graph_nodes = None  # (graph nodes, kernel nodes, recorded launches) of a capture
+        self._cap = _replay.Captured()
         self.fused = None        # the captured batch ends in the fused epilogue
-        self._klist = None
-        self._launches = None
         self._stream = None
         self._home = None        # parameter storage the capture read
         self._tail_step = None   # evaluate()'s remainder batch
@@ -222,6 +220,12 @@ class EvalStep:
         self._cap_records = None    # the records the captured launches carry
         self._cpu_records = None    # predict() on the CPU: (labelled, the batches' rows)
         self._zero_labels = None
+
+    # the captured batch, read-only (replay.Captured; _klist: its list's raw handle)
+    graph = _replay.forwarded("graph")
+    _klist = _replay.forwarded("handle")
+    _launches = _replay.forwarded("launches")
+    graph_nodes = _replay.forwarded("nodes")
 
     # -- the batch ----------------------------------------------------------
     def _storage(self):
@@ -299,52 +303,24 @@ class EvalStep:
             self.loss.copy_(loss.detach())
 
     def _refresh_prologue(self):
-        if self._pro is not None:
-            with self.plan.active():
-                self._pro.launch(stream_ref=self.image)
+        _replay.refresh_prologue(self.plan, self._pro, self.image)
 
     def _stage(self, image, label):
-        """The batch into the resident buffers: the prologue's hand-over launch when both
-        tensors already live on the device in the buffers' layout."""
+        """The batch into the resident buffers (replay.stage)."""
         if tuple(image.shape) != tuple(self.image.shape) or \
                 tuple(label.shape) != tuple(self.label.shape):
             raise ValueError(f"batch of shape {tuple(image.shape)} / {tuple(label.shape)}; "
                              f"this step takes {tuple(self.image.shape)} / "
                              f"{tuple(self.label.shape)}")
-        direct = image.is_cuda and label.is_cuda and image.dtype == self.image.dtype \
-            and label.dtype == self.label.dtype and image.is_contiguous() \
-            and label.is_contiguous() and image.device == self.device == label.device
-        if self._pro is not None and direct:
-            with self.plan.active():
-                self._pro.launch(self.image, image, self.label, label)
-            return
-        self.image.copy_(image, non_blocking=True)
-        self.label.copy_(label, non_blocking=True)
-        self._refresh_prologue()
+        _replay.stage(self.plan, self._pro, self.image, self.label, image, label, self.device)
 
     def _stage_source(self, view, epoch, position, rank=None, standalone=False):
-        """The batch at ``position`` of ``epoch`` gathered from a device-resident dataset
-        (data.DatasetView) into the resident buffers: the prologue's source mode, or
-        (``standalone``, or no prologue) the standalone gather and a refresh of the
-        prologue."""
-        src = view.desc(epoch, position, rank)
-        if self._pro is not None and not standalone:
-            with self.plan.active():
-                self._pro.launch(self.image, None, self.label, source=src)
-            return
-        import ctypes
-        from . import _lib
-        P = ctypes.c_void_p
-        _lib.call("scae_gather_batch_f32", P(self.image.data_ptr()),
-                  P(self.label.data_ptr()), self.batch_size, ctypes.byref(src),
-                  P(torch.cuda.current_stream(self.device).cuda_stream))
-        self._refresh_prologue()
+        """The view's batch at ``position`` of ``epoch`` gathered (replay.stage_source)."""
+        _replay.stage_source(self.plan, self._pro, self.image, self.label, view, epoch,
+                             position, rank=rank, standalone=standalone)
 
     # -- capture / replay ---------------------------------------------------
     def _capture(self):
-        import ctypes
-        import torch.distributed as dist
-        from . import _lib
         # parameters re-homed since the last capture: the prologue's registered layer
         # inputs point at the old storage -- a fresh prologue (the generator state lives
         # in the plan and continues)
@@ -364,79 +340,19 @@ class EvalStep:
             torch.cuda.current_stream(self.device).wait_stream(s)
             # the warm-ups' batches are not the epoch's
             self.acc.zero_()
-            try:
-                # (keep_graph: the captured graph stays readable -- graph_nodes)
-                graph = torch.cuda.CUDAGraph(keep_graph=True)
-            except TypeError:        # (a torch without keep_graph: graph replay only)
-                graph = torch.cuda.CUDAGraph()
-            mode = "thread_local" if dist.is_available() and dist.is_initialized() \
-                else "global"
-            lib = _lib.load()
-            self._free_list()
-            klist = lib.scae_launch_list_begin(ctypes.c_void_p(s.cuda_stream))
-            try:
-                with torch.cuda.graph(graph, stream=s, capture_error_mode=mode), \
-                        _lib.recorder() as launches:
-                    self._batch()
-                if klist:
-                    lib.scae_launch_list_end(klist)
-                self.graph, self._launches = graph, launches
-                if klist and self.replay == "launches" and \
-                        self._graph_is_only_launches(lib.scae_launch_list_size(klist)):
-                    self._klist, klist = klist, None
-                elif self._klist is None:
-                    self._graph_is_only_launches(
-                        lib.scae_launch_list_size(klist) if klist else -1)
-            finally:
-                if klist:
-                    lib.scae_launch_list_free(klist)
+            # (keep_graph: the captured graph stays readable -- graph_nodes, always read)
+            self._cap = _replay.capture(s, self._batch, keep_graph=True, census_always=True,
+                                        want_list=self.replay == "launches")
         self._home = self._storage()
         self._cap_sink = self.epi.sink
         self._cap_records = self.epi.records
         self._refresh_prologue()
 
-    def _graph_is_only_launches(self, n_launches):
-        """True when the captured graph's nodes are exactly ``n_launches`` kernel nodes (the
-        library's record); sets ``graph_nodes``."""
-        import ctypes
-        try:
-            raw = self.graph.raw_cuda_graph()
-            hip = ctypes.CDLL("libamdhip64.so")
-            n = ctypes.c_size_t(0)
-            if hip.hipGraphGetNodes(ctypes.c_void_p(raw), None, ctypes.byref(n)) != 0:
-                return False
-            nodes = (ctypes.c_void_p * max(1, n.value))()
-            if hip.hipGraphGetNodes(ctypes.c_void_p(raw), nodes, ctypes.byref(n)) != 0:
-                return False
-            kernels = other = 0
-            for i in range(n.value):
-                t = ctypes.c_int(-1)
-                if hip.hipGraphNodeGetType(ctypes.c_void_p(nodes[i]), ctypes.byref(t)) != 0:
-                    return False
-                kernels += t.value == 0          # hipGraphNodeTypeKernel
-                other += t.value not in (0, 5, 6, 7)
-            self.graph_nodes = (n.value, kernels, n_launches)
-            return other == 0 and kernels == n_launches
-        except Exception:       # (no raw graph in this torch build)
-            return False
-
-    def _free_list(self):
-        if getattr(self, "_klist", None):
-            from . import _lib
-            _lib.load().scae_launch_list_free(self._klist)
-        self._klist = None
-
-    def __del__(self):
-        try:
-            self._free_list()
-        except Exception:      # (interpreter shutdown)
-            pass
-
     def capture(self):
         """Build the step's graph now (or again, when the parameters have been re-homed
         since the last capture).  The accumulator is left cleared."""
         if self.use_graph and self._stale():
-            self.graph = None
+            self._cap.drop()
             self._capture()
 
     def _stale(self):
@@ -457,13 +373,7 @@ class EvalStep:
                 self.capture()
                 self.acc.copy_(kept)
                 stage()
-            if self._klist:
-                import ctypes
-                from . import _lib
-                _lib.call("scae_launch_list_run", self._klist, ctypes.c_void_p(
-                    torch.cuda.current_stream(self.device).cuda_stream))
-            else:
-                self.graph.replay()
+            self._cap.replay(self.device)
         else:
             with self._eval_mode():
                 self._batch()

@@ -10,9 +10,9 @@ import os
 import weakref
 
 import torch
-import torch.distributed as dist
 
 from . import ops
+from . import replay as _replay   # (``replay`` is the steps' constructor argument)
 from .data_parallel import (FlatParameters, accumulate_value, all_reduce_gradients,
                             broadcast_parameters, clip_value, load_optimizer_state_dict,
                             make_optimizer, optimizer_state_dict, world)
@@ -27,9 +27,6 @@ REMAINDER_NOISE_SALT = 0x52454D41494E4452 & ((1 << 63) - 1)
 # model): the first all-reduce bucket
 EARLY_PREFIXES = ("obj_decoder.", "part_decoder.", "prior_classifier.",
                   "posterior_classifier.")
-
-# what a captured form of the step holds (TrainStep._use_form swaps them)
-FORM_ATTRS = ("graph", "graph_b", "_klist", "_launches", "graph_nodes", "loss")
 
 
 def update_batch(i, steps_in_epoch, k):
@@ -135,8 +132,9 @@ class TrainStep:
         # batches accumulated since the last optimiser step, optimiser steps taken (one dict,
         # shared with the remainder step)
         self._acc_state = {"pending": 0, "optimizer_steps": 0}
-        self._form = "update"     # the captured form in the step's attributes (FORM_ATTRS)
-        self._other_form = None   # ... and the other one, once captured
+        self._form = "update"     # the captured form the step holds in _cap (with its loss)
+        self._cap = _replay.Captured()
+        self._other_cap = self._other_loss = None   # ... the other one, once swapped out
         self._parent = None      # (a remainder step: the step whose state it shares)
         self._rem = None         # the cached remainder step (remainder_step)
         self.model = model
@@ -235,7 +233,7 @@ class TrainStep:
         self.use_graph = use_graph
         # how a captured step is re-issued: "graph" (hipGraphLaunch: ~10 us of host time and
         # ~8.6 us of device time between two replays, tools/graph_gap_probe.py) or "launches"
-        # (the library's record of the captured launches -- scae_launch_list_run: a
+        # (the library's record of the captured launches -- replay.LaunchList.run: a
         # hipLaunchKernel each on the current stream, no per-replay device cost: 0-5 us per
         # step at cfg-2 depending on the host -- ~18 us of host time per launch leave little
         # room beside a 550 us step --, tools/launch_list_probe.py; single-rank steps only,
@@ -244,9 +242,6 @@ class TrainStep:
         if replay not in ("graph", "launches"):
             raise ValueError("replay must be 'graph' or 'launches'")
         self.replay = replay
-        self._launches = None
-        self._klist = None
-        self.graph_nodes = None  # (graph nodes, kernel nodes, recorded launches) of a capture
         # independent kernels of the step sharing launches (ops.step_fusion:
         # the reconstruction likelihood rides with the object encoder's trunk)
         self.fuse_kernels = fuse_kernels
@@ -254,9 +249,14 @@ class TrainStep:
         self._capturing = False
         self._stream = None
         self._with_log = False
-        self.graph = None        # the whole step, or its part A when split
-        self.graph_b = None
         self._cut = None
+
+    # the captured form in use, read-only (replay.Captured; _klist: its list's raw handle)
+    graph = _replay.forwarded("graph")
+    graph_b = _replay.forwarded("graph_b")
+    _klist = _replay.forwarded("handle")
+    _launches = _replay.forwarded("launches")
+    graph_nodes = _replay.forwarded("nodes")
 
     @property
     def steps(self):
@@ -285,21 +285,19 @@ class TrainStep:
         if form == self._form:
             return
         if self._tail_captured():
-            keep = {k: getattr(self, k) for k in FORM_ATTRS}
-            other = self._other_form or dict(
-                {k: None for k in FORM_ATTRS}, loss=torch.zeros((), device=self.device))
-            for k, v in other.items():
-                setattr(self, k, v)
-            self._other_form = keep
+            cap, loss = self._other_cap, self._other_loss
+            if cap is None:
+                cap, loss = _replay.Captured(), torch.zeros((), device=self.device)
+            self._other_cap, self._other_loss = self._cap, self.loss
+            self._cap, self.loss = cap, loss
         self._form = form
 
     def _drop_forms(self):
         """Forget both captured forms (the next step captures again)."""
-        other, self._other_form = self._other_form, None
-        if other and other.get("_klist"):
-            from . import _lib
-            _lib.load().scae_launch_list_free(other["_klist"])
-        self.graph = self.graph_b = None
+        self._cap.drop()
+        if self._other_cap is not None:
+            self._other_cap.drop()
+        self._other_cap = self._other_loss = None
 
     # -- the remainder step ---------------------------------------------------
     def remainder_step(self, size):
@@ -315,7 +313,7 @@ class TrainStep:
         rem = self._rem
         if rem is None or rem.image.shape[0] != size:
             if rem is not None:
-                rem._free_list()
+                rem._drop_forms()
             self._rem = None
             rem = self._rem = self._remainder_of(size)
         if self._with_log and not rem._with_log:
@@ -346,10 +344,10 @@ class TrainStep:
         rem.label = torch.zeros(size, dtype=torch.long, device=self.device)
         rem.loss = torch.zeros((), device=self.device)
         rem.log = None
-        rem._launches = rem._klist = rem.graph_nodes = None
-        rem.graph = rem.graph_b = rem._cut = None
+        rem._cap, rem._other_cap, rem._other_loss = _replay.Captured(), None, None
+        rem._cut = None
         rem._capturing = rem._warming = False
-        rem._form, rem._other_form = "update", None
+        rem._form = "update"
         return rem
 
     def _for_batch(self, size):
@@ -546,125 +544,42 @@ class TrainStep:
         torch.cuda.current_stream().wait_stream(s)
         # capture on the SAME stream the warm-up ran on: autograd caches each
         # parameter's AccumulateGrad node together with its stream
-        # (keep_graph: the captured hipGraph_t stays readable -- _graph_is_only_launches)
-        try:
-            self.graph = torch.cuda.CUDAGraph(keep_graph=self.replay == "launches")
-        except TypeError:            # (a torch without keep_graph: graph replay only)
-            self.graph = torch.cuda.CUDAGraph()
-        # With a process group alive its watchdog thread polls HIP events at
-        # any time; under the default "global" capture mode such a poll during
-        # the capture is an error that aborts the process.  Then (and only
-        # then) the check is narrowed to the capturing thread.
-        mode = "thread_local" if dist.is_available() and dist.is_initialized() \
-            else "global"
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
-        self._free_list()
-        # the library's record of the launches this capture issues: bound to the capturing
-        # stream, so another step's (or an eager forward's) launches on other streams are
-        # not in it (include/scae_hip.h, launch lists)
-        klist = lib.scae_launch_list_begin(ctypes.c_void_p(s.cuda_stream))
+        self._cap.drop()
+        # an accumulating step's second form shares the first one's memory pool: the two
+        # never replay at once, and each rewrites its temporaries before reading them
+        other = self._other_cap.graph if self._other_cap is not None else None
         self._capturing = True
-        ok = False
         try:
-            # an accumulating step's second form shares the first one's memory pool: the two
-            # never replay at once, and each rewrites its temporaries before reading them
-            other = (self._other_form or {}).get("graph")
-            pool = dict(pool=other.pool()) if other is not None else {}
-            with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode, **pool), \
-                    _lib.recorder() as launches:
-                self._part_a()
-                if not self.split:
-                    self._part_b()
-                    if not self.collective or self.in_graph_collective:
-                        self._finish()
-            if klist:
-                lib.scae_launch_list_end(klist)
-            # The step as a plain list of kernel launches (scae_launch_list_*: kernel, grid,
-            # block, LDS, argument bytes), re-issued by replay_launches() -- but only when the
-            # graph holds exactly these: a captured torch kernel (training_step's accuracy
-            # and log copies), a memset inside a launcher or a collective is a node of the
-            # graph that the list does not have, and replaying the list would silently drop
-            # it.  `launches` (the C-ABI calls with their ctypes arguments) keeps the
-            # buffers the list points into alive.
-            self._launches = launches if not self.collective else None
-            if klist and not self.collective and not self.split \
-                    and self.replay == "launches" \
-                    and self._graph_is_only_launches(lib.scae_launch_list_size(klist)):
-                self._klist, klist = klist, None
+            # the step replays as the library's launch list (replay.adopts) on a single rank
+            # only: a collective is a node of the graph that the list does not have
+            cap = _replay.capture(
+                s, self._captured, keep_graph=self.replay == "launches",
+                pool=None if other is None else other.pool(),
+                want_list=not self.collective and not self.split and self.replay == "launches")
+            if self.collective:
+                cap.launches = None
             if self.split:
                 # part B allocates from part A's pool: the tensors A left for it
                 # (saved activations, the cut gradients) are alive across the two
                 # captures, and the graphs are always replayed A, B, A, B, ...
-                self.graph_b = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_b, stream=s,
-                                      pool=self.graph.pool(),
-                                      capture_error_mode=mode):
+                cap.graph_b = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(cap.graph_b, stream=s, pool=cap.graph.pool(),
+                                      capture_error_mode=_replay.capture_error_mode()):
                     self._part_b()
-            ok = True
+            self._cap = cap
         finally:
             # (a capture that raised -- out of memory, an op that cannot be captured -- must
             # not leave the step in capture mode: eager calls would drop held column sums
             # and alias self.loss to a pool tensor)
             self._capturing = False
-            if klist:
-                lib.scae_launch_list_free(klist)
-            if not ok:
-                self.graph = self.graph_b = None
-                self._launches = None
-                self._free_list()
 
-    def _graph_is_only_launches(self, n_launches):
-        """True when the captured graph's nodes are exactly ``n_launches`` kernel nodes (what
-        the library recorded): only then is the launch list the whole step.  Anything that
-        cannot be verified counts as a mismatch (the step then replays its graph)."""
-        import ctypes
-        try:
-            raw = self.graph.raw_cuda_graph()
-            hip = ctypes.CDLL("libamdhip64.so")
-            n = ctypes.c_size_t(0)
-            if hip.hipGraphGetNodes(ctypes.c_void_p(raw), None, ctypes.byref(n)) != 0:
-                return False
-            nodes = (ctypes.c_void_p * max(1, n.value))()
-            if hip.hipGraphGetNodes(ctypes.c_void_p(raw), nodes, ctypes.byref(n)) != 0:
-                return False
-            kernels = other = 0
-            for i in range(n.value):
-                t = ctypes.c_int(-1)
-                if hip.hipGraphNodeGetType(ctypes.c_void_p(nodes[i]), ctypes.byref(t)) != 0:
-                    return False
-                kernels += t.value == 0          # hipGraphNodeTypeKernel
-                # (empty / event nodes carry no work: with every kernel node one of the
-                # list's launches, all recorded in order on the capturing stream, that
-                # order already holds the edges they stand for)
-                other += t.value not in (0, 5, 6, 7)   # ... Empty, WaitEvent, EventRecord
-            self.graph_nodes = (n.value - (n.value - kernels - other), kernels, n_launches)
-            return other == 0 and kernels == n_launches
-        except Exception:       # (no raw graph in this torch build, no HIP runtime handle)
-            return False
-
-    def replay_launches(self):
-        """The captured step re-issued launch by launch on the current stream instead of as a
-        graph replay (single-rank steps): no per-replay graph cost on the device, one C call
-        (a hipLaunchKernel per recorded launch) on the host."""
-        import ctypes
-        from . import _lib
-        _lib.call("scae_launch_list_run", self._klist, ctypes.c_void_p(
-            torch.cuda.current_stream(self.device).cuda_stream))
-
-    def _free_list(self):
-        if getattr(self, "_klist", None):
-            from . import _lib
-            _lib.load().scae_launch_list_free(self._klist)
-        self._klist = None
-
-    def __del__(self):
-        try:
-            self._free_list()
-            self._drop_forms()
-        except Exception:      # (interpreter shutdown)
-            pass
+    def _captured(self):
+        """What the step's (first) graph holds."""
+        self._part_a()
+        if not self.split:
+            self._part_b()
+            if not self.collective or self.in_graph_collective:
+                self._finish()
 
     def capture(self):
         """Build the step's HIP graph(s) now instead of at the first call
@@ -748,62 +663,16 @@ class TrainStep:
             self.opt.acc.zero_()
 
     def _refresh_prologue(self):
-        """Noise + folding products for the next forward (no batch)."""
-        if self._pro is not None:
-            with self.plan.active():
-                self._pro.launch(stream_ref=self.image)
+        _replay.refresh_prologue(self.plan, self._pro, self.image)
 
     def _stage(self, image, label):
-        """The batch into the resident input buffers: one launch when both
-        tensors already live on the device in the buffers' layout -- the
-        step's prologue launch when there is one."""
-        direct = image.is_cuda and label.is_cuda \
-            and image.dtype == self.image.dtype \
-            and label.dtype == self.label.dtype and image.is_contiguous() \
-            and label.is_contiguous() and image.shape == self.image.shape \
-            and label.shape == self.label.shape \
-            and image.device == self.device == label.device
-        if self._pro is not None:
-            if direct:
-                with self.plan.active():
-                    self._pro.launch(self.image, image, self.label, label)
-            else:
-                self.image.copy_(image, non_blocking=True)
-                self.label.copy_(label, non_blocking=True)
-                self._refresh_prologue()
-            return
-        if image.is_cuda and label.is_cuda and image.dtype == self.image.dtype \
-                and label.dtype == self.label.dtype and image.is_contiguous() \
-                and label.is_contiguous() and image.shape == self.image.shape \
-                and label.shape == self.label.shape \
-                and image.device == self.device == label.device:
-            import ctypes
-            from . import _lib
-            P = ctypes.c_void_p
-            _lib.call("scae_stage_batch", P(self.image.data_ptr()),
-                      P(image.data_ptr()), image.numel(),
-                      P(self.label.data_ptr()), P(label.data_ptr()),
-                      label.numel(),
-                      P(torch.cuda.current_stream(self.device).cuda_stream))
-            return
-        self.image.copy_(image, non_blocking=True)
-        self.label.copy_(label, non_blocking=True)
+        """The batch into the resident input buffers (replay.stage)."""
+        _replay.stage(self.plan, self._pro, self.image, self.label, image, label, self.device,
+                      stage_batch=True)
 
     def _stage_source(self, view, epoch, position):
-        """The batch at ``position`` of ``epoch`` gathered from a device-resident dataset
-        into the resident input buffers: the step's prologue launch, or the standalone
-        gather without a prologue."""
-        src = view.desc(epoch, position)
-        if self._pro is not None:
-            with self.plan.active():
-                self._pro.launch(self.image, None, self.label, source=src)
-            return
-        import ctypes
-        from . import _lib
-        P = ctypes.c_void_p
-        _lib.call("scae_gather_batch_f32", P(self.image.data_ptr()),
-                  P(self.label.data_ptr()), self.image.shape[0], ctypes.byref(src),
-                  P(torch.cuda.current_stream(self.device).cuda_stream))
+        """The view's batch at ``position`` of ``epoch`` gathered (replay.stage_source)."""
+        _replay.stage_source(self.plan, self._pro, self.image, self.label, view, epoch, position)
 
     def step_from(self, view):
         """One step on the next batch of ``view`` (data.DatasetView of a
@@ -870,8 +739,8 @@ class TrainStep:
                 self._run(self.graph.replay, self.graph_b.replay)
                 self._after_buckets()
             else:
-                if self.replay == "launches" and self._klist:
-                    self.replay_launches()
+                if self.replay == "launches":    # (a setting read per step: bench.py flips it)
+                    self._cap.replay(self.device)
                 else:
                     self.graph.replay()
                 if self.collective and not self.in_graph_collective:
