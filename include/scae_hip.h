@@ -1515,6 +1515,27 @@ int scae_render_gmm_sums_bwd_f32(const scae_decoder_desc *d, const float *x,
                                  const float *g_tile_sums, float *g_templates,
                                  float *g_alpha_partial, float *g_pose, float *g_presence,
                                  float *g_bg_image, float *g_scalar_partial, void *stream);
+/* Which kernel form the K1 entry points take for `d` (host only, launches nothing; the
+ * launchers' own predicates).  fused: the backward gets the gradient of log_prob or of its
+ * tile sums (scae_render_gmm_bwd_f32 without g_tt / g_ml, scae_render_gmm_sums_bwd_f32), not
+ * of the materialised tensors; tt / ml: the addresses scae_template_render_fwd_f32 would
+ * write (their alignment picks its form).
+ *   out[0] likelihood forward: SCAE_K1_FWD_*      out[1] its lanes per pixel (KSPLIT)
+ *   out[2] classic forward: 1 = zero-padded planes out[3] render: SCAE_K1_RENDER_*
+ *   out[4] backward: SCAE_K1_BWD_*                out[5] gather: image rows per pass
+ *   out[6] cell-gather: image rows per chunk      out[7] pixels per forward tile
+ *   out[8] cell-gather: (cell, row slice) items per workgroup (its budget)
+ *   out[9] cell-gather: item slots in LDS -- above the budget when the template has more
+ *          cells, (th + 1)(tw + 1), than the budget      out[10], out[11] 0 (reserved) */
+#define SCAE_K1_FWD_WAVE 0
+#define SCAE_K1_FWD_CLASSIC 1
+#define SCAE_K1_RENDER_WAVE 0
+#define SCAE_K1_RENDER_CLASSIC 1
+#define SCAE_K1_BWD_CELL 0
+#define SCAE_K1_BWD_SCATTER 1
+#define SCAE_K1_BWD_GATHER 2
+int scae_render_gmm_forms(const scae_decoder_desc *d, int fused, const void *tt,
+                          const void *ml, int out[12]);
 
 
 /* scae_set_encoder_fwd_f32 and scae_render_gmm_logprob_sums_fwd_f32 as ONE launch:

@@ -7,6 +7,7 @@ import torch
 
 from oracle import scae_oracle as O
 from tests.golden_util import assert_close, load, sub
+from tests.k1_ref import clear_of_cell_boundaries as _clear_of_cell_boundaries
 
 pytestmark = pytest.mark.gpu
 
@@ -492,37 +493,6 @@ def _unit_scale_inputs(B, M, g):
     pose[:, :, 0] += 1.0
     pose[:, :, 4] += 1.0
     return pose, torch.rand(B, M, generator=g)
-
-
-def _clear_of_cell_boundaries(pose, HW, ts, g, margin=8e-6):
-    """d log_prob / d pose jumps where a pixel's sample position crosses a
-    texel-cell boundary: a pixel within fp32 round-off of one has two valid
-    one-sided derivatives (the golden poses are
-    'irrational' for the same reason).  Round-off of a position is a few ulp
-    of ~10 texels, ~1e-6; capsules with a pixel within 8e-6 get their
-    translation nudged until none is left -- the regimes below draw thousands
-    of (capsule, pixel) pairs, the unit-scale test above keeps its round-1
-    draws."""
-    H, W = HW
-    th, tw = ts
-    xs = (2 * torch.arange(W, dtype=torch.float64) + 1) / W - 1
-    ys = (2 * torch.arange(H, dtype=torch.float64) + 1) / H - 1
-    gy, gx = torch.meshgrid(ys, xs, indexing="ij")
-    gx, gy = gx.reshape(-1), gy.reshape(-1)
-    pose = pose.clone()
-    for _ in range(60):
-        a = pose.double()[..., None]                       # (B, M, 6, 1)
-        ix = ((a[:, :, 0] * gx + a[:, :, 1] * gy + a[:, :, 2] + 1) * tw - 1) / 2
-        iy = ((a[:, :, 3] * gx + a[:, :, 4] * gy + a[:, :, 5] + 1) * th - 1) / 2
-        near = lambda v, n: ((v - v.round()).abs() < margin) \
-            & (v > -1.5) & (v < n + 0.5)                   # noqa: E731
-        bad = (near(ix, tw) | near(iy, th)).any(-1)        # (B, M)
-        if not bool(bad.any()):
-            return pose
-        nudge = torch.randn(pose.shape[0], pose.shape[1], 2, generator=g) * 2e-2
-        pose[..., 2] += torch.where(bad, nudge[..., 0], torch.zeros(()))
-        pose[..., 5] += torch.where(bad, nudge[..., 1], torch.zeros(()))
-    raise AssertionError("poses could not be cleared of cell boundaries")
 
 
 def _decoder_vs_oracle(B, M, C, HW, ts, alpha, scale, g, inputs=None,

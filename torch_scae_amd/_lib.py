@@ -390,6 +390,7 @@ SIGNATURES = {
     "scae_render_gmm_logprob_fwd_f32": [POINTER(DecoderDesc), P, P, P, P, P],
     "scae_render_gmm_bwd_f32": [POINTER(DecoderDesc)] + [P] * 12 + [P],
     "scae_render_gmm_logprob_tiles": [POINTER(DecoderDesc)],
+    "scae_render_gmm_forms": [POINTER(DecoderDesc), c_int, P, P, POINTER(c_int)],
     "scae_render_gmm_logprob_sums_fwd_f32": [POINTER(DecoderDesc)] + [P] * 4 + [P],
     "scae_render_gmm_sums_bwd_f32": [POINTER(DecoderDesc)] + [P] * 10 + [P],
     "scae_gmm_log_prob_fwd_f32": [P] * 5 + [c_int] * 4 + [c_int64, P],

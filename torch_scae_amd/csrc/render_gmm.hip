@@ -1094,17 +1094,26 @@ namespace scae_k1 {
 int check_decoder_desc(const scae_decoder_desc *d) { return check_desc(d); }
 }  // namespace scae_k1
 
+namespace {
+// the quad-store render (render_gmm_wave.hip) covers this shape and these addresses
+bool render_takes_wave(const scae_decoder_desc *d, const void *tt, const void *ml) {
+#ifndef SCAE_K1_NO_WAVE
+  return render_wave_lds(d) && (((size_t)tt | (size_t)ml) & 15) == 0 &&
+         (!d->bg_image || ((size_t)d->bg_image & 15) == 0);
+#else
+  return false;
+#endif
+}
+}  // namespace
+
 extern "C" int scae_template_render_fwd_f32(const scae_decoder_desc *d,
                                             float *transformed_templates,
                                             float *mixing_logits, void *stream) {
   int rc = check_desc(d);
   if (rc) return rc;
   SCAE_REQUIRE(transformed_templates && mixing_logits);
-#ifndef SCAE_K1_NO_WAVE
-  if (render_wave_lds(d) && (((size_t)transformed_templates | (size_t)mixing_logits) & 15) == 0 &&
-      (!d->bg_image || ((size_t)d->bg_image & 15) == 0))
+  if (render_takes_wave(d, transformed_templates, mixing_logits))
     return launch_render_wave(d, transformed_templates, mixing_logits, (hipStream_t)stream);
-#endif
   const size_t lds = sizeof(float) * (size_t)(d->C + 1) * pad_elems(d->th, d->tw);
   int rc2 = set_lds(render_fwd_kernel, lds);
   if (rc2) return rc2;
@@ -1161,18 +1170,60 @@ LpTiling lp_tiling(const scae_decoder_desc *d) {
 }  // namespace scae_k1
 
 namespace {
-template <int C>
-int launch_logprob_fwd(const scae_decoder_desc *d, const float *x, float *log_prob,
-                       float *lse_post, float *lse_prior, float *block_sums, hipStream_t st) {
+// the classic likelihood forward's planes: zero-padded (no tap masks) while two workgroups
+// still fit a CU's LDS; -> its dynamic LDS bytes
+struct LpPlanes {
+  bool pad;
+  size_t lds;
+};
+LpPlanes lp_planes(const scae_decoder_desc *d) {
   const size_t planes = (size_t)d->M * (d->C + (d->templates_alpha ? 1 : 0));
-  // zero-padded planes (no tap masks) while two workgroups still fit a CU's LDS
   const size_t lds_pad = sizeof(float) * (planes * pad_elems(d->th, d->tw) + (size_t)d->M * 7);
 #ifndef SCAE_LP_PAD_LIMIT_KB
 #define SCAE_LP_PAD_LIMIT_KB 72
 #endif
-  const bool pad = lds_pad <= (size_t)SCAE_LP_PAD_LIMIT_KB * 1024;
-  const size_t lds =
-      pad ? lds_pad : sizeof(float) * (planes * d->th * d->tw + (size_t)d->M * 7);
+  LpPlanes r;
+  r.pad = lds_pad <= (size_t)SCAE_LP_PAD_LIMIT_KB * 1024;
+  r.lds = r.pad ? lds_pad : sizeof(float) * (planes * d->th * d->tw + (size_t)d->M * 7);
+  return r;
+}
+
+// which backward kernel a call takes, and the LDS and row chunk it is launched with
+enum { BWD_CELL = 0, BWD_SCATTER = 1, BWD_GATHER = 2 };
+struct BwdForm {
+  int kind, rows;
+  bool fused;
+  size_t lds;
+};
+BwdForm bwd_form(const scae_decoder_desc *d, bool fused) {
+  const int tsz = d->th * d->tw;
+  BwdForm f;
+  // the scatter form needs a set of accumulator planes per 16-lane row beside >= 4
+  // workgroups per CU, and a 16-lane row that spans at most two image rows; else the gather
+  const size_t plane = (size_t)(d->C + 1) * pad_elems(d->th, d->tw);
+  const bool scatter = d->W >= 16 &&
+                       sizeof(float) * ((1 + NT / 16) * plane + 11 * (NT / 64)) <= 40 * 1024;
+  int rows = (int)((40 * 1024 / sizeof(float)) / ((size_t)(d->C + 1) * d->W));
+  rows = rows < 1 ? 1 : (rows > d->H ? d->H : rows);
+  f.rows = rows;
+  f.lds = scatter ? sizeof(float) * ((1 + NT / 16) * plane + 11 * (NT / 64))
+                  : sizeof(float) * ((size_t)(d->C + 1) * pad_elems(d->th, d->tw) +
+                                     SLICES * (size_t)(d->C + 1) * tsz + 11 * (NT / 64) +
+                                     (size_t)(d->C + 1) * rows * d->W);
+  f.fused = fused;
+  f.kind = scatter ? BWD_SCATTER : BWD_GATHER;
+#ifndef SCAE_K1_NO_CELL
+  if (f.fused && bwd_cell_lds(d)) f.kind = BWD_CELL;
+#endif
+  return f;
+}
+
+template <int C>
+int launch_logprob_fwd(const scae_decoder_desc *d, const float *x, float *log_prob,
+                       float *lse_post, float *lse_prior, float *block_sums, hipStream_t st) {
+  const LpPlanes pl = lp_planes(d);
+  const bool pad = pl.pad;
+  const size_t lds = pl.lds;
   const LpTiling t = lp_tiling(d);
   if (t.wave) return launch_logprob_wave(d, t, x, log_prob, lse_post, lse_prior, block_sums, st);
   const int ppb = t.ppb;
@@ -1207,28 +1258,16 @@ int launch_bwd(const scae_decoder_desc *d, const float *x, const float *lse_post
                const float *g_ml, float *g_templates, float *g_alpha_partial,
                float *g_pose, float *g_presence, float *g_bg_image,
                float *g_scalar_partial, const float *g_tile, hipStream_t st) {
-  const int tsz = d->th * d->tw;
   const LpTiling lt = lp_tiling(d);
-  // the scatter form needs a set of accumulator planes per 16-lane row beside >= 4
-  // workgroups per CU, and a 16-lane row that spans at most two image rows; else the gather
-  const size_t plane = (size_t)(d->C + 1) * pad_elems(d->th, d->tw);
-  const bool scatter = d->W >= 16 &&
-                       sizeof(float) * ((1 + NT / 16) * plane + 11 * (NT / 64)) <= 40 * 1024;
-  int rows = (int)((40 * 1024 / sizeof(float)) / ((size_t)(d->C + 1) * d->W));
-  rows = rows < 1 ? 1 : (rows > d->H ? d->H : rows);
-  const size_t lds =
-      scatter ? sizeof(float) * ((1 + NT / 16) * plane + 11 * (NT / 64))
-              : sizeof(float) * ((size_t)(d->C + 1) * pad_elems(d->th, d->tw) +
-                                 SLICES * (size_t)(d->C + 1) * tsz + 11 * (NT / 64) +
-                                 (size_t)(d->C + 1) * rows * d->W);
+  const BwdForm form = bwd_form(d, g_tt == nullptr && g_ml == nullptr);
+  const bool scatter = form.kind == BWD_SCATTER, fused = form.fused;
+  const int rows = form.rows;
+  const size_t lds = form.lds;
   const dim3 grid(d->M + 1, d->B);
-  const bool fused = (g_tt == nullptr && g_ml == nullptr);
-#ifndef SCAE_K1_NO_CELL
-  if (fused && bwd_cell_lds(d))
+  if (form.kind == BWD_CELL)
     return launch_bwd_cell(d, x, lse_post, lse_prior, g_logprob, g_tile, lt.tiles, lt.ppb,
                            g_templates, g_alpha_partial, g_pose, g_presence, g_bg_image,
                            g_scalar_partial, st);
-#endif
   int rc;
 #define SCAE_LAUNCH_BWD(KERNEL, FU)                                                          \
   rc = set_lds(KERNEL<C, FU>, lds);                                                          \
@@ -1331,6 +1370,35 @@ extern "C" int scae_render_gmm_bwd_f32(const scae_decoder_desc *d, const float *
                  nullptr, (hipStream_t)stream)
   SCAE_DISPATCH_C(d->C, CALL)
 #undef CALL
+}
+
+// Host only, launches nothing: the kernel forms the entry points above take for this
+// descriptor, from the launchers' own predicates.  `fused`: the backward is asked for the
+// gradient of log_prob (or of its tile sums), not of the materialised tensors; tt / ml: the
+// render's output addresses (their alignment picks its form).
+extern "C" int scae_render_gmm_forms(const scae_decoder_desc *d, int fused, const void *tt,
+                                     const void *ml, int out[12]) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  SCAE_REQUIRE(out);
+  const LpTiling t = lp_tiling(d);
+  const LpPlanes pl = lp_planes(d);
+  out[0] = t.wave ? SCAE_K1_FWD_WAVE : SCAE_K1_FWD_CLASSIC;
+  out[1] = t.ksplit;
+  out[2] = t.wave ? 0 : (pl.pad ? 1 : 0);
+  out[3] = render_takes_wave(d, tt, ml) ? SCAE_K1_RENDER_WAVE : SCAE_K1_RENDER_CLASSIC;
+  const BwdForm f = bwd_form(d, fused != 0);
+  out[4] = f.kind == BWD_CELL ? SCAE_K1_BWD_CELL
+                              : (f.kind == BWD_SCATTER ? SCAE_K1_BWD_SCATTER : SCAE_K1_BWD_GATHER);
+  out[5] = f.kind == BWD_GATHER ? f.rows : 0;
+  int cg[3] = {0, 0, 0};
+  if (f.kind == BWD_CELL) bwd_cell_geom(d, cg);
+  out[6] = cg[0];
+  out[7] = t.ppb;
+  out[8] = cg[1];
+  out[9] = cg[2];
+  out[10] = out[11] = 0;
+  return SCAE_OK;
 }
 
 namespace {

@@ -130,6 +130,8 @@ int launch_render_wave(const scae_decoder_desc *d, float *tt, float *ml, hipStre
 // gradient of the per-pixel log-prob or of its tile sums).  bwd_cell_lds: LDS bytes, 0 when
 // the shape is not covered (the caller falls back to render_gmm.hip's kernels).
 size_t bwd_cell_lds(const scae_decoder_desc *d);
+// {image rows per chunk of parked records, (cell, row slice) item budget, item slots in LDS}
+void bwd_cell_geom(const scae_decoder_desc *d, int out[3]);
 int launch_bwd_cell(const scae_decoder_desc *d, const float *x, const float *lse_post,
                     const float *lse_prior, const float *g_logprob, const float *g_tile,
                     int lp_tiles, int lp_ppb, float *g_templates, float *g_alpha_partial,

@@ -239,6 +239,10 @@ int launch_render_wave(const scae_decoder_desc *d, float *tt, float *ml, hipStre
 }
 
 size_t bwd_cell_lds(const scae_decoder_desc *d) { return cell_geom(d).lds; }
+void bwd_cell_geom(const scae_decoder_desc *d, int out[3]) {
+  const CellGeom g = cell_geom(d);
+  out[0] = g.chunk_rows, out[1] = g.item_budget, out[2] = g.max_items;
+}
 
 int launch_bwd_cell(const scae_decoder_desc *d, const float *x, const float *lse_post,
                     const float *lse_prior, const float *g_logprob, const float *g_tile,
