@@ -875,6 +875,41 @@ int scae_flat_opt_acc_clip_step_f32(float *param, const float *grad, float *acc,
                                     int advance, const double *partials, int n_partials,
                                     float max_norm, float *norm_out, void *stream);
 
+/* Per-parameter gradient norms -- Lightning's Trainer(track_grad_norm=p): one p-norm per
+ * segment of a flat buffer, and their total, as one row of a device ring.
+ *   A segment is a run of elements [offset, offset + length) of src[0, n), length >= 1;
+ *   segments are disjoint and ascending and need not tile the buffer.  Segment s yields
+ *   scale * || x ||_p over its elements, x = src or (acc != NULL) acc + src (one fp32 add, as
+ *   the accumulate forms above):  p = 2: exact fp64 squares summed in fp64, then sqrt;  p = 1:
+ *   the fp64 sum of |x|;  p = inf: max |x| (NaN if any element is NaN, as
+ *   torch.linalg.vector_norm); rounded once to fp32.  row[n_segs]: the p-norm of the segment
+ *   values, formed in fp64 from their unrounded fp64 values.
+ * The caller cuts the segments into chunks once per segment table (a chunk: at most
+ * SCAE_NORM_CHUNK elements of ONE segment, chunks ascending) and packs consecutive chunks
+ * into groups, one workgroup each (at most SCAE_NORM_GROUP_CHUNKS chunks and
+ * 4 * SCAE_NORM_CHUNK elements, unless a single chunk):
+ *   chunks      (n_chunks, 2) int32 device: first element, length;
+ *   group_first (n_groups + 1) int32 device: the groups' first chunks, then n_chunks;
+ *   seg_first   (n_segs + 1) int32 device: the segments' first chunks, then n_chunks.
+ * Two launches: every chunk's fp64 partial into `partials` (n_chunks doubles; a wave per
+ * chunk, a chunk outside [0, n) yields NaN and reads nothing), then one workgroup that
+ * reduces each segment's partials in chunk order and writes the row
+ *   ring + (*cursor % capacity) * (n_segs + 1)
+ * and then advances *cursor (device int64: a replayed launch writes successive rows); cursor
+ * NULL: row 0.  No atomics and no arrival counter; every order of summation is a function of
+ * the tables and of src's phase in a 16-byte line, so two runs give the same bits.  A
+ * non-finite element changes its own segment's value and the total only.
+ * acc: n floats at src's phase in a 16-byte line.  scale >= 0.  n < 2^31. */
+#define SCAE_NORM_CHUNK 2048
+#define SCAE_NORM_GROUP_CHUNKS 16
+#define SCAE_NORM_INF 0 /* norm_kind: 1, 2 or this */
+int scae_segment_norms_chunk(void); /* SCAE_NORM_CHUNK of this build */
+int scae_segment_norms_f32(const float *src, const float *acc, int64_t n, const int32_t *chunks,
+                           int n_chunks, const int32_t *group_first, int n_groups,
+                           const int32_t *seg_first, int n_segs, int norm_kind, float scale,
+                           double *partials, float *ring, int64_t *cursor, int capacity,
+                           void *stream);
+
 /* The batch hand-over of a training step (base_experiment.py:109-112): n_image
  * floats and n_label int64 labels (device memory) into the step's resident
  * input buffers, in one launch. */

@@ -324,6 +324,10 @@ SIGNATURES = {
     "scae_flat_opt_acc_clip_step_f32": [P, P, P, P, P, P, c_int64, P, P, c_int, c_double,
                                         c_double, c_float, c_float, c_float, c_int, c_float,
                                         c_int, P, c_int, c_float, P, P],
+    # per-segment norms of a flat buffer into a device ring (grad_norms.hip)
+    "scae_segment_norms_chunk": [],
+    "scae_segment_norms_f32": [P, P, c_int64, P, c_int, P, c_int, P, c_int, c_int, c_float,
+                               P, P, P, c_int, P],
     "scae_capsule_head_fwd_f32": [P, P, c_float, c_int, P, P, P, P, P] + [c_int] * 4 + [P],
     "scae_capsule_head_conv_supported": [c_int] * 4,
     "scae_capsule_head_conv_preferred": [c_int] * 5,
@@ -418,6 +422,9 @@ EVAL_RECORD_FLOATS = 9       # SCAE_EVAL_RECORD_FLOATS: one row of scae_eval_rec
 EVAL_RECORDS_MAX_CLASSES = 64   # SCAE_EVAL_RECORDS_MAX_CLASSES
 FLAT_OPT_STATE_INTS = 2112   # SCAE_FLAT_OPT_STATE_INTS: the step_state of scae_flat_opt_*
 GRAD_SQ_MAX_PARTIALS = 4096  # SCAE_GRAD_SQ_MAX_PARTIALS: scae_grad_sq_partials_*
+NORM_CHUNK = 2048            # SCAE_NORM_CHUNK: elements per chunk of scae_segment_norms_f32
+NORM_GROUP_CHUNKS = 16       # SCAE_NORM_GROUP_CHUNKS: chunks per workgroup, at most
+NORM_INF = 0                 # SCAE_NORM_INF: scae_segment_norms_f32's norm_kind for p = inf
 ABI_VERSION = 3     # SCAE_ABI_VERSION of the include/scae_hip.h this binding mirrors
 
 _lib = None

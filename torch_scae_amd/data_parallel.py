@@ -343,6 +343,7 @@ class RMSpropFlat(_Accumulating):
                                  dtype=flat.flat_param.dtype)
         _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
         _init_clip(self, gradient_clip_val)
+        _init_track(self)
         _init_accumulate(self, accumulate_grad_batches)
 
     def set_lr(self, lr):
@@ -364,6 +365,7 @@ class RMSpropFlat(_Accumulating):
         (``acc``, unless ``with_acc`` is False): the gradient is acc + g, and acc is 0
         afterwards."""
         acc = self.acc if with_acc else None
+        sum_units = _track_first(self, grad_scale, sum_units, acc)
         if self.look_ahead_k:     # (the fused form that counts steps)
             _fused_step(self, self.buf, self.square_avg,
                         (self.momentum, self.alpha), grad_scale, sum_units,
@@ -476,6 +478,7 @@ class RMSpropFlat(_Accumulating):
         P = ctypes.c_void_p
         st = P(torch.cuda.current_stream(g.device).cuda_stream)
         n_partials = _launch_norm(self, g, sum_units, st, acc)
+        _track_after_norm(self, grad_scale, acc)
         for i, (off, n) in enumerate(ranges):
             ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
             name, a = ("scae_rmsprop_clip_step_f32", ()) if acc is None else \
@@ -554,6 +557,217 @@ def _init_clip(opt, gradient_clip_val):
         from ._lib import GRAD_SQ_MAX_PARTIALS
         opt.grad_sq = torch.zeros(GRAD_SQ_MAX_PARTIALS, dtype=torch.float64, device=dev)
         opt.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+
+
+def track_value(v):
+    """``track_grad_norm`` as Lightning's Trainer reads it: 1, 2, ``float('inf')`` or ``'inf'``
+    -> the norm's p as a float; None, -1 or 0 -> None (off, Lightning's default -1); a bool,
+    another string or any other number is an error."""
+    if v is None:
+        return None
+    if isinstance(v, str):
+        if v == "inf":
+            return math.inf
+    elif not isinstance(v, bool) and isinstance(v, numbers.Real):
+        v = float(v)
+        if v in (-1.0, 0.0):
+            return None
+        if v in (1.0, 2.0, math.inf):
+            return v
+    raise ValueError(f"track_grad_norm must be 1, 2 or 'inf' (None, -1 or 0: off), got {v!r}")
+
+
+def norm_segments(flat, model, split_capsules=True, seen=None):
+    """[(key, offset, length)]: the segments of ``flat``'s buffers whose norms are tracked, in
+    flat order -- the parameters that received a gradient (``seen``: a flag per parameter of
+    ``flat.params``; default: in the last backward), keyed by their ``model.state_dict()``
+    names.  ``split_capsules``: a ``nn_ext.GroupedMLP`` stacked parameter gives one segment per
+    capsule slice under the reference's per-capsule key (the mapping of
+    ``GroupedMLP._save_to_state_dict``); else one segment under the stacked parameter's own
+    name."""
+    from .nn_ext import GroupedMLP
+    names, slices = {}, {}
+    for name, p in model.named_parameters():
+        names.setdefault(id(p), name)
+    if split_capsules:
+        for mod_name, mod in model.named_modules():
+            if not isinstance(mod, GroupedMLP):
+                continue
+            prefix = mod_name + "." if mod_name else ""
+            for j in range(mod.n_layers):
+                for kind, stacked in (("weight", mod.weights[j]),
+                                      ("bias", mod.biases[j] if mod.has_bias else None)):
+                    if stacked is not None:
+                        slices[id(stacked)] = [f"{prefix}{g}.{2 * j}.{kind}"
+                                               for g in range(mod.n_groups)]
+    if seen is None:
+        seen = [getattr(p, "_flat_was_set", True) for p in flat.params]
+    out = []
+    for p, off, s in zip(flat.params, flat.offsets, seen):
+        n = p.numel()
+        if not s or n == 0:
+            continue
+        keys = slices.get(id(p))
+        if keys is None:
+            out.append((names[id(p)], off, n))
+            continue
+        per = n // len(keys)
+        out.extend((key, off + g * per, per) for g, key in enumerate(keys))
+    return out
+
+
+def norm_chunk_table(segments, n, chunk=None, group_chunks=None):
+    """The work division of scae_segment_norms_f32 for ``segments`` [(offset, length)] of a
+    buffer of ``n`` elements -> (chunks, group_first, seg_first): chunks [(first element,
+    length)] of at most ``chunk`` elements of one segment each, ascending; ``group_first``: the
+    first chunk of every workgroup's run of chunks (at most ``group_chunks`` chunks and four
+    chunks' worth of elements: small segments share a workgroup), then the chunk count;
+    ``seg_first``: every segment's first chunk, then the chunk count.  Segments must be
+    ascending, disjoint, non-empty and inside [0, n)."""
+    from ._lib import NORM_CHUNK, NORM_GROUP_CHUNKS
+    chunk = NORM_CHUNK if chunk is None else int(chunk)
+    group_chunks = NORM_GROUP_CHUNKS if group_chunks is None else int(group_chunks)
+    chunks, seg_first, end = [], [], 0
+    for off, length in segments:
+        off, length = int(off), int(length)
+        if length < 1 or off < end or off + length > n:
+            raise ValueError(f"segment ({off}, {length}) is empty, overlaps the one before it or "
+                             f"leaves the buffer of {n} elements")
+        end = off + length
+        seg_first.append(len(chunks))
+        chunks.extend((b, min(chunk, end - b)) for b in range(off, end, chunk))
+    if not chunks:
+        raise ValueError("no segments")
+    seg_first.append(len(chunks))
+    group_first, load, count = [0], 0, 0
+    for i, (_, length) in enumerate(chunks):
+        if count and (count >= group_chunks or load + length > 4 * chunk):
+            group_first.append(i)
+            load = count = 0
+        load, count = load + length, count + 1
+    group_first.append(len(chunks))
+    return chunks, group_first, seg_first
+
+
+def segment_norms_host(x, segments, p, scale=1.0):
+    """The row scae_segment_norms_f32 writes, in torch on the host: fp32 (len(segments) + 1) of
+    fp32(scale) * ||x[offset:offset + length]||_p per segment [(offset, length)], taken in fp64,
+    then the p-norm of those (fp64, before rounding).  The CPU form of a tracking step and
+    the tests' yardstick."""
+    x = x.detach().double()
+    vals = [torch.linalg.vector_norm(x[off:off + n], p) for off, n in segments]
+    vals.append(torch.linalg.vector_norm(torch.stack(vals), p) if vals else x.new_zeros(()))
+    scale = float(torch.tensor(float(scale), dtype=torch.float32))
+    return (torch.stack(vals) * scale).float()
+
+
+class GradNorms:
+    """Per-parameter norms of the gradient an optimiser step consumes (Lightning's
+    ``Trainer(track_grad_norm=p)``): one row per optimiser step -- a norm per segment
+    (``norm_segments``), then the total -- in a device ring of ``capacity`` rows whose cursor
+    the launch itself advances (scae_segment_norms_f32; on CPU tensors ``segment_norms_host``).
+    The segment table is fixed by the first ``build``: after a backward, outside any capture.
+    ``count``: the host's mirror of the cursor (the step that owns the optimiser counts)."""
+
+    def __init__(self, flat, model, p, capacity=1, split_capsules=True):
+        self.flat, self.model, self.p = flat, model, float(p)
+        self.capacity = max(1, int(capacity))
+        self.split_capsules = bool(split_capsules)
+        self.segments = None
+        self.ring = self.cursor = self.partials = self.tables = None
+        self.count = 0
+
+    def build(self, seen=None):
+        if self.segments is not None:
+            return
+        flat = self.flat
+        segs = norm_segments(flat, self.model, self.split_capsules, seen)
+        if not segs:
+            raise ValueError("no parameter received a gradient: nothing to track")
+        dev = flat.flat_grad.device
+        self.ring = torch.zeros(self.capacity, len(segs) + 1, device=dev)
+        self.cursor = torch.zeros(1, dtype=torch.int64, device=dev)
+        if dev.type == "cuda":
+            chunks, group_first, seg_first = norm_chunk_table(
+                [(off, n) for _, off, n in segs], flat.numel)
+            self.tables = tuple(torch.tensor(t, dtype=torch.int32).to(dev)
+                                for t in (chunks, group_first, seg_first))
+            self.partials = torch.zeros(len(chunks), dtype=torch.float64, device=dev)
+        self.segments = segs
+
+    def names(self, prefix=""):
+        return [f"grad_{self.p}_norm_{prefix}{key}" for key, _, _ in self.segments] + \
+            [f"grad_{self.p}_norm_total"]
+
+    @torch.no_grad()
+    def launch(self, x, acc, scale, p=None, into=None):
+        """One row of the norms of ``x`` (or ``acc + x``), scaled.  ``into``: a (1, n + 1) row
+        of the caller's instead of the ring's next one (the cursor stays)."""
+        p = self.p if p is None else p
+        ring, cursor = (self.ring, self.cursor) if into is None else (into, None)
+        if not x.is_cuda:
+            if acc is not None:
+                x = acc + x
+            row = segment_norms_host(x, [(off, n) for _, off, n in self.segments], p, scale)
+            if cursor is None:
+                ring[0].copy_(row)
+            else:
+                ring[int(cursor) % self.capacity].copy_(row)
+                cursor += 1
+            return
+        from . import _lib
+        P = ctypes.c_void_p
+        chunks, group_first, seg_first = self.tables
+        partials = self.partials if into is None else torch.empty_like(self.partials)
+        _lib.call("scae_segment_norms_f32", P(x.data_ptr()),
+                  None if acc is None else P(acc.data_ptr()), x.numel(),
+                  P(chunks.data_ptr()), chunks.shape[0], P(group_first.data_ptr()),
+                  group_first.numel() - 1, P(seg_first.data_ptr()), len(self.segments),
+                  _lib.NORM_INF if math.isinf(p) else int(p), float(scale),
+                  P(partials.data_ptr()), P(ring.data_ptr()),
+                  None if cursor is None else P(cursor.data_ptr()),
+                  self.capacity if into is None else 1,
+                  P(torch.cuda.current_stream(x.device).cuda_stream))
+
+    def last(self):
+        """The newest row (a device view, no read); None before the first one."""
+        return None if self.count == 0 else self.ring[(self.count - 1) % self.capacity]
+
+
+def _init_track(opt):
+    """``opt.track``: the ``GradNorms`` of a step that tracks (train_step.TrainStep attaches
+    it), else None."""
+    opt.track = None
+
+
+def _track_first(opt, grad_scale, sum_units, acc):
+    """A tracking optimiser's step, before its pass: the norms of the gradient the pass
+    consumes.  The flat gradient is complete only once the step's last column sums
+    (``sum_units``) have run, so they are launched on their own here -- the same bits as riding
+    in the pass -- and the norms after them; -> the units still to launch.  A clipping step on
+    the device keeps them: they ride in its norm launch, and the norms follow that
+    (``_track_after_norm``)."""
+    trk = opt.track
+    if trk is None:
+        return sum_units
+    g = opt.flat.flat_grad
+    if g.is_cuda and opt.max_norm:
+        return sum_units
+    if sum_units:
+        from . import ops
+        ops._launch_sum_units(sum_units)
+    trk.build(_group_seen(opt))
+    trk.launch(g, acc, grad_scale)
+    return None
+
+
+def _track_after_norm(opt, grad_scale, acc):
+    """... of a clipping step on the device: after the clip's norm launch, which hosts the
+    column sums, and before the pass (whose accumulate form clears acc)."""
+    trk = opt.track
+    if trk is not None:
+        trk.build(_group_seen(opt))
+        trk.launch(opt.flat.flat_grad, acc, grad_scale)
 
 
 def _launch_norm(opt, g, sum_units, st, acc=None):
@@ -666,6 +880,7 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update, acc=None):
                   opt.kind, float(betas[0]), float(betas[1]), float(opt.eps))
         if clip:     # the norm launch (the column sums ride in it), then the clip forms
             n_partials = _launch_norm(opt, g, sum_units, st, acc)
+            _track_after_norm(opt, grad_scale, acc)
             for i, (off, n) in enumerate(ranges):
                 ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
                 _lib.call(f"scae_flat_opt{A}_clip_step_f32", ptr(flat.flat_param), ptr(g),
@@ -747,6 +962,7 @@ class _FlatAdamBase(_Accumulating):
                                  dtype=flat.flat_param.dtype)
         _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
         _init_clip(self, gradient_clip_val)
+        _init_track(self)
         _init_accumulate(self, accumulate_grad_batches)
 
     def set_lr(self, lr):
@@ -761,8 +977,10 @@ class _FlatAdamBase(_Accumulating):
         """As ``RMSpropFlat.step``: ``grad_scale`` multiplies the gradient on
         the fly, ``sum_units`` ride in the launch (scae_flat_opt_sums_step_f32);
         accumulating, the gradient is acc + g and acc is 0 afterwards."""
+        acc = self.acc if with_acc else None
+        sum_units = _track_first(self, grad_scale, sum_units, acc)
         _fused_step(self, self.exp_avg, self.exp_avg_sq, self.betas, grad_scale,
-                    sum_units, self._cpu_update, self.acc if with_acc else None)
+                    sum_units, self._cpu_update, acc)
 
     def state_buffers(self):
         """(torch.optim's state key, flat buffer) pairs."""

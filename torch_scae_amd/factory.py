@@ -168,11 +168,12 @@ def make_train_step(model, cfg: dict, **kw):
     ``Trainer(**cfg.trainer)`` of train.py:40: clipping by global norm, off
     when absent or <= 0; a non-numeric or non-finite value raises ValueError) and
     ``trainer.accumulate_grad_batches`` (gradient accumulation over that many batches: 1 when
-    absent; anything but an int >= 1 raises ValueError).  The reference reads LookAhead's k and alpha from
+    absent; anything but an int >= 1 raises ValueError) and ``trainer.track_grad_norm`` (per-parameter
+    gradient norms: 1, 2 or 'inf'; off when absent, -1 or 0; anything else raises ValueError).  The reference reads LookAhead's k and alpha from
     ``cfg.optimizer``, where none of its yaml files defines them
     (base_experiment.py:67-70); they are read from ``meta_optimizer`` here,
     where config.yaml puts them.  ``kw``: further TrainStep arguments."""
-    from .data_parallel import accumulate_value, clip_value
+    from .data_parallel import accumulate_value, clip_value, track_value
     from .train_step import TrainStep
     opt = cfg["optimizer"]
     kind = _OPTIMIZERS.get(opt["type"])
@@ -197,5 +198,8 @@ def make_train_step(model, cfg: dict, **kw):
     k = trainer.get("accumulate_grad_batches")
     if k is not None:
         args["accumulate_grad_batches"] = accumulate_value(k)
+    track = trainer.get("track_grad_norm")
+    if track is not None:
+        args["track_grad_norm"] = track_value(track)
     args.update(kw)
     return TrainStep(model, int(cfg["data_loader"]["batch_size"]), shape, **args)

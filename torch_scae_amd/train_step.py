@@ -13,9 +13,10 @@ import torch
 
 from . import ops
 from . import replay as _replay   # (``replay`` is the steps' constructor argument)
-from .data_parallel import (FlatParameters, accumulate_value, all_reduce_gradients,
-                            broadcast_parameters, clip_value, load_optimizer_state_dict,
-                            make_optimizer, optimizer_state_dict, world)
+from .data_parallel import (FlatParameters, GradNorms, _group_seen, accumulate_value,
+                            all_reduce_gradients, broadcast_parameters, clip_value,
+                            load_optimizer_state_dict, make_optimizer, optimizer_state_dict,
+                            segment_norms_host, track_value, world)
 
 
 # the remainder step's noise generators: keyed by torch's seed XOR this (step_plan.StepPlan.
@@ -109,6 +110,28 @@ class TrainStep:
     of its own (captured on first use).  With a collective: no all-reduce until the group's
     last batch, then one of the accumulated gradient.  ``steps`` counts batches,
     ``optimizer_steps`` optimiser steps; k = 1 (the default) is the step as it was.
+
+    ``track_grad_norm`` (p): Lightning's ``Trainer(track_grad_norm=p)`` -- 1, 2, ``float('inf')``
+    or ``'inf'``; None, -1 or 0 (the default, Lightning's -1) is off, and then every captured
+    form has exactly the launches it has without the argument.  Every OPTIMISER step (not
+    every batch: the batches inside an accumulated group write nothing) leaves one row in a
+    device ring of ``log_steps`` rows (1 without a log): the p-norm of the gradient the
+    optimiser consumes -- after the all-reduce, with the scale the optimiser pass applies
+    (1/k, 1/world), before clipping: what ``p.grad.norm(p)`` is in Lightning between backward
+    and ``clip_grad_norm_`` -- per parameter that received a gradient, in ``FlatParameters``
+    order (``obj_decoder.dummy_vote`` and ``posterior_classifier.*`` are absent from the default
+    model, as Lightning skips ``p.grad is None``), then the p-norm of those.  ``split_capsules``
+    (default True): a ``nn_ext.GroupedMLP`` stacked parameter is reported as one entry per
+    capsule under the reference's per-capsule ``state_dict`` key -- which object capsules have
+    stopped learning --; False: one entry per stacked tensor.  The segment table is fixed at
+    the first capture (eager: the first optimiser step).  Two launches more per optimiser step
+    (scae_segment_norms_f32: the chunks' fp64 partials, then the row; the cursor advances on
+    the device, so a graph and a launch list replay into successive rows), after the step's
+    last column sums: those no longer ride in the optimiser pass but launch on their own (with
+    clipping they ride in its norm launch as before) -- the same bits either way, and the
+    trained state equals the untracked step's bit for bit.  ``grad_norm_names()``,
+    ``last_grad_norms()``, ``grad_norm_history()``; ``parameter_norms()`` for the weights'.  The
+    remainder step and ``end_epoch``'s step on a pending group write to the same ring.
     """
 
     MODES = ("2 buckets", "1 bucket", "in graph")
@@ -120,12 +143,17 @@ class TrainStep:
                  prologue=True, fuse_kernels=True, collective_mode=None,
                  replay="graph", betas=(0.9, 0.999),
                  look_ahead=False, look_ahead_k=5, look_ahead_alpha=0.5,
-                 log_steps=0, gradient_clip_val=0.0, accumulate_grad_batches=1):
+                 log_steps=0, gradient_clip_val=0.0, accumulate_grad_batches=1,
+                 track_grad_norm=None, split_capsules=True):
         if not isinstance(log_steps, int) or isinstance(log_steps, bool) or log_steps < 0:
             raise ValueError(f"log_steps must be an int >= 0, got {log_steps!r}")
         gradient_clip_val = clip_value(gradient_clip_val)
         if gradient_clip_val and optimizer in (None, False):
             raise ValueError("gradient_clip_val needs an optimizer: clipping is part of its step")
+        track_grad_norm = track_value(track_grad_norm)
+        if track_grad_norm is not None and optimizer in (None, False):
+            raise ValueError("track_grad_norm needs an optimizer: the norms are those of the "
+                             "gradient its step consumes")
         self.accumulate_grad_batches = accumulate_value(accumulate_grad_batches)
         if self.accumulate_grad_batches > 1 and optimizer in (None, False):
             raise ValueError("accumulate_grad_batches needs an optimizer: it steps once a group")
@@ -200,6 +228,11 @@ class TrainStep:
             look_ahead_alpha=look_ahead_alpha, gradient_clip_val=gradient_clip_val,
             accumulate_grad_batches=self.accumulate_grad_batches) \
             if optimizer not in (None, False) else None
+        # the tracked gradient norms (data_parallel.GradNorms): on the optimiser, whose step
+        # launches them -- the remainder step shares both
+        if track_grad_norm is not None:
+            self.opt.track = GradNorms(self.flat, model, track_grad_norm,
+                                       capacity=log_steps or 1, split_capsules=split_capsules)
         self.steps = 0           # steps taken (host count, with the remainder step's; the
         #                          optimisers keep their own)
         # the training log (ops.TrainLog): ring, step counter, epoch accumulator
@@ -541,6 +574,10 @@ class TrainStep:
             finally:
                 self._warming = False
             self._refresh_prologue()    # what the capture below consumes
+            if self.grad_norms is not None:
+                # the segment table goes to the device here: the warm-ups have shown which
+                # parameters receive a gradient, and the capture below cannot copy
+                self.grad_norms.build(_group_seen(self.opt))
         torch.cuda.current_stream().wait_stream(s)
         # capture on the SAME stream the warm-up ran on: autograd caches each
         # parameter's AccumulateGrad node together with its stream
@@ -730,6 +767,8 @@ class TrainStep:
         elif self.opt is not None:
             acc["pending"] = 0
             acc["optimizer_steps"] += 1
+            if self.grad_norms is not None:
+                self.grad_norms.count += 1   # (the row this optimiser step wrote)
         return self.loss
 
     def _step_form(self):
@@ -765,11 +804,77 @@ class TrainStep:
         return dict(loss=loss, log=step.log)
 
     def last_grad_norm(self):
-        """The last step's total gradient norm before clipping (what Lightning's
-        ``track_grad_norm`` reports): a device scalar the next step overwrites, no read.  None
-        when the step does not clip."""
+        """The last step's total gradient L2 norm before clipping (the total that Lightning's
+        ``track_grad_norm=2`` reports): a device scalar the next step overwrites, no read.  A
+        step that clips returns the clip's own norm; one that only tracks with p = 2 the
+        tracked total (None before its first optimiser step); None otherwise."""
         opt = self.opt
-        return None if opt is None or not opt.max_norm else opt.grad_norm
+        if opt is None:
+            return None
+        if opt.max_norm:
+            return opt.grad_norm
+        if opt.track is not None and opt.track.p == 2.0:
+            row = opt.track.last()
+            return None if row is None else row[-1]
+        return None
+
+    # -- tracked gradient norms (track_grad_norm) ---------------------------------------------
+    @property
+    def grad_norms(self):
+        """The step's ``data_parallel.GradNorms`` (None: not tracking)."""
+        return None if self.opt is None else self.opt.track
+
+    def _need_norms(self, built=True):
+        trk = self.grad_norms
+        if trk is None:
+            raise ValueError("this step tracks no gradient norms (TrainStep(track_grad_norm=...))")
+        if built and trk.segments is None:
+            raise ValueError("the tracked segments are fixed by the first capture or optimiser "
+                             "step: take a step (or capture()) first")
+        return trk
+
+    def grad_norm_names(self, prefix=""):
+        """The names of a row's entries: ``f"grad_{float(p)}_norm_{prefix}{key}"`` per tracked
+        segment (key: the parameter's ``state_dict`` name, per capsule with
+        ``split_capsules``), then ``f"grad_{float(p)}_norm_total"``.  Modelled on the
+        ``grad_norm`` dict of Lightning 0.9's ``track_grad_norm``; the spelling is this
+        library's and has not been checked against Lightning, and Lightning's rounding of the
+        values to 3 decimals is not reproduced."""
+        return self._need_norms().names(prefix)
+
+    def last_grad_norms(self):
+        """The newest row -- the tracked norms of the last optimiser step, in
+        ``grad_norm_names()`` order -- as a device view (a later step overwrites it once the
+        ring wraps), no read.  None before the first optimiser step."""
+        return self._need_norms(built=False).last()
+
+    def grad_norm_history(self, prefix=""):
+        """-> ({name: host tensor (n,)}, optimiser steps): the last n = min(optimiser steps,
+        capacity) rows in step order and those steps' numbers (0-based).  One read of the
+        ring."""
+        trk = self._need_norms(built=False)
+        slots, steps = ops.ring_order(trk.count, trk.capacity)
+        if not slots:
+            return {}, []
+        rows = trk.ring.cpu()[slots]
+        return {k: rows[:, i] for i, k in enumerate(trk.names(prefix))}, steps
+
+    @torch.no_grad()
+    def parameter_norms(self, p=2):
+        """The p-norms of the parameters over the tracked segments (``grad_norm_names()``
+        order, then the total): one eager call of the gradient norms' kernel on the flat
+        parameter buffer -> a fresh device row.  With ``last_grad_norms()`` (times the learning
+        rate) it gives the update-to-weight ratio."""
+        p = track_value(p)
+        if p is None:
+            raise ValueError("parameter_norms needs p = 1, 2 or inf")
+        trk = self._need_norms()
+        w = self.flat.flat_param
+        if not w.is_cuda:
+            return segment_norms_host(w, [(off, n) for _, off, n in trk.segments], p)
+        row = torch.empty(1, len(trk.segments) + 1, device=w.device)
+        trk.launch(w, None, 1.0, p=p, into=row)
+        return row[0]
 
     # -- the training log (log_steps) ---------------------------------------------
     def _need_log(self):
@@ -835,5 +940,7 @@ class TrainStep:
                 self.opt.flush(scale)
             acc["pending"] = 0
             acc["optimizer_steps"] += 1
+            if self.grad_norms is not None:
+                self.grad_norms.count += 1
         if self.opt is not None and self.lr_decay_rate:
             self.opt.decay_lr(self.lr_decay_rate)
