@@ -1776,6 +1776,63 @@ int scae_probe_predict_f32(const float *x, int64_t N, int F, int C, const float 
                            const float *bias, const int64_t *y, int64_t *pred, float *log_prob,
                            double *part_ce, double *mean_ce, void *stream);
 
+/* ------------------------------------------------------------------------
+ * t-SNE (csrc/tsne.hip): exact 2-D t-SNE of x (N, F) -- dense joint affinities P (N, N) from a
+ * per-row bandwidth search, then gradient iterations with gains and momentum.  No float
+ * atomics, every sum in a fixed order: two runs give the same bits.
+ *   d_ij = sum_f (x_if - x_jf)^2 in f order.  For j != i p_{j|i} = e_j / S with
+ *   e_j = exp(-beta_i (d_ij - min_{k != i} d_ik)), S = sum_j e_j; beta_i by bisection on
+ *   H = log S + beta sum_j (d e) / S from beta = 1, both bounds open (double / halve while the
+ *   side is open, else the midpoint), until |H - log(perplexity)| <= 1e-5 or 100 evaluations.
+ *   P_ij = (p_{j|i} + p_{i|j}) / (2 N), P_ii = 0: symmetric bit for bit.
+ *   q_ij = 1 / (1 + |y_i - y_j|^2), q_ii = 0; Z = sum q (fp64 over the rows' sums);
+ *   g_i = 4 (exaggeration sum_j P_ij q_ij (y_i - y_j) - (1/Z) sum_j q_ij^2 (y_i - y_j));
+ *   per coordinate gain = max(g velocity < 0 ? gain + 0.2 : gain * 0.8, 0.01),
+ *   velocity = momentum velocity - learning_rate gain g, y += velocity; then Y loses its column
+ *   means (fp64 sums).  Iteration it < exaggeration_iter runs with early_exaggeration and
+ *   momentum 0.5, a later one with exaggeration 1 and momentum 0.8.
+ *   KL = sum P log P + sum_ij P_ij log1p(|y_i - y_j|^2) + log Z (fp64 over the rows' sums).
+ * ------------------------------------------------------------------------ */
+#define SCAE_TSNE_MAX_N 32768      /* one row of fp32 distances (128 KiB) in a CU's LDS */
+#define SCAE_TSNE_MAX_F 256
+#define SCAE_TSNE_HISTORY_COLS 3   /* iteration, KL, the gradient's 2-norm */
+#define SCAE_TSNE_BLOCK_DOUBLES 640   /* the update launches' per-workgroup partials */
+/* 1 for 2 <= N <= SCAE_TSNE_MAX_N and 1 <= F <= SCAE_TSNE_MAX_F, else 0 */
+int scae_tsne_supported(int N, int F);
+/* the column groups of a gradient launch (the partials' G): 256 columns each up to N = 2048,
+ * 1024 above, so that the (row block, column group) grid covers the CUs from N of about 10^3
+ * on; a function of N alone (0 for N out of range) */
+int scae_tsne_groups(int N);
+/* x (N, F) -> P (N, N), beta (N) and *plogp = the fp64 sum of P log P over P > 0, from part
+ * (T (T + 1) / 2 doubles, T = ceil(N / 32): one per pair of mirrored 32 x 32 tiles) added in
+ * index order.  P holds the distances, then the conditional affinities, on the way. */
+int scae_tsne_affinities_f32(const float *x, int N, int F, float perplexity, float *P,
+                             float *beta, double *part, double *plogp, void *stream);
+typedef struct scae_tsne_desc {
+  int N;
+  int G;                     /* scae_tsne_groups(N) */
+  int n_iter;                /* the run's length: nothing stops early */
+  int exaggeration_iter;
+  int check_every;
+  float early_exaggeration;
+  float learning_rate;
+  const float *P;            /* (N, N) */
+  float *Y, *velocity, *gains;   /* (N, 2): the state in, the result out */
+  float *part;               /* (6, G, N): attraction (2), repulsion (2), Z, KL per column group */
+  float *rows;               /* (6, N): the same, the groups added in g order */
+  double *block;             /* (SCAE_TSNE_BLOCK_DOUBLES) */
+  const double *plogp;       /* (1) */
+  double *history;           /* (ceil(n_iter / check_every), SCAE_TSNE_HISTORY_COLS) */
+} scae_tsne_desc;
+/* iterations first_iter .. first_iter + n - 1, four launches each: the gradient's partials per
+ * (row block, column group), the rows' sums in g order, the update, and a one-workgroup
+ * recentring.  An iteration it > 0 that is a multiple of check_every also records
+ * (it, KL, |g|) of the Y it starts from in history row it / check_every - 1 (its gradient
+ * launch is the form that adds P log1p(d)); when first_iter + n == n_iter a last evaluation
+ * without an update records (n_iter, KL, |g|) of the result in the last row.  Nothing is read
+ * back: the host enqueues a whole run. */
+int scae_tsne_run_f32(const scae_tsne_desc *d, int first_iter, int n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

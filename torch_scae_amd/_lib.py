@@ -131,6 +131,14 @@ class ProbeDesc(Structure):
                 ("part_grad", P), ("part_loss", P), ("history", P), ("state", P)]
 
 
+class TsneDesc(Structure):
+    """struct scae_tsne_desc"""
+    _fields_ = [("N", c_int), ("G", c_int), ("n_iter", c_int), ("exaggeration_iter", c_int),
+                ("check_every", c_int), ("early_exaggeration", c_float),
+                ("learning_rate", c_float), ("P", P), ("Y", P), ("velocity", P), ("gains", P),
+                ("part", P), ("rows", P), ("block", P), ("plogp", P), ("history", P)]
+
+
 class SeedFoldDesc(Structure):
     """struct scae_seed_fold_desc"""
     _fields_ = [(n, P) for n in (
@@ -390,6 +398,10 @@ SIGNATURES = {
     "scae_probe_moments_f64": [P, P, c_int64, c_int, c_int, P, P, P, P],
     "scae_probe_fit_f32": [POINTER(ProbeDesc), c_int, P],
     "scae_probe_predict_f32": [P, c_int64, c_int, c_int] + [P] * 8,
+    "scae_tsne_supported": [c_int] * 2,
+    "scae_tsne_groups": [c_int],
+    "scae_tsne_affinities_f32": [P, c_int, c_int, c_float, P, P, P, P, P],
+    "scae_tsne_run_f32": [POINTER(TsneDesc), c_int, c_int, P],
     "scae_template_render_fwd_f32": [POINTER(DecoderDesc), P, P, P],
     "scae_render_gmm_logprob_fwd_f32": [POINTER(DecoderDesc), P, P, P, P, P],
     "scae_render_gmm_bwd_f32": [POINTER(DecoderDesc)] + [P] * 12 + [P],
@@ -415,6 +427,10 @@ EVAL_ACC_DOUBLES = 17        # SCAE_EVAL_ACC_DOUBLES: the accumulator of scae_ev
 TRAIN_LOG_ROW = 19           # SCAE_TRAIN_LOG_ROW: one row of scae_train_log_desc's ring
 KMEANS_STATE_INTS = 4        # SCAE_KMEANS_STATE_INTS: per restart of scae_kmeans_desc's state
 PROBE_STATE_INTS = 4         # SCAE_PROBE_STATE_INTS: per problem of scae_probe_desc's state
+TSNE_MAX_N = 32768           # SCAE_TSNE_MAX_N
+TSNE_MAX_F = 256             # SCAE_TSNE_MAX_F
+TSNE_HISTORY_COLS = 3        # SCAE_TSNE_HISTORY_COLS: iteration, KL, gradient norm
+TSNE_BLOCK_DOUBLES = 640     # SCAE_TSNE_BLOCK_DOUBLES: scae_tsne_desc's block workspace
 EVAL_SINK_INT64S = 4         # struct scae_eval_sink: rows, capacity, cursor, overflow
 # struct scae_eval_records: rows, capacity, cursor, overflow, confusion, ncls, labelled
 EVAL_RECORDS_INT64S = 7
