@@ -1833,6 +1833,51 @@ typedef struct scae_tsne_desc {
  * back: the host enqueues a whole run. */
 int scae_tsne_run_f32(const scae_tsne_desc *d, int first_iter, int n, void *stream);
 
+/* ------------------------------------------------------------------------
+ * k nearest neighbours (csrc/knn.hip): the exact, brute-force search for the k nearest rows of a
+ * base (Nb, F) for every query row (Nq, F), the k-NN vote on the lists, and the neighbour ranks
+ * behind trustworthiness.  The result is defined by a total order, so its bits do not depend on
+ * how the base is split over workgroups; no float atomics, no global atomics.
+ *   d_ij = sum_f (q_if - b_jf)^2 in f order from 0, the difference, the product and the sum each
+ *   rounded to fp32 (no fused multiply-add: numpy's float32 reproduces it exactly).
+ *   Neighbours ascend by the pair (d_ij, j): equal distances go to the lower base index.  In
+ *   self mode the base is the queries and row i is not its own neighbour.
+ *   Inputs are finite (not checked).
+ * ------------------------------------------------------------------------ */
+#define SCAE_KNN_MAX_K 64
+#define SCAE_KNN_MAX_F 256
+#define SCAE_KNN_MAX_KS 8
+/* 1 for 1 <= Nq, Nb < 2^31, 1 <= F <= SCAE_KNN_MAX_F and 1 <= k <= min(SCAE_KNN_MAX_K, Nb),
+ * else 0 (self mode needs k <= Nb - 1 besides: scae_knn_f32 checks it) */
+int scae_knn_supported(int64_t Nq, int64_t Nb, int F, int k);
+/* base groups G of a search launch: a function of (Nq, Nb) alone -- enough (query tile, base
+ * group) workgroups to cover the CUs when Nq is small, at least 512 base rows each, at most 64;
+ * 0 for sizes out of range */
+int scae_knn_groups(int64_t Nq, int64_t Nb);
+/* q (Nq, F), base (Nb, F) -> d2 (Nq, k) fp32 and idx (Nq, k) int64, ascending by (d2, idx).
+ * self_mode: base must be q and Nb == Nq.  part: (Nq, G, k) 64-bit words, G =
+ * scae_knn_groups(Nq, Nb) -- each group's sorted list as (bits of d2) << 32 | idx, merged by a
+ * second launch; with G == 1 the search writes d2 / idx itself and part may be NULL. */
+int scae_knn_f32(const float *q, int64_t Nq, const float *base, int64_t Nb, int F, int k,
+                 int self_mode, uint64_t *part, float *d2, int64_t *idx, void *stream);
+/* The vote on neighbour lists idx / d2 (Nq, k) of a base with labels base_labels (Nb):
+ * pred (Nq, n_ks) int64, column i the prediction from the first ks[i] neighbours (ks ascending,
+ * ks[n_ks - 1] == k, n_ks <= SCAE_KNN_MAX_KS; a host array).  Walking the list m = 0, 1, ...:
+ * w_m = 1, or with `weighted` 1 / sqrt(d2_m) (both correctly rounded) -- unless d2_0 == 0, then
+ * w_m = 1 where d2_m == 0 and 0 elsewhere; the tally of neighbour m is the fp32 sum in list order
+ * of w_n over n <= m with label_n == label_m, and the running best becomes (tally, label_m) when
+ * the tally is greater, or equal with a lower label.  No per-class array: any int64 labels. */
+int scae_knn_vote_f32(const int64_t *idx, const float *d2, int64_t Nq, int k,
+                      const int64_t *base_labels, int64_t Nb, const int *ks, int n_ks,
+                      int weighted, int64_t *pred, void *stream);
+/* Self-mode ranks of listed neighbours: for x (N, F) and idx (N, k) (rows j != i of x; values
+ * outside [0, N) are clamped into it) rank (N, k) int32 = 1 + #{ l != i : (d_il, l) < (d_ij, j) }
+ * and *penalty = sum max(0, rank - k), an exact int64.  part_count: (N, G, k) int32 with G =
+ * scae_knn_groups(N, N); part: ceil(N / 256) int64 per-workgroup penalties, added in index
+ * order by a last launch. */
+int scae_knn_ranks_f32(const float *x, int64_t N, int F, const int64_t *idx, int k, int *rank,
+                       int *part_count, int64_t *part, int64_t *penalty, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

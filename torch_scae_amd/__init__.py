@@ -9,6 +9,7 @@ from . import (cv_ops, distributions, factory, general_utils, math_ops,  # noqa
 from . import cluster  # noqa
 from . import probe  # noqa
 from . import embed  # noqa
+from . import neighbors  # noqa
 from .eval_step import EvalStep  # noqa
 from .stacked_capsule_auto_encoder import SCAE  # noqa
 

@@ -402,6 +402,11 @@ SIGNATURES = {
     "scae_tsne_groups": [c_int],
     "scae_tsne_affinities_f32": [P, c_int, c_int, c_float, P, P, P, P, P],
     "scae_tsne_run_f32": [POINTER(TsneDesc), c_int, c_int, P],
+    "scae_knn_supported": [c_int64, c_int64, c_int, c_int],
+    "scae_knn_groups": [c_int64, c_int64],
+    "scae_knn_f32": [P, c_int64, P, c_int64, c_int, c_int, c_int, P, P, P, P],
+    "scae_knn_vote_f32": [P, P, c_int64, c_int, P, c_int64, POINTER(c_int), c_int, c_int, P, P],
+    "scae_knn_ranks_f32": [P, c_int64, c_int, P, c_int, P, P, P, P, P],
     "scae_template_render_fwd_f32": [POINTER(DecoderDesc), P, P, P],
     "scae_render_gmm_logprob_fwd_f32": [POINTER(DecoderDesc), P, P, P, P, P],
     "scae_render_gmm_bwd_f32": [POINTER(DecoderDesc)] + [P] * 12 + [P],
@@ -431,6 +436,9 @@ TSNE_MAX_N = 32768           # SCAE_TSNE_MAX_N
 TSNE_MAX_F = 256             # SCAE_TSNE_MAX_F
 TSNE_HISTORY_COLS = 3        # SCAE_TSNE_HISTORY_COLS: iteration, KL, gradient norm
 TSNE_BLOCK_DOUBLES = 640     # SCAE_TSNE_BLOCK_DOUBLES: scae_tsne_desc's block workspace
+KNN_MAX_K = 64               # SCAE_KNN_MAX_K
+KNN_MAX_F = 256              # SCAE_KNN_MAX_F
+KNN_MAX_KS = 8               # SCAE_KNN_MAX_KS
 EVAL_SINK_INT64S = 4         # struct scae_eval_sink: rows, capacity, cursor, overflow
 # struct scae_eval_records: rows, capacity, cursor, overflow, confusion, ncls, labelled
 EVAL_RECORDS_INT64S = 7

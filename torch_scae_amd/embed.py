@@ -404,10 +404,16 @@ def tsne(x, perplexity=30.0, n_iter=1000, early_exaggeration=12.0, exaggeration_
 
 
 # -- the whole figure ----------------------------------------------------------------------------
-def capsule_embedding(step, split, feature="prior", **tsne_args):
+def capsule_embedding(step, split, feature="prior", trustworthiness_k=None, **tsne_args):
     """The t-SNE embedding of the object-capsule features of ``split`` (an (images, labels) pair
     or a data.DatasetView), encoded by the EvalStep ``step``.  -> {"y" (N, 2), "label" (N,) in
-    encode order, "kl", "history"}."""
+    encode order, "kl", "history"}, and with ``trustworthiness_k`` also "trustworthiness": how
+    far y keeps the features' neighbourhoods at that k (``neighbors.trustworthiness``)."""
     enc = _encode(step, split)
-    res = tsne(features(enc, feature), **tsne_args)
-    return {"y": res.y, "label": enc["label"], "kl": res.kl, "history": res.history}
+    x = features(enc, feature)
+    res = tsne(x, **tsne_args)
+    out = {"y": res.y, "label": enc["label"], "kl": res.kl, "history": res.history}
+    if trustworthiness_k is not None:
+        from .neighbors import trustworthiness
+        out["trustworthiness"] = trustworthiness(x, res.y, trustworthiness_k)
+    return out
