@@ -1655,6 +1655,33 @@ int scae_gmm_mode_f32(const float *loc, const float *mixing_logits,
 int scae_render_gmm_mode_f32(const scae_decoder_desc *d, float *out, int what, int first,
                              int count, void *stream);
 
+/* The mixture's E-step from the compact inputs (csrc/render_gmm_parts.hip): which component owns
+ * each pixel of images [first, first + count).  Per pixel p and channel c, K = M + 1 components
+ * with values loc[k,c,p] and mixing logits ml[k,cm,p] in the arithmetic of
+ * scae_render_gmm_mode_f32 (cm = 0 in alpha mode, c in temperature mode), sigma the Normal scale:
+ *   j[k,c,p] = ml[k,cm,p] - 0.5 (x[c,p] - loc[k,c,p])^2 / sigma^2    (x null: ml[k,cm,p] alone)
+ *   r[k,c,p] = softmax_k j[.,c,p]   two passes (max, then sum) in component order
+ *   R[k,p]   = (1/C) sum_c r[k,c,p]
+ *   part[p]  = first k with the largest R[k,p] (k = M: background),  conf[p] = R[part[p],p]
+ *   mass[k]  = sum_p R[k,p]: wave sums, waves, pixel rounds and tiles each in a fixed order, no
+ *              atomics -- the same bits on every run of a call (and of another slice of the
+ *              batch while both take the same pixel tiling)
+ *   group[p] = part_group[b, part[p]] for part[p] < M, else -1
+ *   rgb[:,p] = t palette[id mod P] (id = part[p] / group[p]) with t = mean_c loc[part[p],c,p];
+ *              t (1, 1, 1) on a background pixel
+ * x: (B, C, H, W) or null.  part_group: (B, M) int32 or null (then group and rgb_group must be
+ * null).  palette: (P, 3).  part, group: (count, H, W) int32; conf: (count, H, W); mass:
+ * (count, M + 1); mass_partial: (count, tiles, M + 1) workspace, tiles from
+ * scae_render_gmm_parts_geometry; rgb_part, rgb_group: (count, 3, H, W) or null.  Two launches:
+ * the E-step, then the tiles' sums. */
+int scae_render_gmm_parts_f32(const scae_decoder_desc *d, const float *x, const int *part_group,
+                              const float *palette, int P, int *part, float *conf, float *mass,
+                              float *mass_partial, int *group, float *rgb_part,
+                              float *rgb_group, int first, int count, void *stream);
+/* out[0..2] = {pixel tiles per image, pixels per tile, templates staged at a time} of that call
+ * (and of scae_render_gmm_mode_f32) for `count` images; templates staged < d->M: chunked. */
+int scae_render_gmm_parts_geometry(const scae_decoder_desc *d, int count, int *out);
+
 /* ------------------------------------------------------------------------
  * Image sheets (csrc/image_sheet.hip): up to 4 sources (n[i], C, H, W), taken as one batch of
  * N = sum n[i] images in source order, laid into sheet (3, Hs, Ws) in one launch.

@@ -10,6 +10,7 @@ from . import cluster  # noqa
 from . import probe  # noqa
 from . import embed  # noqa
 from . import neighbors  # noqa
+from . import segment  # noqa
 from .eval_step import EvalStep  # noqa
 from .stacked_capsule_auto_encoder import SCAE  # noqa
 

@@ -419,6 +419,8 @@ SIGNATURES = {
     "scae_gmm_mean_f32": [P] * 3 + [c_int] * 4 + [c_int64, P],
     "scae_gmm_mode_f32": [P] * 4 + [c_int] * 5 + [c_int64, P],
     "scae_render_gmm_mode_f32": [POINTER(DecoderDesc), P, c_int, c_int, c_int, P],
+    "scae_render_gmm_parts_f32": [POINTER(DecoderDesc), P, P, P, c_int] + [P] * 7 + [c_int, c_int, P],
+    "scae_render_gmm_parts_geometry": [POINTER(DecoderDesc), c_int, POINTER(c_int)],
     "scae_image_sheet_f32": [c_int, POINTER(P), POINTER(c_int)] + [c_int] * 5 + [c_float, P, P],
 }
 

@@ -439,6 +439,40 @@ class EvalStep:
                                                               padding=1, pad_value=0.0)
         return sheets
 
+    def segmentation_images(self, result=None, n=8):
+        """Two more sheets for ``add_image``, the image decomposed into its parts
+        (torch_scae_amd.segment), each a (3, Hs, Ws) fp32 device tensor of the first
+        ``min(batch_size, n)`` images:
+
+        'parts': rows input, mode of ``rec``, every pixel painted with its owning part's
+          colour times the part's value there (background pixels stay grey);
+        'capsules': the same with the colour of the object capsule that owns the part
+          (``segment.part_owner``).
+
+        ``result`` as for ``validation_images``, whose first two 'recons' rows these sheets
+        repeat.  The owners are the posterior given the staged batch, from the fused E-step
+        kernel for the ``n`` images alone; ``result`` stays unrendered, the accumulator and
+        the captured step untouched."""
+        if not self.cuda:
+            raise ops.ScaeHipError("segmentation_images runs on the library's kernels: the "
+                                   "model is on the CPU")
+        if not isinstance(n, int) or isinstance(n, bool) or n <= 0:
+            raise ValueError(f"n must be a positive int, got {n!r}")
+        from . import segment
+        res = self._eager_result() if result is None else result
+        n = min(self.batch_size, n)
+        with torch.no_grad():
+            image = dict.get(res, "image")
+            image = self.image if image is None else image
+            inputs = res["rec"].pdf._decoder_inputs
+            # (the sheet kernel takes one channel count for all its sources)
+            rgb = lambda t: t.expand(-1, 3, -1, -1) if t.shape[1] == 1 else t  # noqa: E731
+            rows = [rgb(image[:n]), rgb(ops.render_gmm_mode(inputs, first=0, count=n))]
+            seg = segment.segment(res, image, first=0, count=n)
+            return {key: ops.image_sheet(rows + [painted], nrow=n, padding=1, pad_value=0.0)
+                    for key, painted in (("parts", seg.rgb_part),
+                                         ("capsules", seg.rgb_group))}
+
     def validation_step(self, image, label, batch_idx=None):
         """-> {'val_loss', 'accuracy'} as device tensors the next call overwrites
         (base_experiment.py:128-143); with ``batch_idx == 0`` also 'result'."""

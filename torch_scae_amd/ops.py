@@ -6,6 +6,7 @@ are ``torch.empty`` allocations, kernels are enqueued on the calling thread's
 current HIP stream (so everything composes with ``torch.cuda.graph`` capture
 and with autograd's backward thread).  No op has a CPU or eager fallback.
 """
+import collections
 import ctypes
 import functools
 
@@ -19,7 +20,7 @@ from .step_plan import StepPlan, current as _plan
 __all__ = ["geometric_transform", "qkv_attention", "set_encoder", "grouped_mlp", "seed_attention", "seed_attention_supported", "seed_fold", "seed_fold_supported", "loss_tail", "loss_tail_scalar", "loss_tail_supported", "capsule_votes",
            "capsule_likelihood", "colored_templates", "template_color_supported", "attention_conv_pool", "attention_pool_supported", "capsule_head", "part_encoder", "conv_stack", "conv_stack_supported",
            "uniform", "reset_noise", "pack_params", "render_templates", "render_gmm_log_prob", "render_gmm_log_prob_sums",
-           "gmm_log_prob", "gmm_mean", "gmm_mode", "render_gmm_mode", "image_sheet", "ScaeHipError"]
+           "gmm_log_prob", "gmm_mean", "gmm_mode", "render_gmm_mode", "render_gmm_parts", "GmmParts", "image_sheet", "ScaeHipError"]
 
 
 def _need_hip(*tensors):
@@ -3545,6 +3546,80 @@ def render_gmm_mode(inputs: DecoderInputs, mean=False, first=0, count=None):
     _lib.call("scae_render_gmm_mode_f32", ctypes.byref(d), _p(out),
               1 if mean else 0, first, count, _stream(t[0]))
     return out
+
+
+GmmParts = collections.namedtuple(
+    "GmmParts", ["part", "conf", "mass", "group", "rgb_part", "rgb_group"])
+
+
+def render_gmm_parts_geometry(inputs: DecoderInputs, count=None):
+    """(pixel tiles per image, pixels per tile, templates staged at a time) of
+    the ``render_gmm_parts`` / ``render_gmm_mode`` launch for ``count`` images;
+    fewer templates staged than the decoder has: their planes are chunked."""
+    t = [None if v is None else v.detach() for v in inputs.tensors()]
+    d, (B, M, C, th, tw, H, W) = _make_desc(t, inputs.output_size)
+    out = (ctypes.c_int * 3)()
+    _lib.call("scae_render_gmm_parts_geometry", ctypes.byref(d),
+              B if count is None else count, out)
+    return tuple(out)
+
+
+def render_gmm_parts(inputs: DecoderInputs, x=None, part_group=None,
+                     palette=None, first=0, count=None):
+    """The E-step of the decoder's mixture straight from its compact inputs, for
+    images [first, first + count): which of the M templates (or the background,
+    index M) owns each pixel given the observed image ``x`` (B, C, H, W) -- or a
+    priori, ``x=None``.  -> GmmParts(part (count, H, W) int32, conf (count, H,
+    W), mass (count, M+1), group (count, H, W) int32 or None, rgb_part (count,
+    3, H, W), rgb_group or None); include/scae_hip.h states every definition.
+    ``part_group``: (B, M) int32 owner of each part (``segment.part_owner``);
+    without it ``group`` and ``rgb_group`` are None.  ``palette``: (P, 3) fp32,
+    default ``segment.palette(M)``.  ``mass`` has the same bits on every run.
+    Forward only: nothing here is differentiable."""
+    B0, M, C = inputs.templates.shape[:3]
+    B, (H, W) = inputs.pose.shape[0], inputs.output_size
+    count = B - first if count is None else count
+    if not (isinstance(first, int) and isinstance(count, int)
+            and 0 <= first and count > 0 and first + count <= B):
+        raise ValueError(f"images [{first}, {first}+{count}) are not a slice of "
+                         f"the {B} this decoder call holds")
+    if x is not None and tuple(x.shape) != (B, C, H, W):
+        raise ValueError(f"the observed image must be {(B, C, H, W)}, got "
+                         f"{tuple(x.shape)}")
+    if part_group is not None and (tuple(part_group.shape) != (B, M)
+                                   or part_group.dtype != torch.int32):
+        raise ValueError(f"part_group must be an int32 tensor of shape {(B, M)}, "
+                         f"got {part_group.dtype} {tuple(part_group.shape)}")
+    if palette is not None and (palette.dim() != 2 or palette.shape[1] != 3
+                                or palette.shape[0] == 0
+                                or palette.dtype != torch.float32):
+        raise ValueError("palette must be a (P, 3) float32 tensor, P > 0")
+    t = _prep_decoder(inputs.tensors())
+    _need_hip(x, palette)
+    if part_group is not None and not part_group.is_cuda:
+        raise ScaeHipError("part_group must be on the HIP device")
+    d, _ = _make_desc(t, inputs.output_size)
+    dev = t[0].device
+    if palette is None:
+        from .segment import palette as default_palette
+        palette = default_palette(M).to(dev)
+    x, part_group, palette = _c(_detached(x)), _c(part_group), _c(palette.detach())
+    tiles = render_gmm_parts_geometry(inputs, count)[0]
+    f32 = dict(device=dev, dtype=torch.float32)
+    part = torch.empty(count, H, W, device=dev, dtype=torch.int32)
+    conf = torch.empty(count, H, W, **f32)
+    mass = torch.empty(count, M + 1, **f32)
+    partial = torch.empty(count, tiles, M + 1, **f32)
+    rgb_part = torch.empty(count, 3, H, W, **f32)
+    group = rgb_group = None
+    if part_group is not None:
+        group = torch.empty_like(part)
+        rgb_group = torch.empty_like(rgb_part)
+    _lib.call("scae_render_gmm_parts_f32", ctypes.byref(d), _p(x), _p(part_group),
+              _p(palette), palette.shape[0], _p(part), _p(conf), _p(mass),
+              _p(partial), _p(group), _p(rgb_part), _p(rgb_group), first, count,
+              _stream(t[0]))
+    return GmmParts(part, conf, mass, group, rgb_part, rgb_group)
 
 
 # ----------------------------------------------------------------------------
