@@ -1905,6 +1905,61 @@ int scae_knn_vote_f32(const int64_t *idx, const float *d2, int64_t Nq, int k,
 int scae_knn_ranks_f32(const float *x, int64_t N, int F, const int64_t *idx, int k, int *rank,
                        int *part_count, int64_t *part, int64_t *penalty, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Sparse t-SNE (csrc/tsne_sparse.hip, the wide search in csrc/knn.hip): t-SNE past
+ * SCAE_TSNE_MAX_N rows.  P lives on each row's K nearest neighbours (CSR after the
+ * symmetrisation, which the caller assembles: embed.py does it with integer sorts on the
+ * device); the repulsion is still exact over every pair, an N-body pass over Y with no N^2
+ * memory.  The rules are the dense ones term for term, with these differences:
+ *   the neighbour lists are the k-NN search's (d, j)-ordered lists in self mode;
+ *   the bandwidth search runs over the row's K listed distances, shifted by the first;
+ *   p_{j|i} = 0 off the list, P_ij = (p_{j|i} + p_{i|j}) / (2 N) on the union of the edges;
+ *   the attraction and KL sums run over row i's stored entries in column order.
+ * No float atomics, every sum in a fixed order: two runs give the same bits.
+ * ------------------------------------------------------------------------ */
+#define SCAE_TSNE_MAX_NEIGHBORS 128      /* the search's lists at k = 128: 144 KiB of LDS */
+#define SCAE_TSNE_SPARSE_MAX_N 262144
+#define SCAE_TSNE_SPARSE_BLOCK_DOUBLES 5120   /* 5 x (SCAE_TSNE_SPARSE_MAX_N / 256) partials */
+/* scae_knn_f32 in self mode for 1 <= k <= min(SCAE_TSNE_MAX_NEIGHBORS, N - 1): the same
+ * kernels, the same lists (part as there: (N, G, k) words with G = scae_knn_groups(N, N)) */
+int scae_knn_wide_f32(const float *x, int64_t N, int F, int k, uint64_t *part, float *d2,
+                      int64_t *idx, void *stream);
+/* 1 for 2 <= N <= SCAE_TSNE_SPARSE_MAX_N, 1 <= F <= SCAE_TSNE_MAX_F and
+ * 1 <= K <= min(SCAE_TSNE_MAX_NEIGHBORS, N - 1), else 0 */
+int scae_tsne_sparse_supported(int N, int F, int K);
+/* the column groups of a repulsion launch (the partials' G): a function of N alone -- about
+ * 1024 (512-row block, column group) workgroups, whole 512-column tiles each, at most 64; 0 for
+ * N out of range */
+int scae_tsne_sparse_groups(int N);
+/* d2 (N, K), a row ascending (the search's lists) -> beta (N) and the conditional rows cond
+ * (N, K): p_{j|i} of the listed neighbours.  One row per wave, two entries per lane. */
+int scae_tsne_knn_bandwidths_f32(const float *d2, int N, int K, float perplexity, float *cond,
+                                 float *beta, void *stream);
+typedef struct scae_tsne_sparse_desc {
+  int N;
+  int G;                     /* scae_tsne_sparse_groups(N) */
+  int n_iter;
+  int exaggeration_iter;
+  int check_every;
+  float early_exaggeration;
+  float learning_rate;
+  const int64_t *indptr;     /* (N + 1): CSR of the joint affinities, */
+  const int *cols;           /* (nnz) a row's columns ascending, no diagonal, */
+  const float *vals;         /* (nnz) symmetric */
+  int64_t nnz;
+  float *Y, *velocity, *gains;   /* (N, 2): the state in, the result out */
+  float *part;               /* (3, G, N): repulsion (2) and Z per column group */
+  float *rows;               /* (6, N): attraction (2), repulsion (2), Z, KL */
+  double *block;             /* (SCAE_TSNE_SPARSE_BLOCK_DOUBLES) */
+  const double *plogp;       /* (1) */
+  double *history;           /* (ceil(n_iter / check_every), SCAE_TSNE_HISTORY_COLS) */
+} scae_tsne_sparse_desc;
+/* scae_tsne_run_f32 for the sparse form, five launches an iteration: the attraction (a CSR row
+ * per wave; the recorded iterations' form adds P log1p(d)), the repulsion's partials per (row
+ * block, column group), the rows' sums in g order, the update, the recentring.  The same
+ * schedule, history rows and final evaluation; nothing is read back. */
+int scae_tsne_sparse_run_f32(const scae_tsne_sparse_desc *d, int first_iter, int n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,7 @@
 with 10 classes, at N = 10 000 and N = 32 768, HIP-event timed after a warm-up, one JSON line:
 
     python tools/tsne_time.py [--n 10000 32768] [--iters 1000] [--host-n 2000] [--no-host]
+                              [--neighbors auto|K]
 
 - ``embed.affinities``; ``embed.tsne`` for ``--iters`` iterations (affinities and the PCA
   initialisation included) and the iterations alone; the same iteration as a torch-op loop on the
@@ -9,6 +10,11 @@ with 10 classes, at N = 10 000 and N = 32 768, HIP-event timed after a warm-up, 
 - ``embed.tsne_host`` (fp64 numpy) at a size it finishes, ``--host-n``;
 - scikit-learn's ``TSNE(method="exact")`` at ``--host-n`` and ``"barnes_hut"`` at the first N, if
   ``sklearn`` imports; silent otherwise.
+- with ``--neighbors`` the sparse form (csrc/tsne_sparse.hip) instead: ``embed.affinities_knn``,
+  ``embed.tsne(neighbors=...)`` and its iterations alone, no torch loop; and, at the first N when
+  the dense form takes it, the trustworthiness at k = 12 of the sparse and the dense embedding
+  from the same initialisation ("quality").  The split of an iteration into its launches is a
+  kernel trace's to give: run ``--child tsne`` under a profiler;
 Every GPU measurement runs in a child process of its own under its own time limit; a child that
 fails or runs out of time leaves an "error" entry and ends the measurements."""
 import argparse
@@ -60,12 +66,29 @@ def torch_iteration(P, Y, vel, gains, ex, mom, lr):
     return Y - Y.mean(0), vel, gains
 
 
-def child(what, N, iters):
+def child(what, N, iters, nb=None):
     import torch
     from torch_scae_amd import embed
     x = torch.from_numpy(synthetic(N)[0]).cuda()
     out = dict(what=what, N=N)
-    if what == "affinities":
+    if nb is not None:
+        out.update(neighbors=nb)
+    if what == "affinities" and nb is not None:
+        ms, res = timed(lambda: embed.affinities_knn(x, 30.0, nb))
+        out.update(ms=round(ms, 3), nnz=res[1].numel())
+    elif what == "tsne" and nb is not None:
+        ms, res = timed(lambda: embed.tsne(x, n_iter=iters, neighbors=nb))
+        csr, _, plogp = embed._affinities_knn_device(x, 30.0, embed._check_sparse(x, 30.0, nb))
+        p = embed._SparseProblem(csr, plogp, res.y, iters, 12.0, 250, max(N / 48.0, 50.0), 50)
+        ms_it, _ = timed(lambda: p.run(0, iters), warm=0)
+        out.update(ms=round(ms, 3), iterations=iters, kl=res.kl,
+                   iterations_ms=round(ms_it, 3), us_per_iteration=round(1e3 * ms_it / iters, 2))
+    elif what == "quality":
+        from torch_scae_amd.neighbors import trustworthiness
+        for name, arg in (("sparse", nb), ("dense", None)):
+            res = embed.tsne(x, n_iter=iters, neighbors=arg)
+            out[name] = dict(kl=res.kl, trustworthiness_12=trustworthiness(x, res.y, 12))
+    elif what == "affinities":
         ms, _ = timed(lambda: embed.affinities(x, 30.0))
         out.update(ms=round(ms, 3))
     elif what == "tsne":
@@ -88,9 +111,11 @@ def child(what, N, iters):
     print(json.dumps(out), flush=True)
 
 
-def run_child(what, N, iters, limit):
+def run_child(what, N, iters, limit, nb=None):
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__),
            "--child", what, "--n", str(N), "--iters", str(iters)]
+    if nb is not None:
+        cmd += ["--neighbors", str(nb)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         return dict(what=what, N=N, error=f"exit {r.returncode}"), False
@@ -106,18 +131,25 @@ def main():
     ap.add_argument("--host-iters", type=int, default=1000)
     ap.add_argument("--limit", type=int, default=240)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--neighbors", type=lambda v: v if v == "auto" else int(v))
     ap.add_argument("--child")
     args = ap.parse_args()
+    nb = args.neighbors
     if args.child:
-        return child(args.child, args.n[0], args.iters)
+        return child(args.child, args.n[0], args.iters, nb)
     results, ok = [], True
     for N in args.n:
         for what, iters in (("affinities", 0), ("tsne", args.iters), ("torch", args.torch_iters)):
-            if what == "torch" and N > 16384:
+            if what == "torch" and (N > 16384 or nb is not None):
                 continue                      # (its (N, N, 2) temporaries: 8 GiB each at 32 768)
             if ok:
-                r, ok = run_child(what, N, iters, args.limit)
+                r, ok = run_child(what, N, iters, args.limit, nb)
                 results.append(r)
+    if ok and nb is not None and args.n[0] <= 32768:
+        r, ok = run_child("quality", args.n[0], args.iters, args.limit, nb)
+        results.append(r)
+    if nb is not None:
+        args.no_host = True
     if not args.no_host:
         import torch
         from torch_scae_amd import embed

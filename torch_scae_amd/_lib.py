@@ -139,6 +139,15 @@ class TsneDesc(Structure):
                 ("part", P), ("rows", P), ("block", P), ("plogp", P), ("history", P)]
 
 
+class TsneSparseDesc(Structure):
+    """struct scae_tsne_sparse_desc"""
+    _fields_ = [("N", c_int), ("G", c_int), ("n_iter", c_int), ("exaggeration_iter", c_int),
+                ("check_every", c_int), ("early_exaggeration", c_float),
+                ("learning_rate", c_float), ("indptr", P), ("cols", P), ("vals", P),
+                ("nnz", c_int64), ("Y", P), ("velocity", P), ("gains", P), ("part", P),
+                ("rows", P), ("block", P), ("plogp", P), ("history", P)]
+
+
 class SeedFoldDesc(Structure):
     """struct scae_seed_fold_desc"""
     _fields_ = [(n, P) for n in (
@@ -402,6 +411,11 @@ SIGNATURES = {
     "scae_tsne_groups": [c_int],
     "scae_tsne_affinities_f32": [P, c_int, c_int, c_float, P, P, P, P, P],
     "scae_tsne_run_f32": [POINTER(TsneDesc), c_int, c_int, P],
+    "scae_tsne_sparse_supported": [c_int] * 3,
+    "scae_tsne_sparse_groups": [c_int],
+    "scae_tsne_knn_bandwidths_f32": [P, c_int, c_int, c_float, P, P, P],
+    "scae_tsne_sparse_run_f32": [POINTER(TsneSparseDesc), c_int, c_int, P],
+    "scae_knn_wide_f32": [P, c_int64, c_int, c_int, P, P, P, P],
     "scae_knn_supported": [c_int64, c_int64, c_int, c_int],
     "scae_knn_groups": [c_int64, c_int64],
     "scae_knn_f32": [P, c_int64, P, c_int64, c_int, c_int, c_int, P, P, P, P],
@@ -438,6 +452,9 @@ TSNE_MAX_N = 32768           # SCAE_TSNE_MAX_N
 TSNE_MAX_F = 256             # SCAE_TSNE_MAX_F
 TSNE_HISTORY_COLS = 3        # SCAE_TSNE_HISTORY_COLS: iteration, KL, gradient norm
 TSNE_BLOCK_DOUBLES = 640     # SCAE_TSNE_BLOCK_DOUBLES: scae_tsne_desc's block workspace
+TSNE_MAX_NEIGHBORS = 128     # SCAE_TSNE_MAX_NEIGHBORS
+TSNE_SPARSE_MAX_N = 262144   # SCAE_TSNE_SPARSE_MAX_N
+TSNE_SPARSE_BLOCK_DOUBLES = 5120   # SCAE_TSNE_SPARSE_BLOCK_DOUBLES
 KNN_MAX_K = 64               # SCAE_KNN_MAX_K
 KNN_MAX_F = 256              # SCAE_KNN_MAX_F
 KNN_MAX_KS = 8               # SCAE_KNN_MAX_KS

@@ -408,6 +408,29 @@ extern "C" int scae_knn_f32(const float *q, int64_t Nq, const float *base, int64
   return scae_launch_status();
 }
 
+// the self-mode search of sparse t-SNE: the same launches up to k = SCAE_TSNE_MAX_NEIGHBORS (the
+// lists of a workgroup then take 128 KiB of LDS, one workgroup a CU; the merge's byte cursors
+// end at k <= 128)
+extern "C" int scae_knn_wide_f32(const float *x, int64_t N, int F, int k, uint64_t *part,
+                                 float *d2, int64_t *idx, void *stream) {
+  SCAE_REQUIRE(x && d2 && idx);
+  static_assert(SCAE_TSNE_MAX_NEIGHBORS <= 255, "knn_merge_kernel's cursors are bytes");
+  if (N < 2 || N >= ((int64_t)1 << 31) || F < 1 || F > SCAE_KNN_MAX_F || k < 1 ||
+      k > SCAE_TSNE_MAX_NEIGHBORS || k > N - 1)
+    return SCAE_ERR_UNSUPPORTED;
+  const int G = scae_knn_groups(N, N);
+  SCAE_REQUIRE(G == 1 || part);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)((N + TQ - 1) / TQ), G);
+  const int rc = F <= FXR ? launch_search<FXR>(grid, st, x, N, x, N, F, k, 1, G, part, d2, idx)
+                          : launch_search<0>(grid, st, x, N, x, N, F, k, 1, G, part, d2, idx);
+  if (rc) return rc;
+  if (G > 1)
+    scae::launch(knn_merge_kernel, dim3((unsigned)((N + TM - 1) / TM)), dim3(TM), 0, st,
+                 (const uint64_t *)part, N, G, k, d2, idx);
+  return scae_launch_status();
+}
+
 extern "C" int scae_knn_vote_f32(const int64_t *idx, const float *d2, int64_t Nq, int k,
                                  const int64_t *base_labels, int64_t Nb, const int *ks, int n_ks,
                                  int weighted, int64_t *pred, void *stream) {

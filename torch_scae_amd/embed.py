@@ -45,6 +45,26 @@ to check the kernels.  Exact t-SNE, every pair, no approximation.  Both follow o
   the rows land in a buffer that is read once at the end;
 - every sum that crosses a lane, a workgroup or a column group is taken in a fixed order and there
   are no floating-point atomics: two runs give the same bits, whatever ``check_every`` is.
+
+The sparse form (``neighbors="auto"`` or an int K; ``affinities_knn`` / ``affinities_knn_host``;
+csrc/tsne_sparse.hip) keeps P on each row's K nearest neighbours and the repulsion exact over every
+pair: no (N, N) array, no Barnes-Hut, no FFT.  It follows the rules above with these differences:
+
+- input: 3 * perplexity <= K <= min(N - 1, ``MAX_NEIGHBORS`` = 128), F <= 256, 2 <= N <=
+  ``SPARSE_MAX_N`` = 262144; "auto" is K = ceil(3 * perplexity);
+- neighbour lists: ``neighbors.knn``'s rule in self mode -- d_ij = sum_f (x_if - x_jf)^2 in f
+  order, the difference, the product and the sum each rounded (no fused multiply-add), the
+  neighbours ascending by (d_ij, j) -- so the device's lists are ``neighbors.knn_host``'s bit for
+  bit (the host restatement takes them in its own ``dtype``, or the device's through ``lists``);
+- bandwidth: the same bisection over the row's K listed distances, shifted by the first (the
+  smallest); p_{j|i} = e_j / S for j in the list and 0 elsewhere;
+- joint affinities: P_ij = (p_{j|i} + p_{i|j}) / (2 N) on the union of the directed edges, as CSR
+  with a row's columns ascending and no diagonal: a stable sort of the integer keys i N + j over
+  the forward and the mirrored edges, then the sum of a key's one or two values -- symmetric bit
+  for bit.  sum P log P is taken once in fp64 over the stored entries;
+- iteration: the sums of P q (y_i - y_j) and P log1p(|y_i - y_j|^2) run over row i's stored
+  entries in column order, those of q^2 (y_i - y_j) and q over every j != i; everything after
+  the rows' sums is the dense form's.
 """
 import ctypes
 import math
@@ -54,12 +74,21 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import neighbors as _nb
 from .cluster import _P, _encode, _stream, features
 from .data import _M32, _philox
 
 MAX_N, MAX_F = _lib.TSNE_MAX_N, _lib.TSNE_MAX_F   # SCAE_TSNE_MAX_N / _F
+MAX_NEIGHBORS, SPARSE_MAX_N = _lib.TSNE_MAX_NEIGHBORS, _lib.TSNE_SPARSE_MAX_N
 _TAG_TSNE = 0x54534E45
 _ROWS = 256        # the host restatement's row chunk (memory, not arithmetic)
+
+
+class Csr(NamedTuple):
+    """The sparse joint affinities: row i holds columns indices[indptr[i]:indptr[i + 1]]."""
+    indptr: object               # (N + 1,) int64
+    indices: object              # (nnz,) int64, a row's columns ascending, no diagonal
+    values: object               # (nnz,)
 
 
 class TsneResult(NamedTuple):
@@ -84,15 +113,41 @@ def _check_x(x, perplexity):
         raise ValueError(f"perplexity = {perplexity}, N = {N}: needs 3 * perplexity <= N - 1")
 
 
+def _check_sparse(x, perplexity, neighbors):
+    """The sparse form's arguments -> K"""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+        raise ValueError("x must be an (N, F) tensor with N, F > 0")
+    N, F = x.shape
+    if N < 2 or N > SPARSE_MAX_N or F > MAX_F:
+        raise ValueError(f"N = {N}, F = {F}: sparse t-SNE takes 2 <= N <= {SPARSE_MAX_N}, "
+                         f"F <= {MAX_F}")
+    if isinstance(perplexity, bool) or not isinstance(perplexity, (int, float)) or \
+            not (perplexity > 0 and math.isfinite(perplexity)):
+        raise ValueError(f"perplexity must be a positive float, got {perplexity!r}")
+    if isinstance(neighbors, str) and neighbors == "auto":
+        K = math.ceil(3 * perplexity)
+    elif isinstance(neighbors, int) and not isinstance(neighbors, bool):
+        K = neighbors
+    else:
+        raise ValueError(f"neighbors must be None, 'auto' or an int, got {neighbors!r}")
+    if not 3 * perplexity <= K <= min(N - 1, MAX_NEIGHBORS):
+        raise ValueError(f"neighbors = {K}, perplexity = {perplexity}, N = {N}: needs "
+                         f"3 * perplexity <= neighbors <= min(N - 1, {MAX_NEIGHBORS})")
+    return K
+
+
 def _pos_int(name, v, least=1):
     if not isinstance(v, int) or isinstance(v, bool) or v < least:
         raise ValueError(f"{name} must be an int >= {least}, got {v!r}")
 
 
 def _args(x, perplexity, n_iter, early_exaggeration, exaggeration_iter, learning_rate, init,
-          check_every):
+          check_every, neighbors=None):
     """-> the learning rate as a float"""
-    _check_x(x, perplexity)
+    if neighbors is None:
+        _check_x(x, perplexity)
+    else:
+        _check_sparse(x, perplexity, neighbors)
     _pos_int("n_iter", n_iter)
     _pos_int("check_every", check_every)
     _pos_int("exaggeration_iter", exaggeration_iter, 0)
@@ -240,8 +295,109 @@ def affinities_host(x, perplexity=30.0, dtype=np.float64):
     return torch.from_numpy(P), torch.from_numpy(beta), plogp
 
 
+def neighbor_lists_host(x, K, dtype=np.float32):
+    """The self-mode lists of ``neighbors.knn_host`` for K up to ``MAX_NEIGHBORS``, arithmetic in
+    ``dtype`` -> KnnResult(idx (N, K) int64, d2 (N, K)) with CPU tensors."""
+    X = _nb._np(x, dtype)
+    N = X.shape[0]
+    idx, d2 = np.empty((N, K), dtype=np.int64), np.empty((N, K), dtype=dtype)
+    for lo, hi in _nb._chunks(N, N):
+        d = _nb._dist_rows(X, X, lo, hi)
+        d[np.arange(hi - lo), np.arange(lo, hi)] = np.inf
+        idx[lo:hi], d2[lo:hi] = _nb._least(d, K)
+    return _nb.KnnResult(torch.from_numpy(idx), torch.from_numpy(d2))
+
+
+def conditionals_knn_host(d2, beta, dtype=np.float64):
+    """-> (p_{j|i} of the listed neighbours (N, K), the rows' entropies H (N,)) at the given
+    ``beta``, from the lists' distances ``d2`` (N, K); arithmetic in ``dtype``."""
+    d2 = _np(d2, dtype)
+    H, e, S = _entropy(d2 - d2[:, :1], _np(beta, dtype))
+    return e / S[:, None], H
+
+
+def joint_knn_host(idx, cond, dtype=np.float64):
+    """The lists ``idx`` (N, K) and their conditional rows ``cond`` (N, K) -> (Csr of numpy arrays,
+    sum P log P (fp64)): the stable sort of the keys i N + j over the forward, then the mirrored
+    edges, a key's one or two values added in that order, / (2 N)."""
+    idx, c = _np(idx, np.int64), _np(cond, dtype).reshape(-1)
+    N, K = idx.shape
+    i, j = np.repeat(np.arange(N, dtype=np.int64), K), idx.reshape(-1)
+    keys, v = np.concatenate([i * N + j, j * N + i]), np.concatenate([c, c])
+    order = np.argsort(keys, kind="stable")
+    keys, v = keys[order], v[order]
+    first = np.ones(len(keys), dtype=bool)
+    first[1:] = keys[1:] != keys[:-1]
+    pos = np.nonzero(first)[0]
+    nxt = np.minimum(pos + 1, len(keys) - 1)
+    twice = (pos + 1 < len(keys)) & ~first[nxt]
+    values = ((v[pos] + np.where(twice, v[nxt], dtype(0))) / dtype(2 * N)).astype(dtype)
+    indptr = np.searchsorted(keys[pos], np.arange(N + 1, dtype=np.int64) * N).astype(np.int64)
+    p = values[values > 0].astype(np.float64)
+    return Csr(indptr, keys[pos] % N, values), float((p * np.log(p)).sum())
+
+
+def affinities_knn_host(x, perplexity=30.0, neighbors="auto", dtype=np.float64, lists=None):
+    """``affinities_knn`` in numpy -> (indptr, indices, values, beta, sum P log P) with CPU tensors,
+    values and beta in ``dtype``.  ``lists`` = (idx, d2): neighbour lists to use instead of the
+    host's own (the tests hand it the device's)."""
+    K = _check_sparse(x, perplexity, neighbors)
+    idx, d2 = neighbor_lists_host(x, K, dtype) if lists is None else lists
+    if tuple(idx.shape) != (x.shape[0], K) or tuple(d2.shape) != (x.shape[0], K):
+        raise ValueError(f"lists must be (idx, d2), each ({x.shape[0]}, {K})")
+    d2 = _np(d2, dtype)
+    beta = bandwidths_host(d2 - d2[:, :1], perplexity, dtype)
+    csr, plogp = joint_knn_host(idx, conditionals_knn_host(d2, beta, dtype)[0], dtype)
+    return tuple(torch.from_numpy(a) for a in csr) + (torch.from_numpy(beta), plogp)
+
+
+def densify(indptr, indices, values):
+    """The CSR as a dense (N, N) numpy array of the values' dtype (tests, small N)."""
+    indptr, indices, values = (np.asarray(torch.as_tensor(a).cpu()) for a in
+                               (indptr, indices, values))
+    N = len(indptr) - 1
+    P = np.zeros((N, N), dtype=values.dtype)
+    P[np.repeat(np.arange(N), np.diff(indptr)), indices] = values
+    return P
+
+
+def pair_sums_host(Y, dtype=np.float64, rows=None):
+    """The repulsion's sums over every j != i for the given ``rows`` (all by default), in
+    ``dtype`` -> dict(rep (R, 2), z (R,))."""
+    Y = _np(Y, dtype)
+    rows = np.arange(Y.shape[0]) if rows is None else np.asarray(rows)
+    rep, z = np.empty((len(rows), 2), dtype=dtype), np.empty(len(rows), dtype=dtype)
+    for lo in range(0, len(rows), _ROWS):
+        r = rows[lo:lo + _ROWS]
+        dy0 = Y[r, None, 0] - Y[None, :, 0]
+        dy1 = Y[r, None, 1] - Y[None, :, 1]
+        q = dtype(1) / (dtype(1) + (dy0 * dy0 + dy1 * dy1))
+        q[np.arange(len(r)), r] = 0
+        q2 = q * q
+        rep[lo:lo + _ROWS, 0], rep[lo:lo + _ROWS, 1] = (q2 * dy0).sum(1), (q2 * dy1).sum(1)
+        z[lo:lo + _ROWS] = q.sum(1)
+    return dict(rep=rep, z=z)
+
+
+def edge_sums_host(P, Y, dtype=np.float64):
+    """The attraction's and the KL's sums over the stored entries of the Csr ``P`` (every row
+    has some), in ``dtype`` -> dict(att (N, 2), kl (N,))."""
+    indptr, cols = (np.asarray(torch.as_tensor(a).cpu()) for a in P[:2])
+    v, Y = _np(P[2], dtype), _np(Y, dtype)
+    i = np.repeat(np.arange(len(indptr) - 1), np.diff(indptr))
+    dy0, dy1 = Y[i, 0] - Y[cols, 0], Y[i, 1] - Y[cols, 1]
+    d = dy0 * dy0 + dy1 * dy1
+    pq = v * (dtype(1) / (dtype(1) + d))
+    at = indptr[:-1]
+    att = np.stack([np.add.reduceat(pq * dy0, at), np.add.reduceat(pq * dy1, at)], 1)
+    return dict(att=att.astype(dtype), kl=np.add.reduceat(v * np.log1p(d), at).astype(dtype))
+
+
 def row_sums_host(P, Y, dtype=np.float64):
-    """The rows' sums over j in ``dtype`` -> dict(att (N, 2), rep (N, 2), z (N,), kl (N,))."""
+    """The rows' sums over j in ``dtype`` -> dict(att (N, 2), rep (N, 2), z (N,), kl (N,)).
+    ``P``: the dense (N, N) matrix, or the sparse form's ``Csr``."""
+    if isinstance(P, Csr):
+        return {**edge_sums_host(P, Y, dtype), **pair_sums_host(Y, dtype)}
     P, Y = _np(P, dtype), _np(Y, dtype)
     N = Y.shape[0]
     att, rep = np.empty((N, 2), dtype=dtype), np.empty((N, 2), dtype=dtype)
@@ -293,13 +449,18 @@ def _schedule(it, exaggeration_iter, early_exaggeration):
 
 
 def tsne_host(x, perplexity=30.0, n_iter=1000, early_exaggeration=12.0, exaggeration_iter=250,
-              learning_rate="auto", init="pca", seed=0, check_every=50, dtype=np.float64):
+              learning_rate="auto", init="pca", seed=0, check_every=50, dtype=np.float64,
+              neighbors=None):
     """``tsne`` in numpy (the kernels' check; CPU tensors take it), fp64 or, with
     ``dtype=np.float32``, the same arithmetic in fp32.  -> TsneResult with CPU tensors."""
     lr = _args(x, perplexity, n_iter, early_exaggeration, exaggeration_iter, learning_rate, init,
-               check_every)
-    P, beta, plogp = affinities_host(x, perplexity, dtype)
-    P = P.numpy()
+               check_every, neighbors)
+    if neighbors is None:
+        P, beta, plogp = affinities_host(x, perplexity, dtype)
+        P = P.numpy()
+    else:
+        *csr, beta, plogp = affinities_knn_host(x, perplexity, neighbors, dtype)
+        P = Csr(*(a.numpy() for a in csr))
     Y = _init(x, init, seed).numpy().astype(dtype)
     vel, gains = np.zeros_like(Y), np.ones_like(Y)
     hist = []
@@ -346,6 +507,109 @@ def affinities(x, perplexity=30.0):
     return P, beta, float(plogp)
 
 
+def neighbor_lists(x, K):
+    """The K nearest other rows of every row of ``x`` (N, F), ``neighbors.knn``'s self mode for
+    1 <= K <= min(N - 1, ``MAX_NEIGHBORS``): the lists the sparse affinities are built on.
+    -> KnnResult(idx (N, K) int64, d2 (N, K)); CPU tensors take ``neighbor_lists_host``."""
+    _check_sparse(x, 1.0 / 3.0, K)       # (the perplexity that admits every K >= 1)
+    if not x.is_cuda:
+        return neighbor_lists_host(x, K)
+    x = _device_x(x)
+    (N, F), dev = x.shape, x.device
+    G = _lib.load().scae_knn_groups(N, N)
+    part = torch.empty(N * G * K, device=dev, dtype=torch.int64) if G > 1 else None
+    d2 = torch.empty(N, K, device=dev)
+    idx = torch.empty(N, K, device=dev, dtype=torch.int64)
+    _lib.call("scae_knn_wide_f32", _P(x), N, F, K, _P(part), _P(d2), _P(idx), _stream(x))
+    return _nb.KnnResult(idx, d2)
+
+
+def _joint_knn_device(idx, cond):
+    """``joint_knn_host`` in torch ops on the lists' device (integer sorts: deterministic)
+    -> (Csr, sum P log P as a (1,) fp64 tensor)"""
+    (N, K), dev = idx.shape, idx.device
+    i = torch.arange(N, device=dev).repeat_interleave(K)
+    j, c = idx.reshape(-1), cond.reshape(-1)
+    keys, order = torch.sort(torch.cat([i * N + j, j * N + i]), stable=True)
+    v = torch.cat([c, c])[order]
+    first = torch.ones_like(keys, dtype=torch.bool)
+    first[1:] = keys[1:] != keys[:-1]
+    pos = first.nonzero().squeeze(1)
+    nxt = (pos + 1).clamp_(max=keys.numel() - 1)
+    twice = (pos + 1 < keys.numel()) & ~first[nxt]
+    # (a tensor divisor: a Python scalar would be turned into a multiplication by 1 / (2 N))
+    values = (v[pos] + torch.where(twice, v[nxt], torch.zeros_like(c[:1]))) / \
+        torch.full((1,), float(2 * N), device=dev)
+    ukeys = keys[pos]
+    indptr = torch.searchsorted(ukeys, torch.arange(N + 1, device=dev) * N)
+    p = values.double()
+    plogp = torch.where(p > 0, p * torch.log(p), torch.zeros_like(p)).sum().reshape(1)
+    return Csr(indptr, ukeys % N, values), plogp
+
+
+def _affinities_knn_device(x, perplexity, K):
+    """-> (Csr, beta (N,), sum P log P as a (1,) fp64 device tensor)"""
+    idx, d2 = neighbor_lists(x, K)
+    N = x.shape[0]
+    cond, beta = torch.empty(N, K, device=x.device), torch.empty(N, device=x.device)
+    _lib.call("scae_tsne_knn_bandwidths_f32", _P(d2), N, K, float(perplexity), _P(cond),
+              _P(beta), _stream(x))
+    csr, plogp = _joint_knn_device(idx, cond)
+    return csr, beta, plogp
+
+
+def affinities_knn(x, perplexity=30.0, neighbors="auto"):
+    """The sparse joint affinities of the rows of ``x`` (N, F) on their K nearest neighbours
+    (``neighbors``: "auto" = ceil(3 * perplexity), or K): -> (indptr (N + 1,) int64, indices
+    (nnz,) int64, values (nnz,), beta (N,), sum P log P), a row's columns ascending, no diagonal.
+    Device tensors (fp32) run on the kernels, CPU tensors take ``affinities_knn_host`` (fp64)."""
+    K = _check_sparse(x, perplexity, neighbors)
+    if not x.is_cuda:
+        return affinities_knn_host(x, perplexity, K)
+    csr, beta, plogp = _affinities_knn_device(_device_x(x), perplexity, K)
+    return csr + (beta, float(plogp))
+
+
+class _SparseProblem:
+    """``_TsneProblem`` for the sparse form: the device state of one run over a Csr."""
+
+    def __init__(self, csr, plogp, Y0, n_iter, early_exaggeration, exaggeration_iter,
+                 learning_rate, check_every):
+        N, dev = csr.indptr.numel() - 1, csr.values.device
+        self.indptr = csr.indptr.contiguous()
+        self.cols = csr.indices.to(torch.int32).contiguous()
+        self.vals = csr.values.contiguous()
+        self.plogp = torch.as_tensor(plogp, dtype=torch.float64).reshape(1).to(dev)
+        self.Y = torch.as_tensor(Y0).to(dev, torch.float32).contiguous().clone()
+        self.velocity = torch.zeros(N, 2, device=dev)
+        self.gains = torch.ones(N, 2, device=dev)
+        G = _lib.load().scae_tsne_sparse_groups(N)
+        self.part = torch.empty(3 * G * N, device=dev)
+        self.rows = torch.zeros(6 * N, device=dev)
+        self.block = torch.zeros(_lib.TSNE_SPARSE_BLOCK_DOUBLES, device=dev, dtype=torch.float64)
+        self.history = torch.zeros(-(-n_iter // check_every), _lib.TSNE_HISTORY_COLS, device=dev,
+                                   dtype=torch.float64)
+        d = self.desc = _lib.TsneSparseDesc()
+        d.N, d.G, d.n_iter, d.exaggeration_iter, d.check_every = \
+            N, G, n_iter, exaggeration_iter, check_every
+        d.early_exaggeration, d.learning_rate = early_exaggeration, learning_rate
+        d.indptr, d.cols, d.vals, d.nnz = (self.indptr.data_ptr(), self.cols.data_ptr(),
+                                           self.vals.data_ptr(), self.vals.numel())
+        d.Y, d.velocity, d.gains = (self.Y.data_ptr(), self.velocity.data_ptr(),
+                                    self.gains.data_ptr())
+        d.part, d.rows, d.block = self.part.data_ptr(), self.rows.data_ptr(), self.block.data_ptr()
+        d.plogp, d.history = self.plogp.data_ptr(), self.history.data_ptr()
+
+    def load_state(self, Y, velocity, gains):
+        self.Y.copy_(torch.as_tensor(Y).to(self.Y))
+        self.velocity.copy_(torch.as_tensor(velocity).to(self.Y))
+        self.gains.copy_(torch.as_tensor(gains).to(self.Y))
+
+    def run(self, first_iter, n):
+        _lib.call("scae_tsne_sparse_run_f32", ctypes.byref(self.desc), first_iter, n,
+                  _stream(self.Y))
+
+
 class _TsneProblem:
     """The device state of one run over a given P: Y, velocity, gains, the partials, the history
     and the descriptor; ``run(first_iter, n)`` enqueues iterations.  ``tsne`` drives it; the tests
@@ -384,20 +648,28 @@ class _TsneProblem:
 
 
 def tsne(x, perplexity=30.0, n_iter=1000, early_exaggeration=12.0, exaggeration_iter=250,
-         learning_rate="auto", init="pca", seed=0, check_every=50):
+         learning_rate="auto", init="pca", seed=0, check_every=50, neighbors=None):
     """Exact t-SNE of the rows of ``x`` (N, F) into two dimensions.  ``init``: "pca", "random"
-    (seeded by ``seed``) or an (N, 2) tensor.  On the device the affinities and all ``n_iter``
-    iterations are enqueued with no read until the end; CPU tensors take ``tsne_host``.
-    -> TsneResult."""
+    (seeded by ``seed``) or an (N, 2) tensor.  ``neighbors``: None for the dense (N, N) affinities
+    (N <= ``MAX_N``), "auto" or an int K for the sparse form on each row's K nearest neighbours
+    (N <= ``SPARSE_MAX_N``; the repulsion stays exact).  On the device the affinities and all
+    ``n_iter`` iterations are enqueued with no read until the end; CPU tensors take
+    ``tsne_host``.  -> TsneResult."""
     lr = _args(x, perplexity, n_iter, early_exaggeration, exaggeration_iter, learning_rate, init,
-               check_every)
+               check_every, neighbors)
     if not x.is_cuda:
         return tsne_host(x, perplexity, n_iter, early_exaggeration, exaggeration_iter,
-                         learning_rate, init, seed, check_every)
+                         learning_rate, init, seed, check_every, neighbors=neighbors)
     x = _device_x(x)
-    P, beta, plogp = _affinities_device(x, perplexity)
-    p = _TsneProblem(P, plogp, _init(x, init, seed), n_iter, float(early_exaggeration),
-                     exaggeration_iter, lr, check_every)
+    if neighbors is None:
+        P, beta, plogp = _affinities_device(x, perplexity)
+        p = _TsneProblem(P, plogp, _init(x, init, seed), n_iter, float(early_exaggeration),
+                         exaggeration_iter, lr, check_every)
+    else:
+        csr, beta, plogp = _affinities_knn_device(x, perplexity,
+                                                  _check_sparse(x, perplexity, neighbors))
+        p = _SparseProblem(csr, plogp, _init(x, init, seed), n_iter, float(early_exaggeration),
+                           exaggeration_iter, lr, check_every)
     p.run(0, n_iter)
     hist = p.history.cpu()
     return TsneResult(p.Y, float(hist[-1, 1]), hist, beta, n_iter)
