@@ -1960,6 +1960,44 @@ typedef struct scae_tsne_sparse_desc {
  * schedule, history rows and final evaluation; nothing is read back. */
 int scae_tsne_sparse_run_f32(const scae_tsne_sparse_desc *d, int first_iter, int n, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Cluster quality (csrc/cluster_quality.hip): the exact silhouette of a labelling of x (N, F) and
+ * the per-cluster tables behind the Calinski-Harabasz and Davies-Bouldin indices.  No float
+ * atomics, every sum in a fixed order that no launch geometry changes: two runs give the same
+ * bits.  The caller sorts the rows by (label, row) with a stable integer sort: xs (N, F) the
+ * sorted rows, ls (N) their clusters, order (N) their original rows, off (k + 1) the clusters'
+ * first positions (cluster_quality.py does it on the device).
+ *   d_ij = sqrt(sum_f (x_if - x_jf)^2): the squared distance by the k-NN search's rule (f order,
+ *   the difference, the product and the sum each rounded to fp32, no fused multiply-add), the
+ *   correctly rounded fp32 root, then widened to fp64.
+ *   D_i(c) = the fp64 sum of d_ij over cluster c's rows j != i in ascending row order;
+ *   a_i = D_i(c(i)) / (n_c(i) - 1); b_i = min over non-empty c != c(i) of D_i(c) / n_c, nearest_i
+ *   the lowest c that attains it; s_i = (b_i - a_i) / max(a_i, b_i).  s_i = 0 when n_c(i) = 1
+ *   (then a_i = 0), when no other cluster is non-empty (then b_i = +inf, nearest_i = -1) or when
+ *   max(a_i, b_i) = 0.  The self pair is skipped by row, not by d = 0.
+ * ------------------------------------------------------------------------ */
+#define SCAE_CLUSTER_QUALITY_MAX_F 256
+/* 1 for 1 <= N < 2^31, 1 <= F <= SCAE_CLUSTER_QUALITY_MAX_F and 1 <= k < 2^31 - 1, else 0 */
+int scae_cluster_quality_supported(int64_t N, int F, int64_t k);
+/* labels (N) int64 -> lab32 (N) int32 clamped into [0, k); *outside (zeroed by the caller) counts
+ * the labels that were outside */
+int scae_cluster_quality_labels(const int64_t *labels, int64_t N, int64_t k, int *lab32,
+                                int *outside, void *stream);
+/* -> values, a, b (N) fp64 and nearest (N) int64 in the original row order, sorted_values (N)
+ * the values in sorted order (workspace), scores (k + 1): the mean of each cluster's values (the
+ * fp64 sum in row order over n_c; NaN for an empty cluster) and, last, the mean of all values
+ * (the fp64 sum in row order over N).  One row per lane, the sorted rows streamed through LDS;
+ * a second launch for the scores. */
+int scae_cluster_quality_silhouette_f32(const float *xs, const int *ls, const int64_t *off,
+                                        const int64_t *order, int64_t N, int F, int64_t k,
+                                        double *values, double *a, double *b, int64_t *nearest,
+                                        double *sorted_values, double *scores, void *stream);
+/* -> table (k, F + 3) fp64, row c = (n_c, the mean m_c (F), W_c = sum |x_i - m_c|^2,
+ * S_c = the mean of |x_i - m_c|), fp64 sums in a fixed order; an empty cluster's row is
+ * (0, NaN.., 0, NaN).  One workgroup per cluster. */
+int scae_cluster_quality_dispersion_f32(const float *xs, const int64_t *off, int64_t N, int F,
+                                        int64_t k, double *table, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

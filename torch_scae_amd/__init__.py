@@ -7,6 +7,7 @@ from . import (cv_ops, distributions, factory, general_utils, math_ops,  # noqa
                nn_ext, nn_utils, object_decoder, ops, part_decoder,
                part_encoder, set_transformer, stacked_capsule_auto_encoder)
 from . import cluster  # noqa
+from . import cluster_quality  # noqa
 from . import probe  # noqa
 from . import embed  # noqa
 from . import neighbors  # noqa

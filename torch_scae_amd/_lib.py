@@ -421,6 +421,10 @@ SIGNATURES = {
     "scae_knn_f32": [P, c_int64, P, c_int64, c_int, c_int, c_int, P, P, P, P],
     "scae_knn_vote_f32": [P, P, c_int64, c_int, P, c_int64, POINTER(c_int), c_int, c_int, P, P],
     "scae_knn_ranks_f32": [P, c_int64, c_int, P, c_int, P, P, P, P, P],
+    "scae_cluster_quality_supported": [c_int64, c_int, c_int64],
+    "scae_cluster_quality_labels": [P, c_int64, c_int64, P, P, P],
+    "scae_cluster_quality_silhouette_f32": [P, P, P, P, c_int64, c_int, c_int64] + [P] * 7,
+    "scae_cluster_quality_dispersion_f32": [P, P, c_int64, c_int, c_int64, P, P],
     "scae_template_render_fwd_f32": [POINTER(DecoderDesc), P, P, P],
     "scae_render_gmm_logprob_fwd_f32": [POINTER(DecoderDesc), P, P, P, P, P],
     "scae_render_gmm_bwd_f32": [POINTER(DecoderDesc)] + [P] * 12 + [P],
@@ -458,6 +462,7 @@ TSNE_SPARSE_BLOCK_DOUBLES = 5120   # SCAE_TSNE_SPARSE_BLOCK_DOUBLES
 KNN_MAX_K = 64               # SCAE_KNN_MAX_K
 KNN_MAX_F = 256              # SCAE_KNN_MAX_F
 KNN_MAX_KS = 8               # SCAE_KNN_MAX_KS
+CLUSTER_QUALITY_MAX_F = 256  # SCAE_CLUSTER_QUALITY_MAX_F
 EVAL_SINK_INT64S = 4         # struct scae_eval_sink: rows, capacity, cursor, overflow
 # struct scae_eval_records: rows, capacity, cursor, overflow, confusion, ncls, labelled
 EVAL_RECORDS_INT64S = 7

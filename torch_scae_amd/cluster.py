@@ -367,13 +367,16 @@ def _encode(step, split):
 
 
 def unsupervised_accuracy(step, fit, *others, k=10, feature="prior", names=None,
-                          n_classes=None, **kmeans_args):
+                          n_classes=None, metrics=False, **kmeans_args):
     """k-means on the object-capsule features of split ``fit`` (encoded by the EvalStep
     ``step``), clusters matched to classes on ``fit``'s contingency table, and that mapping
     applied to ``others`` under the fitted centroids.  Splits are (images, labels) pairs or
     data.DatasetView objects; ``names`` names ``others`` (default "test" for one, else
     "split1", "split2", ...).  -> {"fit_accuracy", "<name>_accuracy"..., "inertia",
-    "mapping", "n_iter"}."""
+    "mapping", "n_iter"}.  ``metrics=True`` adds the figures that need no matching
+    (``cluster_quality``): "fit_nmi", "fit_ari", "fit_purity", "<name>_nmi", "<name>_ari",
+    "<name>_purity", and of the fit split's clustering "silhouette", "calinski_harabasz",
+    "davies_bouldin"."""
     if names is None:
         names = ["test"] if len(others) == 1 else [f"split{i + 1}" for i in range(len(others))]
     if len(names) != len(others):
@@ -383,12 +386,27 @@ def unsupervised_accuracy(step, fit, *others, k=10, feature="prior", names=None,
     enc = _encode(step, fit)
     if n_classes is None:
         n_classes = int(enc["label"].max()) + 1
-    res = kmeans(features(enc, feature), k, **kmeans_args)
+    xf = features(enc, feature)
+    res = kmeans(xf, k, **kmeans_args)
     mapping, acc = match_clusters(res.labels, enc["label"], k, n_classes)
     out = {"fit_accuracy": acc}
+    if metrics:
+        from . import cluster_quality as Q       # (it imports this module)
+
+        def label_figures(name, cid, lab):
+            ind = Q.label_indices_of(cid, lab, k, n_classes)
+            out.update({f"{name}_{m}": ind[m] for m in ("nmi", "ari", "purity")})
+
+        label_figures("fit", res.labels, enc["label"])
     for name, split in zip(names, others):
         e = _encode(step, split)
         cid = assign(features(e, feature), res.centroids)
         out[f"{name}_accuracy"] = mapped_accuracy(cid, e["label"], mapping, n_classes)
+        if metrics:
+            label_figures(name, cid, e["label"])
+    if metrics:
+        sil, disp = Q.quality(xf, res.labels, k)
+        out.update(silhouette=sil.score, calinski_harabasz=disp.calinski_harabasz,
+                   davies_bouldin=disp.davies_bouldin)
     out.update(inertia=res.inertia, mapping=mapping, n_iter=res.n_iter)
     return out
