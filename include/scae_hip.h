@@ -1852,8 +1852,8 @@ typedef struct scae_tsne_desc {
   double *history;           /* (ceil(n_iter / check_every), SCAE_TSNE_HISTORY_COLS) */
 } scae_tsne_desc;
 /* iterations first_iter .. first_iter + n - 1, four launches each: the gradient's partials per
- * (row block, column group), the rows' sums in g order, the update, and a one-workgroup
- * recentring.  An iteration it > 0 that is a multiple of check_every also records
+ * (row block, column group), the rows' sums in g order, the update, and the recentring on
+ * the update's grid.  An iteration it > 0 that is a multiple of check_every also records
  * (it, KL, |g|) of the Y it starts from in history row it / check_every - 1 (its gradient
  * launch is the form that adds P log1p(d)); when first_iter + n == n_iter a last evaluation
  * without an update records (n_iter, KL, |g|) of the result in the last row.  Nothing is read

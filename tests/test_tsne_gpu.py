@@ -26,6 +26,8 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(4, 1, 1.0), (63, 3, 5.0), (64, 24, 10.0), (65, 24, 21.0), (257, 255, 30.0),
           (4099, 24, 30.0)]
+# for one iteration besides: two update workgroups and a nearly empty third (the recentring's grid)
+ITERATION_SHAPES = SHAPES + [(513, 24, 30.0)]
 
 
 def _input(N, F, kind):
@@ -57,7 +59,7 @@ def test_affinities_from_the_devices_own_beta(N, F, perplexity, kind):
 def _joint(N):
     """The device's P of the uniform input at N -> (P on the device, P fp32 numpy, sum P log P
     of those fp32 values in fp64)."""
-    _, F, perplexity = next(s for s in SHAPES if s[0] == N)
+    _, F, perplexity = next(s for s in ITERATION_SHAPES if s[0] == N)
     P, _, _ = E.affinities(uniform(N, F, 20 + N).cuda(), perplexity)
     Pn = P.cpu().numpy()
     pos = Pn[Pn > 0].astype(np.float64)
@@ -82,7 +84,7 @@ def clear_gains(h32, h64):
 
 
 @pytest.mark.parametrize("scale, it", [(1e-4, 3), (5.0, 300)])
-@pytest.mark.parametrize("N", [s[0] for s in SHAPES])
+@pytest.mark.parametrize("N", [s[0] for s in ITERATION_SHAPES])
 def test_one_iteration_from_a_chosen_state(N, scale, it):
     case = f"(N = {N}, Y ~ {scale}, iteration {it})"
     P, Pn, plogp = _joint(N)
@@ -101,7 +103,16 @@ def test_one_iteration_from_a_chosen_state(N, scale, it):
     print(f"{case} fp32-host gradient error "
           f"{float(np.abs(h32['grad'] - h64['grad']).max()):.3e} against "
           f"{float(np.abs(h64['grad']).max()):.3e}")
-    within("Y", p.Y.cpu().numpy(), h32["Y"], h64["Y"], case)
+    got = p.Y.cpu().numpy()
+    within("Y", got, h32["Y"], h64["Y"], case)
+    # every workgroup of the finish launch recentres its own rows: the columns sum to zero
+    # (test_bits_repeat's bar), and each workgroup's first and last row moved by the host's amount
+    assert float(np.abs(got.astype(np.float64).mean(0)).max()) <= 1e-6 * float(np.abs(got).max())
+    m32, m64 = h32["Y"].astype(np.float64) - Y, h64["Y"] - Y
+    ends = sorted({0, min(255, N - 1), min(256, N - 1), N - 1})
+    err = float(np.abs((got.astype(np.float64) - Y - m64)[ends]).max())
+    print(f"{case} movement of rows {ends}: error {err:.3e} (bar {bar(m32, m64):.3e})")
+    assert err <= bar(m32, m64), (case, ends, err)
     within("velocity", p.velocity.cpu().numpy(), h32["velocity"], h64["velocity"], case)
     hist = p.history.cpu().numpy()
     assert hist[it - 1, 0] == it and not hist[:it - 1].any() and not hist[it:].any()

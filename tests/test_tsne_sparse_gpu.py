@@ -161,6 +161,40 @@ def test_one_iteration_with_every_pair_stored_is_the_dense_step(scale, it):
     _one_iteration((66, 3, 65), scale, it, dense=True)
 
 
+def test_one_update_kernel_two_strides():
+    """The dense and the sparse path run one update kernel over ``block`` rows 128 and 1024
+    apart.  N = 300 (two update workgroups), every pair stored with P = 2^-17, Y on (0, 0) and
+    (1, 0): d is 0 or 1, q 1 or 1/2, every term of every sum a multiple of a power of two, so both
+    paths leave the same ``rows`` whatever their order of summation (checked), and the partials
+    of y0, y1 and |g|^2 -- from random velocities and gains -- must agree bit for bit, segment k
+    of one at k x its stride with segment k of the other."""
+    N, nb, lr = 300, 2, 50.0
+    rng = np.random.default_rng(5)
+    Y = np.stack([rng.integers(0, 2, N), np.zeros(N)], 1).astype(np.float32)
+    vel = (0.1 * rng.standard_normal((N, 2))).astype(np.float32)
+    gains = rng.uniform(0.01, 2.0, (N, 2)).astype(np.float32)
+    P = torch.full((N, N), 2.0 ** -17).fill_diagonal_(0.0).cuda()
+    off = ~torch.eye(N, dtype=torch.bool)
+    csr = E.Csr(torch.arange(N + 1, dtype=torch.int64).cuda() * (N - 1),
+                torch.arange(N).repeat(N, 1)[off].cuda(), P.cpu()[off].cuda())
+    dense = E._TsneProblem(P, 0.0, torch.zeros(N, 2), 1000, 12.0, 250, lr, 1)
+    sparse = E._SparseProblem(csr, 0.0, torch.zeros(N, 2), 1000, 12.0, 250, lr, 1)
+    for p in (dense, sparse):
+        p.load_state(Y, vel, gains)
+        p.run(3, 1)
+    torch.cuda.synchronize()
+    assert torch.equal(dense.rows[:5 * N], sparse.rows[:5 * N]) and bool(dense.rows[:N].any())
+    sd, ss = _lib.TSNE_BLOCK_DOUBLES // 5, _lib.TSNE_SPARSE_BLOCK_DOUBLES // 5
+    assert (sd, ss) == (128, 1024)
+    for k, name in ((0, "Z"), (2, "y0"), (3, "y1"), (4, "|g|^2")):
+        a, b = dense.block[k * sd:k * sd + nb], sparse.block[k * ss:k * ss + nb]
+        print(f"{name}: dense {a.tolist()}, sparse {b.tolist()}")
+        assert torch.equal(a, b) and bool((a != 0).all()), name
+        assert not bool(dense.block[k * sd + nb:(k + 1) * sd].any())
+        assert not bool(sparse.block[k * ss + nb:(k + 1) * ss].any())
+    assert torch.equal(dense.Y, sparse.Y) and torch.equal(dense.gains, sparse.gains)
+
+
 @pytest.mark.parametrize("shape", [RING, SPHERE])
 def test_a_hub_row(shape):
     """A ring in the plane, and a sphere in 64 dimensions.  In the plane a ring point

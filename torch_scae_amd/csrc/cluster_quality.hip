@@ -2,10 +2,10 @@
 // all-pairs pass over the features -- its mean per cluster and overall, and the per-cluster
 // centroid / scatter tables behind the Calinski-Harabasz and Davies-Bouldin indices.
 //
-// MUST BE COMPILED WITH -ffp-contract=off (csrc/Makefile gives this file the flag): the squared
-// distance is knn.hip's -- the difference, the product and the sum each rounded to fp32, f order
-// -- and the fp64 sums and quotients below are each rounded once as well, which is what numpy
-// does; under HIP's default -ffp-contract=fast the backend would fuse products into sums.
+// MUST BE COMPILED WITH -ffp-contract=off (csrc/Makefile gives this file the flag): the fp64
+// sums and quotients below are each rounded once, which is what numpy does; under HIP's default
+// -ffp-contract=fast the backend would fuse products into sums.  The squared distance is
+// row_dist_dev.h's, which keeps contraction off for itself.
 // sqrtf / sqrt / the fp64 divide are the correctly rounded ones (hipcc's default, no fast-math).
 //
 // The rows arrive sorted by (label, row) (a stable integer sort, cluster_quality.py): cluster c
@@ -13,10 +13,10 @@
 //
 //   cq_labels_kernel      labels -> int32 clamped into [0, k), the ones outside counted (an
 //                         integer atomic, as the contingency table counts them);
-//   cq_silhouette_kernel  knn.hip's tiling with one row i per lane (its features in registers up
-//                         to F = 32, read from memory above): every sorted row streamed through
-//                         LDS in tiles and read as a broadcast, d_ij = sqrtf(d2) widened to fp64
-//                         and added to the lane's ONE running sum of the cluster being streamed.
+//   cq_silhouette_kernel  row_dist_dev.h's tile and distance with one row i per lane over
+//                         every sorted row (the tile rows' clusters staged beside it), d_ij =
+//                         sqrtf(d2) widened to fp64 and added to the lane's ONE running sum
+//                         of the cluster being streamed.
 //                         Every lane meets the same row at the same time, so the end of a
 //                         cluster is wave-uniform: there the sum becomes a's numerator (own
 //                         cluster) or, over n_c, a candidate for the running (b, nearest) minimum
@@ -32,42 +32,15 @@
 //                         are added in order), then W_c = sum |x_i - m_c|^2 and S_c = the mean of
 //                         |x_i - m_c| (row r to thread r mod 256, the threads added in order).
 #include "common.h"
+#include "row_dist_dev.h"
 
 namespace {
+using namespace scae_rows;
 constexpr int TQ = 64;             // rows of a silhouette workgroup, one per lane: one wave, so
                                    // that N = 10^4 still gives 157 workgroups
-constexpr int TILE_FLOATS = 4096;  // the base tile in LDS (16 KiB)
 constexpr int TILE_ROWS = TILE_FLOATS / 4;   // rows of a tile at most (F4 = 4)
 constexpr int FXR = 32;            // features held in registers by the register form
 constexpr int TR = 256;            // score / dispersion / label workgroup
-
-// knn.hip's distance: the difference, the product and the sum each rounded to fp32
-__device__ __forceinline__ float sq_add(float d, float a, float b) {
-  const float u = __fsub_rn(a, b);
-  return __fadd_rn(d, __fmul_rn(u, u));
-}
-
-// squared distance of the row (registers xr, FX > 0, zero above F; or global row xp) to the
-// base row at b in LDS, padded with zeros to F4 = 4 * ceil(F / 4) floats (a zero pair adds +0)
-template <int FX>
-__device__ __forceinline__ float dist2(const float (&xr)[FX > 0 ? FX : 1], const float *xp,
-                                       const float *b, int F, int F4) {
-  float d = 0.f;
-  if constexpr (FX > 0) {
-#pragma unroll
-    for (int f = 0; f < FX; f += 4)
-      if (f < F4) {
-        const float4 v = *reinterpret_cast<const float4 *>(b + f);
-        d = sq_add(d, xr[f], v.x);
-        d = sq_add(d, xr[f + 1], v.y);
-        d = sq_add(d, xr[f + 2], v.z);
-        d = sq_add(d, xr[f + 3], v.w);
-      }
-  } else {
-    for (int f = 0; f < F; ++f) d = sq_add(d, xp[f], b[f]);
-  }
-  return d;
-}
 
 __global__ __launch_bounds__(TR) void cq_labels_kernel(const int64_t *labels, int64_t N, int k,
                                                        int *lab32, int *outside) {
@@ -89,8 +62,7 @@ __global__ __launch_bounds__(TQ) void cq_silhouette_kernel(
   const int t = threadIdx.x;
   const int64_t p = (int64_t)blockIdx.x * TQ + t;
   const bool active = p < N;
-  const int F4 = (F + 3) & ~3;
-  const int TB = (TILE_FLOATS / F4) & ~3;   // rows of a tile: a multiple of four, >= 16
+  const TileGeom tg = tile_geom(F);
   const float *xp = xs + (active ? p : 0) * F;
   float xr[FX > 0 ? FX : 1];
   if constexpr (FX > 0) {
@@ -100,12 +72,13 @@ __global__ __launch_bounds__(TQ) void cq_silhouette_kernel(
   const int own = ls[active ? p : 0];
   double run = 0.0, own_sum = 0.0, b = __longlong_as_double(0x7FF0000000000000ll);
   int near = -1;
-  for (int64_t row0 = 0; row0 < N; row0 += TB) {
+  for (int64_t row0 = 0; row0 < N; row0 += tg.TB) {
     const int64_t left = N - row0;
-    const int rows = left < TB ? (int)left : TB;
+    const int rows = left < tg.TB ? (int)left : tg.TB;
     __syncthreads();   // (the previous tile has been read)
-    for (int e = t; e < TB * F4; e += TQ) {
-      const int r = e / F4, f = e - r * F4;
+    // (row_dist_dev.h's load_tile writes the same tile; this 32-bit row test is 2 % faster here)
+    for (int e = t; e < tg.TB * tg.F4; e += TQ) {
+      const int r = e / tg.F4, f = e - r * tg.F4;
       tile[e] = (f < F && r < rows) ? xs[(row0 + r) * F + f] : 0.f;
     }
     for (int r = t; r <= rows; r += TQ) tl[r] = row0 + r < N ? ls[row0 + r] : -1;
@@ -115,7 +88,7 @@ __global__ __launch_bounds__(TQ) void cq_silhouette_kernel(
       // four rows at a time: independent sums (rows past the end are zeros in LDS)
       float d[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) d[u] = dist2<FX>(xr, xp, tile + (r + u) * F4, F, F4);
+      for (int u = 0; u < 4; ++u) d[u] = dist2<FX>(xr, xp, tile + (r + u) * tg.F4, F, tg.F4);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (r + u >= rows) break;

@@ -11,9 +11,11 @@
 //   km_update_kernel   one workgroup per restart: the G partials summed in g order, the stop
 //                      decision (no assignment changed, or max_iter reached) and the new means.
 // No float atomics: two runs give the same bits.  A stopped restart's launches exit at once,
-// so the host can enqueue several iterations and read one counter per chunk.
+// so the host can enqueue several iterations and read one counter per chunk.  The wave sums
+// are reduce_f64_dev.h's.
 #include "common.h"
 #include "noise_dev.h"
+#include "reduce_f64_dev.h"
 
 namespace {
 constexpr int TP = 256;    // points per tile = lanes of an assignment workgroup
@@ -23,22 +25,15 @@ constexpr int MAX_GROUPS = 2048;  // assignment workgroups of all restarts toget
 constexpr uint32_t TAG_KMPP = 0x4B4D5050u;
 constexpr int ST = SCAE_KMEANS_STATE_INTS;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
+using scae_reduce::wave_sum_f64;
+using scae_reduce::wave_sum_i32;
 
 // squared distance of the point whose features sit in xr (FX > 0: registers) or at xp (FX == 0)
-// to the centroid at cc (LDS), in f order
+// to the centroid at cc (LDS), in f order.  An fmaf accumulation: NOT row_dist_dev.h's
+// three-roundings rule, and the labels' bits depend on it -- the two are not to be unified
 template <int FX>
-__device__ __forceinline__ float dist2(const float (&xr)[FX > 0 ? FX : 1], const float *xp,
-                                       const float *cc, int F) {
+__device__ __forceinline__ float dist2_fma(const float (&xr)[FX > 0 ? FX : 1], const float *xp,
+                                           const float *cc, int F) {
   float d = 0.f;
   if constexpr (FX > 0) {
 #pragma unroll
@@ -68,7 +63,7 @@ __device__ __forceinline__ int nearest(const float *xp, const float *cs, int k, 
   int best = 0;
   float bd = INFINITY;
   for (int c = 0; c < k; ++c) {
-    const float d = dist2<FX>(xr, xp, cs + c * F, F);
+    const float d = dist2_fma<FX>(xr, xp, cs + c * F, F);
     if (d < bd) bd = d, best = c;
   }
   best_d = bd;

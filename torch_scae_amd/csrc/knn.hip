@@ -1,11 +1,9 @@
 // Exact k nearest neighbours for gfx950 (neighbors.py): the brute-force search, the k-NN vote and
 // the neighbour ranks behind trustworthiness.
 //
-// MUST BE COMPILED WITH -ffp-contract=off (csrc/Makefile gives this file the flag): the distance
-// d = sum_f (q_f - b_f)^2 rounds the difference, the product and the sum each to fp32, which is
-// what numpy's float32 does; under HIP's default -ffp-contract=fast the backend would fuse the
-// product into the sum.  The rounding intrinsics below are plain operators to the compiler; they
-// mark the places that rely on the flag.
+// The distance, the row tile and its geometry are row_dist_dev.h's, which states the
+// rounding rule and keeps contraction off for itself; csrc/Makefile also gives this file
+// -ffp-contract=off, for the vote's tallies.
 //
 // A neighbour is the 64-bit key (bits of d) << 32 | j.  d is a sum of squares from +0, so its
 // bits order as unsigned integers the way the floats do, and the keys of one query are distinct:
@@ -20,16 +18,17 @@
 //                      it beats that threshold.  G == 1 writes the result, else the group's list;
 //   knn_merge_kernel   one query per thread: the G sorted lists merged by key;
 //   knn_vote_kernel    one query per thread, O(k^2 / 2) label compares;
-//   knn_rank_count_kernel  the search's tiling with one row i per lane: the k target keys
+//   knn_rank_count_kernel  the same streaming with one row i per lane: the k target keys
 //                      (d_ij, j) in LDS, then for every streamed row l one d_il and k compares
 //                      into register counters (skipped when the key is above all targets);
 //   knn_rank_finish_kernel / knn_penalty_kernel  the groups' counts added, the ranks written,
 //                      the penalties summed per workgroup and then in index order.
 #include "common.h"
+#include "row_dist_dev.h"
 
 namespace {
+using namespace scae_rows;
 constexpr int TQ = 128;            // queries of a search workgroup, one per lane
-constexpr int TILE_FLOATS = 4096;  // the base tile in LDS (16 KiB)
 constexpr int FXR = 32;            // features held in registers by the register form
 constexpr int MAX_G = 64;          // base groups at most
 constexpr int MIN_GROUP_ROWS = 512;
@@ -40,52 +39,6 @@ constexpr uint64_t EMPTY = ~0ull;  // no finite distance has these bits
 
 __device__ __forceinline__ uint64_t make_key(float d, int64_t j) {
   return ((uint64_t)__float_as_uint(d) << 32) | (uint32_t)j;
-}
-
-__device__ __forceinline__ float sq_add(float d, float a, float b) {
-  const float u = __fsub_rn(a, b);
-  return __fadd_rn(d, __fmul_rn(u, u));
-}
-
-// squared distance of the query (registers xr, FX > 0, zero above F; or global row xp) to the
-// base row at b in LDS: rows there are padded with zeros to F4 = 4 * ceil(F / 4) floats (a
-// zero pair adds +0 to d: nothing changes), so the register form runs in whole groups of four
-template <int FX>
-__device__ __forceinline__ float dist2(const float (&xr)[FX > 0 ? FX : 1], const float *xp,
-                                       const float *b, int F, int F4) {
-  float d = 0.f;
-  if constexpr (FX > 0) {
-#pragma unroll
-    for (int f = 0; f < FX; f += 4)
-      if (f < F4) {
-        const float4 v = *reinterpret_cast<const float4 *>(b + f);
-        d = sq_add(d, xr[f], v.x);
-        d = sq_add(d, xr[f + 1], v.y);
-        d = sq_add(d, xr[f + 2], v.z);
-        d = sq_add(d, xr[f + 3], v.w);
-      }
-  } else {
-    for (int f = 0; f < F; ++f) d = sq_add(d, xp[f], b[f]);
-  }
-  return d;
-}
-
-// two rows of global memory, the same arithmetic
-__device__ __forceinline__ float dist2_rows(const float *a, const float *b, int F) {
-  float d = 0.f;
-  for (int f = 0; f < F; ++f) d = sq_add(d, a[f], b[f]);
-  return d;
-}
-
-// base rows [row0, row0 + rows) -> tile (rows, F4), zeros for the padding and past `end`
-template <int NT>
-__device__ __forceinline__ void load_tile(float *tile, const float *base, int64_t row0,
-                                          int64_t end, int rows, int F, int F4) {
-  for (int e = threadIdx.x; e < rows * F4; e += NT) {
-    const int r = e / F4, f = e - r * F4;
-    const int64_t j = row0 + r;
-    tile[e] = (f < F && j < end) ? base[j * F + f] : 0.f;
-  }
 }
 
 // key into the lane's sorted list (stride TQ), which it is known to beat; -> the new k-th key
@@ -123,8 +76,7 @@ __global__ __launch_bounds__(TQ) void knn_search_kernel(const float *q, int64_t 
   const int t = threadIdx.x, g = blockIdx.y;
   const int64_t qi = (int64_t)blockIdx.x * TQ + t;
   const bool active = qi < Nq;
-  const int F4 = (F + 3) & ~3;
-  const int TB = (TILE_FLOATS / F4) & ~3;   // rows of a tile: a multiple of four, >= 16
+  const TileGeom tg = tile_geom(F);
   const float *xp = q + (active ? qi : 0) * F;
   float xr[FX > 0 ? FX : 1];
   if constexpr (FX > 0) {
@@ -135,18 +87,18 @@ __global__ __launch_bounds__(TQ) void knn_search_kernel(const float *q, int64_t 
   uint64_t thr = EMPTY;
   const int64_t skip = self_mode ? qi : -1;
   const Range rg = group_range(Nb, G, g);
-  for (int64_t row0 = rg.begin; row0 < rg.end; row0 += TB) {
+  for (int64_t row0 = rg.begin; row0 < rg.end; row0 += tg.TB) {
     __syncthreads();   // (the previous tile has been read)
-    load_tile<TQ>(tile, base, row0, rg.end, TB, F, F4);
+    load_tile<TQ>(tile, base, row0, rg.end, tg.TB, F, tg.F4);
     __syncthreads();
     if (!active) continue;
     const int64_t left = rg.end - row0;
-    const int rows = left < TB ? (int)left : TB;
+    const int rows = left < tg.TB ? (int)left : tg.TB;
     for (int r = 0; r < rows; r += 4) {
       // four rows at a time: independent sums (rows past the end are zeros in LDS)
       float d[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) d[u] = dist2<FX>(xr, xp, tile + (r + u) * F4, F, F4);
+      for (int u = 0; u < 4; ++u) d[u] = dist2<FX>(xr, xp, tile + (r + u) * tg.F4, F, tg.F4);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int64_t j = row0 + r + u;
@@ -242,8 +194,7 @@ __global__ __launch_bounds__(TQ) void knn_rank_count_kernel(const float *x, int6
   const int t = threadIdx.x, g = blockIdx.y;
   const int64_t i = (int64_t)blockIdx.x * TQ + t;
   const bool active = i < N;
-  const int F4 = (F + 3) & ~3;
-  const int TB = (TILE_FLOATS / F4) & ~3;
+  const TileGeom tg = tile_geom(F);
   const float *xp = x + (active ? i : 0) * F;
   float xr[FX > 0 ? FX : 1];
   if constexpr (FX > 0) {
@@ -263,17 +214,17 @@ __global__ __launch_bounds__(TQ) void knn_rank_count_kernel(const float *x, int6
 #pragma unroll
   for (int m = 0; m < KX; ++m) cnt[m] = 0;
   const Range rg = group_range(N, G, g);
-  for (int64_t row0 = rg.begin; row0 < rg.end; row0 += TB) {
+  for (int64_t row0 = rg.begin; row0 < rg.end; row0 += tg.TB) {
     __syncthreads();
-    load_tile<TQ>(tile, x, row0, rg.end, TB, F, F4);
+    load_tile<TQ>(tile, x, row0, rg.end, tg.TB, F, tg.F4);
     __syncthreads();
     if (!active) continue;
     const int64_t left = rg.end - row0;
-    const int rows = left < TB ? (int)left : TB;
+    const int rows = left < tg.TB ? (int)left : tg.TB;
     for (int r = 0; r < rows; r += 4) {
       float d[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) d[u] = dist2<FX>(xr, xp, tile + (r + u) * F4, F, F4);
+      for (int u = 0; u < 4; ++u) d[u] = dist2<FX>(xr, xp, tile + (r + u) * tg.F4, F, tg.F4);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int64_t l = row0 + r + u;

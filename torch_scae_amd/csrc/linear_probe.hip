@@ -18,8 +18,9 @@
 //                       launch.
 // No float atomics, every sum in a fixed order: two runs give the same bits, and a problem's
 // bits do not depend on the problems solved beside it.  The launches of a stopped problem
-// leave its state untouched.
+// leave its state untouched.  The fp64 wave sum is reduce_f64_dev.h's.
 #include "common.h"
+#include "reduce_f64_dev.h"
 
 namespace {
 constexpr int TR = 64;     // rows per tile
@@ -29,11 +30,7 @@ constexpr int ST = SCAE_PROBE_STATE_INTS;
 constexpr int PREDICT_BLOCKS = 1024;
 constexpr size_t LDS_MAX = 160 * 1024;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
+using scae_reduce::wave_sum_f64;
 __device__ __forceinline__ float wave_max_f32(float v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));

@@ -15,31 +15,28 @@
 //                      y_i wave-uniform and P's row segment read coalesced, and reduces the
 //                      row's five sums (six in the KL form) across lanes by DPP;
 //   tsne_rows_kernel   the G partials of every row in g order, per-workgroup fp64 sums of Z, KL;
-//   tsne_update_kernel Z, gradient, gains, velocity, position; fp64 column-sum and |g|^2 partials;
-//   tsne_finish_kernel one workgroup: the column means leave Y, and the history row.
+//   tsne_update_kernel, tsne_finish_kernel  tsne_step_dev.h's, shared with tsne_sparse.hip, as is
+//                      the schedule: the update, then the column means leave Y and the history row.
 // P is read once per iteration (N^2 floats: the pass is bound by that stream above N of a few
 // thousand); nothing crosses workgroups inside a launch, so stream order is the only ordering.
 // Every product-sum is an explicit fmaf and contraction is off: the KL form of the gradient
 // kernel gives the bits of the plain one.
 #pragma clang fp contract(off)
 #include "common.h"
+#include "tsne_step_dev.h"
 
 namespace {
 constexpr int DT = 64, DF = 32;   // distance tile, feature chunk
 constexpr int NB = 256;           // bandwidth-search workgroup
 constexpr int ST = 32;            // symmetrise tile
 constexpr int NS = 1024;          // one-workgroup reductions
-constexpr int NU = 256;           // rows / update workgroup: one row per thread
 constexpr int SMALL_N = 2048;     // up to here 256-column groups, above 1024
 constexpr int NC = 6;             // att0, att1, rep0, rep1, z, kl
-constexpr int MAXB = SCAE_TSNE_MAX_N / NU;   // 128 update workgroups at most
+// NU, the rows / update / finish workgroup (one row per thread), is tsne_step_dev.h's
+constexpr int MAXB = SCAE_TSNE_MAX_N / NU;   // 128 update workgroups at most: block's stride
 static_assert(5 * MAXB == SCAE_TSNE_BLOCK_DOUBLES, "block partials: z, kl, y0, y1, |g|^2");
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
+using scae_reduce::wave_sum_f64;
 
 __global__ __launch_bounds__(256) void tsne_dist_kernel(const float *x, int N, int F, float *D) {
   __shared__ float xi[DT][DF + 1], xj[DT][DF + 1];
@@ -240,16 +237,6 @@ __global__ __launch_bounds__(256) void tsne_grad_kernel(const float *P, const fl
   }
 }
 
-// the block's fp64 sum of one value per thread: waves by shuffle, then in wave order; valid in
-// thread 0.  red: NU / 64 doubles; contains barriers
-__device__ __forceinline__ double block_sum_f64(double v, double *red) {
-  v = wave_sum_f64(v);
-  __syncthreads();   // (red may still be read from the call before)
-  if (threadIdx.x % SCAE_WAVE == 0) red[threadIdx.x / SCAE_WAVE] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // grid (ceil(N / NU)): rows (c, i) = sum_g part (c, g, i) in g order; block (0 | 1, b) = the
 // workgroup's fp64 sum of z | kl
 template <bool KL>
@@ -267,72 +254,7 @@ __global__ __launch_bounds__(NU) void tsne_rows_kernel(scae_tsne_desc d) {
       if (c == 5) kl = s;
     }
   }
-  const double zs = block_sum_f64((double)z, red);
-  if (threadIdx.x == 0) d.block[blockIdx.x] = zs;
-  if constexpr (KL) {
-    const double ks = block_sum_f64((double)kl, red);
-    if (threadIdx.x == 0) d.block[MAXB + blockIdx.x] = ks;
-  }
-}
-
-__device__ __forceinline__ double ordered_sum(const double *p, int n) {
-  double s = 0.0;
-  for (int b = 0; b < n; ++b) s += p[b];
-  return s;
-}
-
-// grid (ceil(N / NU)).  apply = 0: the gradient's norm alone (the evaluation after the last
-// iteration); block (2 | 3 | 4, b) = the workgroup's fp64 sums of y0 | y1 | g0^2 + g1^2
-__global__ __launch_bounds__(NU) void tsne_update_kernel(scae_tsne_desc d, float exaggeration,
-                                                         float momentum, int apply) {
-  __shared__ double red[NU / SCAE_WAVE];
-  const int i = blockIdx.x * NU + threadIdx.x, N = d.N;
-  const float zinv = (float)(1.0 / ordered_sum(d.block, gridDim.x));
-  double s0 = 0.0, s1 = 0.0, gg = 0.0;
-  if (i < N) {
-    float y[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const float att = d.rows[(size_t)k * N + i], rep = d.rows[(size_t)(2 + k) * N + i];
-      const float g = 4.f * (exaggeration * att - rep * zinv);
-      gg += (double)g * (double)g;
-      y[k] = d.Y[2 * i + k];
-      if (apply) {
-        float vel = d.velocity[2 * i + k], gain = d.gains[2 * i + k];
-        gain = fmaxf(g * vel < 0.f ? gain + 0.2f : gain * 0.8f, 0.01f);
-        vel = momentum * vel - (d.learning_rate * gain) * g;
-        y[k] += vel;
-        d.gains[2 * i + k] = gain, d.velocity[2 * i + k] = vel, d.Y[2 * i + k] = y[k];
-      }
-    }
-    s0 = (double)y[0], s1 = (double)y[1];
-  }
-  s0 = block_sum_f64(s0, red);
-  s1 = block_sum_f64(s1, red);
-  gg = block_sum_f64(gg, red);
-  if (threadIdx.x == 0) {
-    d.block[2 * MAXB + blockIdx.x] = s0;
-    d.block[3 * MAXB + blockIdx.x] = s1;
-    d.block[4 * MAXB + blockIdx.x] = gg;
-  }
-}
-
-// one workgroup.  apply: Y loses its column means; row >= 0: history row (it, KL, |g|)
-__global__ __launch_bounds__(NS) void tsne_finish_kernel(scae_tsne_desc d, int nb, int it,
-                                                         int apply, int row) {
-  const int t = threadIdx.x, N = d.N;
-  if (apply) {
-    const float m0 = (float)(ordered_sum(d.block + 2 * MAXB, nb) / (double)N);
-    const float m1 = (float)(ordered_sum(d.block + 3 * MAXB, nb) / (double)N);
-    for (int i = t; i < N; i += NS) d.Y[2 * i] -= m0, d.Y[2 * i + 1] -= m1;
-  }
-  if (row >= 0 && t == 0) {
-    const double Z = ordered_sum(d.block, nb);
-    double *h = d.history + (size_t)row * SCAE_TSNE_HISTORY_COLS;
-    h[0] = (double)it;
-    h[1] = *d.plogp + ordered_sum(d.block + MAXB, nb) + log(Z);
-    h[2] = sqrt(ordered_sum(d.block + 4 * MAXB, nb));
-  }
+  tsne_block_z_kl<KL>(z, kl, d.block, MAXB, red);
 }
 
 template <int M, int RW>
@@ -344,11 +266,9 @@ void launch_grad(const scae_tsne_desc &d, bool kl, hipStream_t st) {
     scae::launch(tsne_grad_kernel<M, RW, false>, grid, dim3(256), 0, st, d.P, d.Y, d.N, d.G, d.part);
 }
 
-// the launches of iteration it (apply) or of the evaluation at it (no update)
-void iteration(const scae_tsne_desc &d, int it, bool apply, int row, hipStream_t st) {
-  const bool kl = row >= 0;
+// the gradient's sums of one iteration into rows (kl: the recorded form)
+void sum_gradient(const scae_tsne_desc &d, bool kl, hipStream_t st) {
   const int nb = (d.N + NU - 1) / NU;
-  const bool early = it < d.exaggeration_iter;
   if (d.N <= SMALL_N)
     launch_grad<4, 4>(d, kl, st);
   else
@@ -357,9 +277,6 @@ void iteration(const scae_tsne_desc &d, int it, bool apply, int row, hipStream_t
     scae::launch(tsne_rows_kernel<true>, dim3(nb), dim3(NU), 0, st, d);
   else
     scae::launch(tsne_rows_kernel<false>, dim3(nb), dim3(NU), 0, st, d);
-  scae::launch(tsne_update_kernel, dim3(nb), dim3(NU), 0, st, d,
-               early ? d.early_exaggeration : 1.f, early ? 0.5f : 0.8f, (int)apply);
-  scae::launch(tsne_finish_kernel, dim3(1), dim3(NS), 0, st, d, nb, it, (int)apply, row);
 }
 }  // namespace
 
@@ -403,9 +320,6 @@ extern "C" int scae_tsne_run_f32(const scae_tsne_desc *dp, int first_iter, int n
   if (!scae_tsne_supported(d.N, 1)) return SCAE_ERR_UNSUPPORTED;
   SCAE_REQUIRE(d.G == scae_tsne_groups(d.N));
   hipStream_t st = (hipStream_t)stream;
-  for (int it = first_iter; it < first_iter + n; ++it)
-    iteration(d, it, true, it > 0 && it % d.check_every == 0 ? it / d.check_every - 1 : -1, st);
-  if (n > 0 && first_iter + n == d.n_iter)
-    iteration(d, d.n_iter, false, (d.n_iter + d.check_every - 1) / d.check_every - 1, st);
+  tsne_run(d, MAXB, first_iter, n, st, [&](bool kl) { sum_gradient(d, kl, st); });
   return scae_launch_status();
 }

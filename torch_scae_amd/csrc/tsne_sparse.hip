@@ -21,16 +21,14 @@
 //                      of those bounds the pass (the quarter-rate reciprocal is close to half
 //                      of it).  Only a tile that holds the block's own rows or columns past N
 //                      pays for the j != i / j < N test;
-//   tsne_srows_kernel, tsne_supdate_kernel, tsne_sfinish_kernel
-//                      the dense path's rows / update / finish arithmetic.  They are not
-//                      tsne.hip's kernels: those lay their fp64 partials out for 128 update
-//                      workgroups (N <= 32768), here there are up to SCAE_TSNE_SPARSE_MAX_N /
-//                      256 = 1024; the rows kernel adds the repulsion's partials alone, and the
-//                      recentring is spread over the update's grid instead of one workgroup.
+//   tsne_srows_kernel  the repulsion's partials added in g order (the attraction launch has
+//                      written its rows), then tsne_step_dev.h's update, finish and schedule: the
+//                      dense path's, with block's rows SCAE_TSNE_SPARSE_MAX_N / 256 apart.
 // Nothing crosses workgroups inside a launch; every product-sum is an explicit fmaf and
 // contraction is off, so the recorded form of the attraction gives the bits of the plain one.
 #pragma clang fp contract(off)
 #include "common.h"
+#include "tsne_step_dev.h"
 
 namespace {
 constexpr int NW = 4;              // rows (waves) of a bandwidth / attraction workgroup
@@ -40,16 +38,10 @@ constexpr int RB = RT * RR;        // rows per workgroup
 constexpr int TJ = 256;            // columns per LDS tile: one per thread to load
 constexpr int TARGET_WG = 1024;    // workgroups a repulsion launch aims for: four per CU
 constexpr int MAX_G = 64;
-constexpr int NU = 256;            // rows / update / finish workgroup: one row per thread
-constexpr int MAXB = SCAE_TSNE_SPARSE_MAX_N / NU;
+// NU, the rows / update / finish workgroup (one row per thread), is tsne_step_dev.h's
+constexpr int MAXB = SCAE_TSNE_SPARSE_MAX_N / NU;   // block's stride
 static_assert(5 * MAXB == SCAE_TSNE_SPARSE_BLOCK_DOUBLES, "block partials: z, kl, y0, y1, |g|^2");
 static_assert(SCAE_TSNE_MAX_NEIGHBORS == 2 * SCAE_WAVE, "two list entries per lane");
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // grid ceil(N / NW): wave w of workgroup b takes row NW b + w (no barrier: a wave past N leaves)
 __global__ __launch_bounds__(NW * SCAE_WAVE) void tsne_knn_beta_kernel(const float *d2, int N,
@@ -185,16 +177,6 @@ __global__ __launch_bounds__(RT) void tsne_rep_kernel(const float *Y, int N, int
     }
 }
 
-// the block's fp64 sum of one value per thread: waves by shuffle, then in wave order; valid in
-// thread 0.  red: NU / 64 doubles; contains barriers
-__device__ __forceinline__ double block_sum_f64(double v, double *red) {
-  v = wave_sum_f64(v);
-  __syncthreads();   // (red may still be read from the call before)
-  if (threadIdx.x % SCAE_WAVE == 0) red[threadIdx.x / SCAE_WAVE] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // grid (ceil(N / NU)): rows (2 + c, i) = sum_g part (c, g, i) in g order; block (0 | 1, b) = the
 // workgroup's fp64 sum of z | kl (the attraction launch has written rows 0, 1 and 5).  The loads
 // of GU groups are issued together (a thread's G dependent round trips were the launch's time at
@@ -225,79 +207,7 @@ __global__ __launch_bounds__(NU) void tsne_srows_kernel(scae_tsne_sparse_desc d)
     z = s[2];
     if constexpr (KL) kl = d.rows[(size_t)5 * N + i];
   }
-  const double zs = block_sum_f64((double)z, red);
-  if (threadIdx.x == 0) d.block[blockIdx.x] = zs;
-  if constexpr (KL) {
-    const double ks = block_sum_f64((double)kl, red);
-    if (threadIdx.x == 0) d.block[MAXB + blockIdx.x] = ks;
-  }
-}
-
-__device__ __forceinline__ double ordered_sum(const double *p, int n) {
-  double s = 0.0;
-  for (int b = 0; b < n; ++b) s += p[b];
-  return s;
-}
-
-// grid (ceil(N / NU)).  apply = 0: the gradient's norm alone (the evaluation after the last
-// iteration); block (2 | 3 | 4, b) = the workgroup's fp64 sums of y0 | y1 | g0^2 + g1^2
-__global__ __launch_bounds__(NU) void tsne_supdate_kernel(scae_tsne_sparse_desc d,
-                                                          float exaggeration, float momentum,
-                                                          int apply) {
-  __shared__ double red[NU / SCAE_WAVE];
-  const int i = blockIdx.x * NU + threadIdx.x, N = d.N;
-  const float zinv = (float)(1.0 / ordered_sum(d.block, gridDim.x));
-  double s0 = 0.0, s1 = 0.0, gg = 0.0;
-  if (i < N) {
-    float y[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const float att = d.rows[(size_t)k * N + i], rep = d.rows[(size_t)(2 + k) * N + i];
-      const float g = 4.f * (exaggeration * att - rep * zinv);
-      gg += (double)g * (double)g;
-      y[k] = d.Y[2 * (size_t)i + k];
-      if (apply) {
-        float vel = d.velocity[2 * (size_t)i + k], gain = d.gains[2 * (size_t)i + k];
-        gain = fmaxf(g * vel < 0.f ? gain + 0.2f : gain * 0.8f, 0.01f);
-        vel = momentum * vel - (d.learning_rate * gain) * g;
-        y[k] += vel;
-        d.gains[2 * (size_t)i + k] = gain, d.velocity[2 * (size_t)i + k] = vel;
-        d.Y[2 * (size_t)i + k] = y[k];
-      }
-    }
-    s0 = (double)y[0], s1 = (double)y[1];
-  }
-  s0 = block_sum_f64(s0, red);
-  s1 = block_sum_f64(s1, red);
-  gg = block_sum_f64(gg, red);
-  if (threadIdx.x == 0) {
-    d.block[2 * MAXB + blockIdx.x] = s0;
-    d.block[3 * MAXB + blockIdx.x] = s1;
-    d.block[4 * MAXB + blockIdx.x] = gg;
-  }
-}
-
-// grid (ceil(N / NU)), a row per thread.  apply: Y loses its column means (every workgroup adds
-// the update's partials in the same order; one workgroup walking all of Y took 54 us at
-// N = 60 000); row >= 0: workgroup 0 writes the history row (it, KL, |g|)
-__global__ __launch_bounds__(NU) void tsne_sfinish_kernel(scae_tsne_sparse_desc d, int it,
-                                                          int apply, int row) {
-  __shared__ float mean[2];
-  const int i = blockIdx.x * NU + threadIdx.x, N = d.N, nb = gridDim.x;
-  if (apply) {
-    if (threadIdx.x < 2)
-      mean[threadIdx.x] =
-          (float)(ordered_sum(d.block + (2 + threadIdx.x) * MAXB, nb) / (double)N);
-    __syncthreads();
-    if (i < N) d.Y[2 * (size_t)i] -= mean[0], d.Y[2 * (size_t)i + 1] -= mean[1];
-  }
-  if (row >= 0 && blockIdx.x == 0 && threadIdx.x == 0) {
-    const double Z = ordered_sum(d.block, nb);
-    double *h = d.history + (size_t)row * SCAE_TSNE_HISTORY_COLS;
-    h[0] = (double)it;
-    h[1] = *d.plogp + ordered_sum(d.block + MAXB, nb) + log(Z);
-    h[2] = sqrt(ordered_sum(d.block + 4 * MAXB, nb));
-  }
+  tsne_block_z_kl<KL>(z, kl, d.block, MAXB, red);
 }
 
 // columns of a repulsion group: whole tiles, about TARGET_WG workgroups over the row blocks
@@ -309,11 +219,9 @@ int group_chunk(int N) {
   return (cols + TJ - 1) / TJ * TJ;
 }
 
-// the launches of iteration it (apply) or of the evaluation at it (no update)
-void iteration(const scae_tsne_sparse_desc &d, int it, bool apply, int row, hipStream_t st) {
-  const bool kl = row >= 0;
+// the gradient's sums of one iteration into rows (kl: the recorded form)
+void sum_gradient(const scae_tsne_sparse_desc &d, bool kl, hipStream_t st) {
   const int nb = (d.N + NU - 1) / NU, nw = (d.N + NW - 1) / NW;
-  const bool early = it < d.exaggeration_iter;
   if (kl)
     scae::launch(tsne_att_kernel<true>, dim3(nw), dim3(NW * SCAE_WAVE), 0, st, d);
   else
@@ -324,9 +232,6 @@ void iteration(const scae_tsne_sparse_desc &d, int it, bool apply, int row, hipS
     scae::launch(tsne_srows_kernel<true>, dim3(nb), dim3(NU), 0, st, d);
   else
     scae::launch(tsne_srows_kernel<false>, dim3(nb), dim3(NU), 0, st, d);
-  scae::launch(tsne_supdate_kernel, dim3(nb), dim3(NU), 0, st, d,
-               early ? d.early_exaggeration : 1.f, early ? 0.5f : 0.8f, (int)apply);
-  scae::launch(tsne_sfinish_kernel, dim3(nb), dim3(NU), 0, st, d, it, (int)apply, row);
 }
 }  // namespace
 
@@ -361,9 +266,6 @@ extern "C" int scae_tsne_sparse_run_f32(const scae_tsne_sparse_desc *dp, int fir
   if (!scae_tsne_sparse_supported(d.N, 1, 1)) return SCAE_ERR_UNSUPPORTED;
   SCAE_REQUIRE(d.G == scae_tsne_sparse_groups(d.N));
   hipStream_t st = (hipStream_t)stream;
-  for (int it = first_iter; it < first_iter + n; ++it)
-    iteration(d, it, true, it > 0 && it % d.check_every == 0 ? it / d.check_every - 1 : -1, st);
-  if (n > 0 && first_iter + n == d.n_iter)
-    iteration(d, d.n_iter, false, (d.n_iter + d.check_every - 1) / d.check_every - 1, st);
+  tsne_run(d, MAXB, first_iter, n, st, [&](bool kl) { sum_gradient(d, kl, st); });
   return scae_launch_status();
 }

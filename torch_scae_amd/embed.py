@@ -570,78 +570,74 @@ def affinities_knn(x, perplexity=30.0, neighbors="auto"):
     return csr + (beta, float(plogp))
 
 
-class _SparseProblem:
-    """``_TsneProblem`` for the sparse form: the device state of one run over a Csr."""
+class _Problem:
+    """The device state of one run that both forms share -- Y, velocity, gains, the rows' sums,
+    the partials, the history -- and their fields of the descriptor.  A form names its
+    descriptor type, its ``groups`` function, the ``part`` rows per group, its ``block`` size and
+    whether ``rows`` starts as zeros."""
+    DESC = GROUPS = PART_ROWS = BLOCK_DOUBLES = ZERO_ROWS = None
 
-    def __init__(self, csr, plogp, Y0, n_iter, early_exaggeration, exaggeration_iter,
-                 learning_rate, check_every):
-        N, dev = csr.indptr.numel() - 1, csr.values.device
-        self.indptr = csr.indptr.contiguous()
-        self.cols = csr.indices.to(torch.int32).contiguous()
-        self.vals = csr.values.contiguous()
+    def _setup(self, N, dev, plogp, Y0, n_iter, early_exaggeration, exaggeration_iter,
+               learning_rate, check_every):
+        G = getattr(_lib.load(), self.GROUPS)(N)
         self.plogp = torch.as_tensor(plogp, dtype=torch.float64).reshape(1).to(dev)
         self.Y = torch.as_tensor(Y0).to(dev, torch.float32).contiguous().clone()
         self.velocity = torch.zeros(N, 2, device=dev)
         self.gains = torch.ones(N, 2, device=dev)
-        G = _lib.load().scae_tsne_sparse_groups(N)
-        self.part = torch.empty(3 * G * N, device=dev)
-        self.rows = torch.zeros(6 * N, device=dev)
-        self.block = torch.zeros(_lib.TSNE_SPARSE_BLOCK_DOUBLES, device=dev, dtype=torch.float64)
+        self.part = torch.empty(self.PART_ROWS * G * N, device=dev)
+        self.rows = (torch.zeros if self.ZERO_ROWS else torch.empty)(6 * N, device=dev)
+        self.block = torch.zeros(self.BLOCK_DOUBLES, device=dev, dtype=torch.float64)
         self.history = torch.zeros(-(-n_iter // check_every), _lib.TSNE_HISTORY_COLS, device=dev,
                                    dtype=torch.float64)
-        d = self.desc = _lib.TsneSparseDesc()
+        d = self.desc = self.DESC()
         d.N, d.G, d.n_iter, d.exaggeration_iter, d.check_every = \
             N, G, n_iter, exaggeration_iter, check_every
         d.early_exaggeration, d.learning_rate = early_exaggeration, learning_rate
-        d.indptr, d.cols, d.vals, d.nnz = (self.indptr.data_ptr(), self.cols.data_ptr(),
-                                           self.vals.data_ptr(), self.vals.numel())
         d.Y, d.velocity, d.gains = (self.Y.data_ptr(), self.velocity.data_ptr(),
                                     self.gains.data_ptr())
         d.part, d.rows, d.block = self.part.data_ptr(), self.rows.data_ptr(), self.block.data_ptr()
         d.plogp, d.history = self.plogp.data_ptr(), self.history.data_ptr()
+        return d
 
     def load_state(self, Y, velocity, gains):
         self.Y.copy_(torch.as_tensor(Y).to(self.Y))
         self.velocity.copy_(torch.as_tensor(velocity).to(self.Y))
         self.gains.copy_(torch.as_tensor(gains).to(self.Y))
+
+
+class _SparseProblem(_Problem):
+    """``_TsneProblem`` for the sparse form: the device state of one run over a Csr."""
+    DESC, GROUPS, PART_ROWS = _lib.TsneSparseDesc, "scae_tsne_sparse_groups", 3
+    BLOCK_DOUBLES, ZERO_ROWS = _lib.TSNE_SPARSE_BLOCK_DOUBLES, True
+
+    def __init__(self, csr, plogp, Y0, n_iter, early_exaggeration, exaggeration_iter,
+                 learning_rate, check_every):
+        self.indptr = csr.indptr.contiguous()
+        self.cols = csr.indices.to(torch.int32).contiguous()
+        self.vals = csr.values.contiguous()
+        d = self._setup(csr.indptr.numel() - 1, csr.values.device, plogp, Y0, n_iter,
+                        early_exaggeration, exaggeration_iter, learning_rate, check_every)
+        d.indptr, d.cols, d.vals, d.nnz = (self.indptr.data_ptr(), self.cols.data_ptr(),
+                                           self.vals.data_ptr(), self.vals.numel())
 
     def run(self, first_iter, n):
         _lib.call("scae_tsne_sparse_run_f32", ctypes.byref(self.desc), first_iter, n,
                   _stream(self.Y))
 
 
-class _TsneProblem:
+class _TsneProblem(_Problem):
     """The device state of one run over a given P: Y, velocity, gains, the partials, the history
     and the descriptor; ``run(first_iter, n)`` enqueues iterations.  ``tsne`` drives it; the tests
     also load a state of their own (``load_state``) and read the raw buffers."""
+    DESC, GROUPS, PART_ROWS = _lib.TsneDesc, "scae_tsne_groups", 6
+    BLOCK_DOUBLES, ZERO_ROWS = _lib.TSNE_BLOCK_DOUBLES, False
 
     def __init__(self, P, plogp, Y0, n_iter, early_exaggeration, exaggeration_iter,
                  learning_rate, check_every):
-        N, dev = P.shape[0], P.device
         self.P = P
-        self.plogp = torch.as_tensor(plogp, dtype=torch.float64).reshape(1).to(dev)
-        self.Y = torch.as_tensor(Y0).to(dev, torch.float32).contiguous().clone()
-        self.velocity = torch.zeros(N, 2, device=dev)
-        self.gains = torch.ones(N, 2, device=dev)
-        G = _lib.load().scae_tsne_groups(N)
-        self.part = torch.empty(6 * G * N, device=dev)
-        self.rows = torch.empty(6 * N, device=dev)
-        self.block = torch.zeros(_lib.TSNE_BLOCK_DOUBLES, device=dev, dtype=torch.float64)
-        self.history = torch.zeros(-(-n_iter // check_every), _lib.TSNE_HISTORY_COLS, device=dev,
-                                   dtype=torch.float64)
-        d = self.desc = _lib.TsneDesc()
-        d.N, d.G, d.n_iter, d.exaggeration_iter, d.check_every = \
-            N, G, n_iter, exaggeration_iter, check_every
-        d.early_exaggeration, d.learning_rate = early_exaggeration, learning_rate
-        d.P, d.Y, d.velocity, d.gains = (P.data_ptr(), self.Y.data_ptr(),
-                                         self.velocity.data_ptr(), self.gains.data_ptr())
-        d.part, d.rows, d.block = self.part.data_ptr(), self.rows.data_ptr(), self.block.data_ptr()
-        d.plogp, d.history = self.plogp.data_ptr(), self.history.data_ptr()
-
-    def load_state(self, Y, velocity, gains):
-        self.Y.copy_(torch.as_tensor(Y).to(self.Y))
-        self.velocity.copy_(torch.as_tensor(velocity).to(self.Y))
-        self.gains.copy_(torch.as_tensor(gains).to(self.Y))
+        d = self._setup(P.shape[0], P.device, plogp, Y0, n_iter, early_exaggeration,
+                        exaggeration_iter, learning_rate, check_every)
+        d.P = P.data_ptr()
 
     def run(self, first_iter, n):
         _lib.call("scae_tsne_run_f32", ctypes.byref(self.desc), first_iter, n, _stream(self.P))
