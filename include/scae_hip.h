@@ -376,6 +376,35 @@ int scae_seed_attention_mfma_bwd_gemm_bf16(const float *h, const float *q, const
                                            const float *gout, float *gh, float *partial, int B,
                                            int N, int O, int C, const scae_gemm_desc *descs,
                                            int n, void *stream);
+/* ... and scae_set_encoder_bwd_{f32,bf16} in the same launch (csrc/seed_bwd_gemm.hip): the
+ * trunk's backward reads of the attention's backward only row b of gh, which the workgroup of
+ * set b writes, so each attention workgroup goes on with the trunk's backward of its set --
+ * the gradient handed over in registers -- while the GEMM tiles fill the rest of the grid.
+ * Arguments: those of scae_seed_attention_mfma_bwd_gemm_* (gh and partial are written as
+ * there), then those of scae_set_encoder_bwd_* without gz (trunk_B = B, trunk_N = N; h is the
+ * trunk's output z).  Same bits as the two launches.
+ * scae_object_encoder_bwd_supported: B <= 512 (one set per workgroup), N, O <= 32, C a
+ * multiple of 64, D = 16, Dout = 0 and a trunk on the matrix-core kernels
+ * (scae_set_encoder_bf16_supported); otherwise -- or when the GEMMs do not take the 32 x 32
+ * split-K tiles -- the launchers return SCAE_ERR_UNSUPPORTED and launch nothing. */
+int scae_object_encoder_bwd_supported(int B, int N, int O, int C, int D, int Din, int Dout,
+                                      int L, int layer_norm);
+int scae_object_encoder_bwd_gemm_f32(
+    const float *h, const float *q, const float *wk, const float *wv, const float *presence,
+    const float *gout, float *gh, float *partial, int B, int N, int O, int C,
+    const scae_gemm_desc *descs, int n, int nseg, const float *const *seg_ptr,
+    const int *seg_width, const int *seg_row_stride, const int64_t *seg_batch_stride,
+    float *const *seg_grad, const float *trunk_presence, const float *params,
+    const float *hsave, float *pg_partial, int trunk_B, int trunk_N, int D, int Din, int Dout,
+    int L, int layer_norm, void *stream);
+int scae_object_encoder_bwd_gemm_bf16(
+    const float *h, const float *q, const float *wk, const float *wv, const float *presence,
+    const float *gout, float *gh, float *partial, int B, int N, int O, int C,
+    const scae_gemm_desc *descs, int n, int nseg, const float *const *seg_ptr,
+    const int *seg_width, const int *seg_row_stride, const int64_t *seg_batch_stride,
+    float *const *seg_grad, const float *trunk_presence, const float *params,
+    const float *hsave, float *pg_partial, int trunk_B, int trunk_N, int D, int Din, int Dout,
+    int L, int layer_norm, void *stream);
 
 
 /* ------------------------------------------------------------------------

@@ -231,6 +231,11 @@ SIGNATURES = {
     + [POINTER(GemmDesc), c_int, P],
     "scae_seed_attention_mfma_bwd_gemm_bf16": [P] * 8 + [c_int] * 4
     + [POINTER(GemmDesc), c_int, P],
+    "scae_object_encoder_bwd_supported": [c_int] * 9,
+    "scae_object_encoder_bwd_gemm_f32": [P] * 8 + [c_int] * 4
+    + [POINTER(GemmDesc), c_int] + [c_int, P, P, P, P, P, P, P, P, P] + [c_int] * 7 + [P],
+    "scae_object_encoder_bwd_gemm_bf16": [P] * 8 + [c_int] * 4
+    + [POINTER(GemmDesc), c_int] + [c_int, P, P, P, P, P, P, P, P, P] + [c_int] * 7 + [P],
     "scae_seed_attention_mfma_reduce_f32": [P, c_int] + [P] * 7 + [c_int] * 2 + [P],
     "scae_seed_fold_supported": [c_int] * 3,
     "scae_seed_fold_fwd_f32": [POINTER(SeedFoldDesc), P],

@@ -244,9 +244,12 @@ __global__ __launch_bounds__(NTH) void saw_fwd_kernel(SwArgs a) {
   }
 }
 
-// workgroup `blk` of `nblk` (seed_bwd_gemm.hip runs these as the head of a shared launch)
+// workgroup `blk` of `nblk` (seed_bwd_gemm.hip runs these as the head of a shared launch).
+// Returns what wave u < NT still holds of its last set's dh: key tile u in the MFMA output
+// layout ([e] = row 16 u + 4 q + e, column r; rows >= N are not meaningful), for a caller
+// that goes on with the trunk's backward of that set.
 template <int NT, bool BF>
-__device__ __forceinline__ void saw_bwd_body(const SwArgs &a, float *smem, int blk, int nblk) {
+__device__ __forceinline__ f32x4 saw_bwd_body(const SwArgs &a, float *smem, int blk, int nblk) {
   const Tl<NT> tl{smem};
   const Lane l = make_lane();
   const int C = a.C, O = a.O, N = a.N, CW = C / 4, run = CW / 4;
@@ -262,6 +265,7 @@ __device__ __forceinline__ void saw_bwd_body(const SwArgs &a, float *smem, int b
   bool first = true;
   auto put = [&](int idx, float v) { part[idx] = first ? v : part[idx] + v; };
   const int k0 = CW * l.v + run * l.q;   // this lane group's run of C in the dT product
+  f32x4 gh_tile = splat(0.f);
   for (int b = blk; b < a.B; b += nblk) {
     const float *gb = a.gout + (size_t)b * O * C;
     // dT = gout wv: partial over this wave's quarter of C
@@ -373,10 +377,12 @@ __device__ __forceinline__ void saw_bwd_body(const SwArgs &a, float *smem, int b
         const int n = 16 * u + 4 * l.q + e;
         if (n < N) a.gh[((size_t)b * N + n) * D + l.r] = gh[e];
       }
+      gh_tile = gh;
     }
     first = false;
     __syncthreads();
   }
+  return gh_tile;
 }
 template <int NT, bool BF>
 __global__ __launch_bounds__(NTH) void saw_bwd_kernel(SwArgs a) {

@@ -894,6 +894,29 @@ int encoder_bwd(bool bf16, int nseg, const float *const *seg_ptr, const int *seg
 }
 }  // namespace
 
+// The argument block of scae_set_encoder_bwd_* without gz, for the launch the trunk's backward
+// shares with the output attention's (seed_bwd_gemm.hip): SCAE_ERR_UNSUPPORTED unless the
+// stand-alone launch would take the matrix-core kernels.
+int scae_st::wave_bwd_args(StArgs &a, bool bf16, int nseg, const float *const *seg_ptr,
+                           const int *seg_width, const int *seg_row_stride,
+                           const int64_t *seg_batch_stride, float *const *seg_grad,
+                           const float *presence, const float *params, const float *hsave,
+                           float *pg_partial, int B, int N, int D, int Din, int Dout, int L,
+                           int layer_norm) {
+  a = StArgs{};
+  int rc = fill_args(a, nseg, seg_ptr, seg_width, seg_row_stride, seg_batch_stride, seg_grad,
+                     presence, params, B, N, D, Din, Dout, L, layer_norm);
+  if (rc) return rc;
+  SCAE_REQUIRE(hsave && pg_partial);
+  a.hsave = const_cast<float *>(hsave);
+  a.pg_partial = pg_partial;
+  a.bf16_attention = bf16;
+  return use_wave(a, D) ? SCAE_OK : SCAE_ERR_UNSUPPORTED;
+}
+bool scae_st::wave_bwd_shape(int N, int D, int Din, int Dout, int L, int layer_norm) {
+  return scae_set_encoder_bf16_supported(N, D, Din, Dout, L, layer_norm) != 0;
+}
+
 #define SCAE_ENCODER_ENTRY(SUFFIX, BF)                                                          \
   extern "C" int scae_set_encoder_fwd_##SUFFIX(                                                 \
       int nseg, const float *const *seg_ptr, const int *seg_width, const int *seg_row_stride,   \

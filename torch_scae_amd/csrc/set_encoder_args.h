@@ -34,4 +34,15 @@ struct StArgs {
 // pg_partial = scae_set_encoder_grid(B), as for the workgroup-per-set kernels)
 bool wave_supported(const StArgs &a, int D);
 int wave_launch(const StArgs &a, bool bwd, int grid, hipStream_t st);
+
+// set_encoder.hip, for the launch the backward shares with the output attention's backward
+// (seed_bwd_gemm.hip): the argument block of scae_set_encoder_bwd_* without gz --
+// SCAE_ERR_UNSUPPORTED unless that launch would take the wave kernels -- and the same rule
+// on the shape alone
+int wave_bwd_args(StArgs &a, bool bf16, int nseg, const float *const *seg_ptr,
+                  const int *seg_width, const int *seg_row_stride,
+                  const int64_t *seg_batch_stride, float *const *seg_grad, const float *presence,
+                  const float *params, const float *hsave, float *pg_partial, int B, int N, int D,
+                  int Din, int Dout, int L, int layer_norm);
+bool wave_bwd_shape(int N, int D, int Din, int Dout, int L, int layer_norm);
 }  // namespace scae_st

@@ -621,9 +621,16 @@ __device__ __forceinline__ void flush_layer(const Wave &w, const Lay &lay, const
   }
 }
 
-template <int NT, bool BF>
-__global__ __launch_bounds__(64 * NT) void stw_bwd_kernel(StArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
+// The backward pass as a device function of workgroup `blk` of `nblk` (threads 0 .. 64 NT - 1
+// of the workgroup; `smem`: its dynamic LDS), like stw_fwd_body.  HANDED: the caller runs the
+// output attention's backward of the same set first (seed_bwd_gemm.hip) and hands over
+//   - the wave's tile of the gradient w.r.t. the trunk output in registers (G_in[e] = row
+//     16 t + 4 q + e, column r: what the MFMA left) instead of a.gz in memory, and
+//   - the LDS image zeroed, behind a barrier (the tiles rely on zero padding);
+// it has ONE set per workgroup (nblk = B): G_in is the gradient of set `blk`.
+template <int NT, bool BF, bool HANDED>
+__device__ __forceinline__ void stw_bwd_body(const StArgs &a, float *smem, int blk, int nblk,
+                                             f32x4 G_in) {
   const Lay lay{a.Din, a.L, a.layer_norm};
   const int N = a.N, Din = a.Din;
   Wave w;
@@ -638,20 +645,23 @@ __global__ __launch_bounds__(64 * NT) void stw_bwd_kernel(StArgs a) {
   if (blockIdx.x == 5 && threadIdx.x == 0) g_stw_n = 0;
 #endif
   STW_T();
-  lds_zero(smem, lds_total, threadIdx.x, 64 * NT);
-  lds_fence();
-  if (NT > 1) __syncthreads();
-  float *part = a.pg_partial + (size_t)blockIdx.x * lay.total();
+  if (!HANDED) {
+    lds_zero(smem, lds_total, threadIdx.x, 64 * NT);
+    lds_fence();
+    if (NT > 1) __syncthreads();
+  }
+  float *part = a.pg_partial + (size_t)blk * lay.total();
   STW_T();
   bool first = true;
-  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+  for (int b = blk; b < a.B; b += nblk) {
     f32x4 pres, G;
     float kmask[NT];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int n = 16 * w.t + 4 * w.q + e;
       pres[e] = n < N ? (a.presence ? a.presence[(size_t)b * N + n] : 1.f) : 0.f;
-      G[e] = n < N ? a.gz[((size_t)b * N + n) * D + w.r] : 0.f;
+      // (HANDED: the rows past the set are zeroed here, whatever the attention left there)
+      G[e] = n < N ? (HANDED ? G_in[e] : a.gz[((size_t)b * N + n) * D + w.r]) : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < NT; ++u) {
@@ -816,8 +826,18 @@ __global__ __launch_bounds__(64 * NT) void stw_bwd_kernel(StArgs a) {
     }
     first = false;
   STW_T();
+    // (one set per workgroup, said so that the compiler sees no loop: what does not depend
+    // on the set would be computed ahead of it and held in registers through every block --
+    // registers the launch's other workgroups are allocated too)
+    if (HANDED) break;
     if (NT > 1) __syncthreads();   // GT / GR / the hand-over area are reused
   }
+}
+
+template <int NT, bool BF>
+__global__ __launch_bounds__(64 * NT) void stw_bwd_kernel(StArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  stw_bwd_body<NT, BF, false>(a, smem, blockIdx.x, gridDim.x, splat(0.f));
 }
 
 // The forward pass as a device function of workgroup `blk` of `nblk` (threads 0 .. 64 NT - 1 of
@@ -974,5 +994,8 @@ int wave_launch(const StArgs &a, bool bwd, int grid, hipStream_t st) {
 // the LDS floats a forward workgroup needs (for the shared launch)
 template <int NT>
 static size_t stw_fwd_lds_floats(int Din) { return lds_floats_fwd_aliased<NT>(Din); }
+// ... and a backward workgroup
+template <int NT>
+static size_t stw_bwd_lds_floats(int Din) { return lds_floats<NT>(Din, true); }
 #endif
 }  // namespace scae_st

@@ -726,6 +726,61 @@ class _PendingFoldBackward:
                   ctypes.byref(self.grads), _stream(self.ref))
 
 
+class _TrunkBackwardOffer:
+    """RIDES['trunk_bwd']: the trunk's backward, offered at forward time to the
+    output attention's backward launch.  The trunk's backward reads of that
+    launch only its own set's rows of ``gh`` -- when the attention's input IS
+    the trunk's output ``z`` -- so the attention's workgroup of a set goes on
+    with the trunk's backward of that set (csrc/seed_bwd_gemm.hip).  ``node``
+    is the trunk's autograd context: saved tensors, dims, ``needs_input_grad``
+    and the bf16 flag are all known when the forward returns.  The carrier
+    leaves ``node.carried = (gh, partial, gsegs)`` for ``_SetEncoder.backward``."""
+
+    def __init__(self, node, z):
+        self.node, self.z_ptr, self.shape = node, z.data_ptr(), tuple(z.shape)
+
+    def carry(self, plan, lib, h, args, O, C, parked, gh):
+        """The merged launch (True), or nothing launched (False): the caller
+        then launches as if there had been no offer."""
+        t = self.node
+        B, N, D, Din, Dout, L, ln = t.dims
+        if not (plan.parking and plan.carry_trunk_bwd
+                and h.data_ptr() == self.z_ptr and tuple(h.shape) == self.shape
+                and t.bf16 == plan.bf16
+                and lib.scae_object_encoder_bwd_supported(B, N, O, C, D, Din,
+                                                          Dout, L, ln)):
+            return False
+        packed, hsave = t.saved_tensors[:2]
+        segs = list(t.saved_tensors[2:2 + t.nseg])
+        presence = t.saved_tensors[2 + t.nseg] if t.has_presence else None
+        partial, gsegs, gptrs = _trunk_bwd_outputs(t, packed, segs)
+        ptrs, widths, rs, bs = _seg_arrays(segs)
+        rc = getattr(lib, _prec("scae_object_encoder_bwd_gemm_f32"))(
+            *args, parked.descs, parked.n, len(segs), ptrs, widths, rs, bs,
+            gptrs, _p(presence), _p(packed), _p(hsave), _p(partial), B, N, D,
+            Din, Dout, L, ln, _stream(h))
+        if rc == _lib.ERR_UNSUPPORTED:
+            return False
+        _lib.check(rc, "scae_object_encoder_bwd_gemm")
+        t.carried = (gh, partial, gsegs)
+        return True
+
+
+def _trunk_bwd_outputs(ctx, packed, segs):
+    """What the trunk's backward launch writes: the per-workgroup parameter
+    gradients and the gradients of the segments that want one."""
+    B, N = ctx.dims[:2]
+    grid = _lib.load().scae_set_encoder_grid(B)
+    partial = torch.empty(grid, packed.numel(), device=packed.device,
+                          dtype=packed.dtype)
+    gsegs = [torch.empty(B, N, t.shape[2], device=t.device, dtype=t.dtype)
+             if ctx.needs_input_grad[3 + i] else None
+             for i, t in enumerate(segs)]
+    gptrs = (ctypes.c_void_p * len(segs))(
+        *[None if g is None else g.data_ptr() for g in gsegs])
+    return partial, gsegs, gptrs
+
+
 def flush_pending_backward():
     """Launch what is parked and nobody carried: the K1 backward (e.g. no
     gradient reached the capsule likelihood), the capsule MLPs' weight
@@ -777,6 +832,14 @@ class _SetEncoder(torch.autograd.Function):
         ctx.nseg = len(segs)
         ctx.dims = (B, N, D, Din, Dout, L, int(layer_norm))
         ctx.slot = _slot(packed, ctx)
+        ctx.carried = None
+        # RIDES['trunk_bwd'].  (Offered in every fused step: whether the backward
+        # runs inside a parking plan is known when it runs -- the carrier checks.)
+        if ctx.plan.fused and ctx.plan.carry_trunk_bwd and Dout == 0 and \
+                any(ctx.needs_input_grad) and \
+                lib.scae_set_encoder_bf16_supported(N, D, Din, Dout, L,
+                                                    int(layer_norm)):
+            ctx.plan.offer("trunk_bwd", _TrunkBackwardOffer(ctx, z))
         return z
 
     @_bwd
@@ -786,19 +849,20 @@ class _SetEncoder(torch.autograd.Function):
         presence = ctx.saved_tensors[2 + ctx.nseg] if ctx.has_presence else None
         B, N, D, Din, Dout, L, ln = ctx.dims
         gz = gz.contiguous()
-        grid = _lib.load().scae_set_encoder_grid(B)
-        partial = torch.empty(grid, packed.numel(), device=packed.device,
-                              dtype=packed.dtype)
-        gsegs = [torch.empty(B, N, t.shape[2], device=t.device, dtype=t.dtype)
-                 if ctx.needs_input_grad[3 + i] else None
-                 for i, t in enumerate(segs)]
-        ptrs, widths, rs, bs = _seg_arrays(segs)
-        gptrs = (ctypes.c_void_p * len(segs))(
-            *[None if g is None else g.data_ptr() for g in gsegs])
-        _lib.call("scae_set_encoder_bwd_bf16" if ctx.bf16 else
-                  "scae_set_encoder_bwd_f32", len(segs), ptrs, widths, rs, bs,
-                  gptrs, _p(presence), _p(packed), _p(hsave), _p(gz),
-                  _p(partial), B, N, D, Din, Dout, L, ln, _stream(packed))
+        carried, ctx.carried = ctx.carried, None
+        if carried is not None and carried[0].data_ptr() == gz.data_ptr():
+            # RIDES['trunk_bwd']: the output attention's backward launch ran this
+            # backward on the very gradient autograd now hands over (its own
+            # ``gh``: z had no second consumer, or this would be a sum)
+            _, partial, gsegs = carried
+        else:
+            # (after a carried launch too: its buffers are dropped)
+            partial, gsegs, gptrs = _trunk_bwd_outputs(ctx, packed, segs)
+            ptrs, widths, rs, bs = _seg_arrays(segs)
+            _lib.call("scae_set_encoder_bwd_bf16" if ctx.bf16 else
+                      "scae_set_encoder_bwd_f32", len(segs), ptrs, widths, rs,
+                      bs, gptrs, _p(presence), _p(packed), _p(hsave), _p(gz),
+                      _p(partial), B, N, D, Din, Dout, L, ln, _stream(packed))
         taken_before = ctx.slot is not None and ctx.slot.taken
         if ctx.slot is not None and not taken_before and \
                 any(sl.taken for sl in getattr(ctx.slot, "parts", ())):
@@ -924,7 +988,11 @@ class _SeedAttention(torch.autograd.Function):
                     _p(gout.contiguous()), _p(gh), _p(partial), B, N, O, C)
             plan = ctx.plan
             parked, carried = plan.take("wgrads"), False
-            if parked is not None:
+            trunk = plan.claim("trunk_bwd")
+            if parked is not None and trunk is not None:
+                # ... and the trunk's backward of each set behind its workgroup
+                carried = trunk.carry(plan, lib, h, args, O, C, parked, gh)
+            if parked is not None and not carried:
                 # the capsule MLPs' weight-gradient tiles as the tail of this launch
                 rc = getattr(lib, _prec("scae_seed_attention_mfma_bwd_gemm_f32"))(
                     *args, parked.descs, parked.n, _stream(h))

@@ -62,6 +62,11 @@ RIDES = collections.OrderedDict([
         "the reconstruction likelihood's forward (K1)",
         carriers=("_SetEncoder.forward",), scope="offer",
         abi="scae_set_encoder_fwd_logprob_f32")),
+    ("trunk_bwd", Ride(
+        "the object encoder trunk's backward (K2b), set by set behind the "
+        "output attention's",
+        carriers=("_SeedAttention.backward",), scope="offer",
+        abi="scae_object_encoder_bwd_gemm_f32")),
     ("class_probs", Ride(
         "SCAE.forward's two classifier heads (one wave per image)",
         carriers=("_LossTail.forward",), scope="fusing",
@@ -112,6 +117,9 @@ class StepPlan:
         self.held_sums = []
         self.prologue = prologue  # ops.StepPrologue or None
         self.bf16 = False         # configs[2]'s operand precision
+        # RIDES['trunk_bwd']: the output attention's backward launch also runs the
+        # trunk's backward of its set (False: the two launches, for A/B runs)
+        self.carry_trunk_bwd = True
         self.noise = {}           # (device, stream) -> (seed, generator state)
         # XORed into torch's seed for this plan's generators (0: the seed itself; a training
         # step's remainder step salts its own so that its draws are not the full step's)
