@@ -513,11 +513,12 @@ int scae_conv3x3_fwd_fold_f32(const float *in, const float *wf, const float *bia
                               int Cin, int Cout, int stride, const scae_seed_fold_desc *fold,
                               void *stream);
 /* K8r: the forward with the input images resident in LDS (csrc/conv_resident.hip), for the
- * small layers of the encoder: a workgroup owns `group` images x 32 output channels, stages
- * their input pixels once, reads the filter from its fragment-major copy `wp` (see relayout)
- * straight into MFMA fragments.  Same contract as scae_conv3x3_fwd_f32 otherwise (results agree
- * to fp32 round-off: the K sum is split by input-channel block).  Cin % 128 == 0,
- * Cout % 32 == 0, the group's pixels <= 64 KiB of LDS: scae_conv3x3_fwd_res_supported, else
+ * small layers of the encoder: a workgroup owns `group` images x 32 or 64 output channels, stages
+ * their input pixels once as three bf16 planes (6 bytes per element), reads the filter from its
+ * fragment-major copy `wp` (see relayout) straight into MFMA fragments.  Same contract as
+ * scae_conv3x3_fwd_f32 otherwise (results agree to fp32 round-off: the K sum is split by
+ * input-channel block).  Cin % 128 == 0, Cout % 32 == 0, the group's planes <= 80 KiB of LDS
+ * (two workgroups per CU; a forced group: 150 KiB): scae_conv3x3_fwd_res_supported, else
  * SCAE_ERR_UNSUPPORTED.  group: 0 = by shape; > 0 forces a group size (tests). */
 int scae_conv3x3_fwd_res_supported(int B, int IH, int IW, int Cin, int Cout, int stride);
 int scae_conv3x3_fwd_res_f32(const float *in, const float *wp, const float *bias, float *out,

@@ -18,7 +18,9 @@
 // hi mid, mid hi into the small accumulator, hi hi into the tile's -- so that consecutive MFMAs
 // write different accumulators.
 // The split costs ~5.5 VALU instructions per operand element and is done on the fragments in
-// registers, so no tensor changes its layout or its type: the data in HBM and LDS stay fp32.
+// registers, so no tensor changes its layout or its type: the data in HBM and LDS stay fp32
+// (one exception: conv_resident.hip splits its pixels once, on the way into LDS, and keeps the
+// three planes there).
 #pragma once
 #include "common.h"
 
