@@ -1033,8 +1033,24 @@ int scae_step_prologue_first_f32(float *dst_image, const float *src_image, int64
  *     xin = (k2 + k1 * i + k0 * j) >> 16      yin = (k5 + k4 * i + k3 * j) >> 16
  *     out[b, c, i, j] = x[row, c, yin - (H - h)/2, xin - (W - w)/2] inside the example, else 0
  *   (degrees = 0 without scale and shear gives the bits of affine = NULL); `translate` is
- *   not read then -- the table holds the shift.  position + (rank + 1) * B <= affine_rows.
- *   affine NULL (ctypes' zero): translation alone, as above. */
+ *   no switch then -- the table holds the shift -- but the sampling mode: 0 or 1 the nearest
+ *   form above, 2 bilinear.  position + (rank + 1) * B <= affine_rows.
+ *   Bilinear (translate = 2, affine non-NULL), int64 with arithmetic shifts as above:
+ *     U = k2 + k1 * i + k0 * j - 32768           V = k5 + k4 * i + k3 * j - 32768
+ *     x0 = (U >> 16) - (W - w)/2   fx = (U >> 8) & 255
+ *     y0 = (V >> 16) - (H - h)/2   fy = (V >> 8) & 255
+ *     t00 = x[row, c, y0, x0]  t01 = x[.., y0, x0 + 1]  t10 = x[.., y0 + 1, x0]  t11 = x[.., y0 + 1, x0 + 1]
+ *   each tap 0 where it falls outside the example or the row outside the dataset.
+ *   uint8: acc = (256 - fy) * ((256 - fx) * t00 + fx * t01) + fy * ((256 - fx) * t10 + fx * t11)
+ *   (an integer < 2^24), out = (float)acc / 16711680.0f, correctly rounded.  fp32: weights
+ *   fx / 256, (256 - fx) / 256, ... (exact); top = w_x0 * t00 + w_x1 * t01, bot likewise,
+ *   out = w_y0 * top + w_y1 * bot, every product and sum rounded to fp32 on its own.  At
+ *   integer coordinates (fx = fy = 0) these are the nearest form's bits.  A horizontal flip
+ *   or a shift range other than the pads is composed into the table's rows by the host
+ *   (data.affine_coefficients: flip=, max_shift=); the launch does not know of them.
+ *   affine NULL (ctypes' zero): translation alone, as above; translate must be 0 or 1.
+ *   Any other translate value (< 0, > 2, or 2 without a table) is refused (-1) before any
+ *   HIP call. */
 typedef struct scae_batch_source_desc {
   const void *images;     /* (rows, C, h, w) uint8 (image_u8 = 1) or fp32 in [0, 1] */
   const void *labels;     /* (rows) uint8 (label_u8 = 1) or int64; nullable without labels out */

@@ -22,7 +22,15 @@
 // Its six 16.16 fixed-point coefficients are row p of a table the host builds once per epoch
 // (include/scae_hip.h has the definition; data.affine_coefficients computes it in fp64); the
 // device only reads them and samples in integers, so every copy of an image holds the same
-// bits as data.affine_warp's.
+// bits as data.affine_warp's.  With a table the `translate` word is not a switch (the table
+// holds the shift) but the sampling mode: 0 / 1 nearest, 2 bilinear -- the four taps around
+// the map's point moved half a pixel back, weighted with the 8 fraction bits below the integer
+// part (U = k2 + k1 i + k0 j - 32768: x0 = U >> 16, fx = (U >> 8) & 255; likewise V), a tap
+// outside the example 0.  uint8 data: the weighted sum of the bytes as an integer (< 2^24),
+// one correctly rounded division by 255 * 65536; fp32 data: weights n / 256 (exact), every
+// product and sum rounded on its own, no contraction.  At integer coordinates it is the nearest
+// form's bits.  Horizontal flips and shift ranges other than the pads (data.py: flip=,
+// max_shift=) are composed into the table's rows on the host: nothing here reads them.
 #pragma once
 #include "common.h"
 #include "noise_dev.h"
@@ -98,6 +106,20 @@ __device__ __forceinline__ Draw draw(const scae_batch_source_desc &s, int64_t p)
   return d;
 }
 
+// a * x + b * y with both products and the sum rounded to fp32 (the bilinear form's fp32 rule,
+// data.affine_warp's torch ops).  The rounding intrinsics are plain operators to the compiler,
+// and under HIP's default -ffp-contract=fast the backend fuses a product into the sum whatever
+// a contract pragma says once this is inlined into a kernel (it did: v_pk_fma_f32).  The files
+// that include this header must keep their flags -- the prologue's other arithmetic holds its
+// bits under them -- so each product passes through an empty asm statement, which emits
+// nothing and leaves the backend no product to fuse.
+__device__ __forceinline__ float blend(float a, float x, float b, float y) {
+  float ax = __fmul_rn(a, x), by = __fmul_rn(b, y);
+  asm volatile("" : "+v"(ax));
+  asm volatile("" : "+v"(by));
+  return __fadd_rn(ax, by);
+}
+
 // dst[0 .. C*H*W) = the padded, shifted example of position p (all threads of a 256-thread
 // workgroup; no barrier).  Returns the draw.
 __device__ __forceinline__ Draw gather_image(const scae_batch_source_desc &s, int64_t p,
@@ -107,6 +129,43 @@ __device__ __forceinline__ Draw gather_image(const scae_batch_source_desc &s, in
   const uint8_t *img8 = static_cast<const uint8_t *>(s.images);
   const float *imgf = static_cast<const float *>(s.images);
   const size_t base = d.row < 0 ? 0 : (size_t)d.row * s.C * hw;
+  if (s.affine && s.translate == 2) {   // bilinear: 8-bit weights of the same fixed-point map
+    const int ph = (s.H - s.h) / 2, pw = (s.W - s.w) / 2;
+    for (int e = threadIdx.x; e < count; e += 256) {
+      const int ch = e / HW, rr = e - ch * HW, i = rr / s.W, j = rr - i * s.W;
+      const int64_t U = d.k[2] + (int64_t)d.k[1] * i + (int64_t)d.k[0] * j - 32768;
+      const int64_t V = d.k[5] + (int64_t)d.k[4] * i + (int64_t)d.k[3] * j - 32768;
+      const int64_t x0 = (U >> 16) - pw, y0 = (V >> 16) - ph;
+      const int fx = (int)((U >> 8) & 255), fy = (int)((V >> 8) & 255);
+      // the four taps' validity; a tap outside the example (or the dataset) is 0
+      const bool r0 = d.row >= 0 && y0 >= 0 && y0 < s.h, r1 = d.row >= 0 && y0 >= -1 && y0 < s.h - 1;
+      const bool c0 = x0 >= 0 && x0 < s.w, c1 = x0 >= -1 && x0 < s.w - 1;
+      // (clamped so that every formed offset lies inside the example; read only where valid)
+      const size_t ya = (size_t)(y0 < 0 ? 0 : y0 >= s.h ? s.h - 1 : y0);
+      const size_t yb = (size_t)(y0 + 1 < 0 ? 0 : y0 + 1 >= s.h ? s.h - 1 : y0 + 1);
+      const size_t xa = (size_t)(x0 < 0 ? 0 : x0 >= s.w ? s.w - 1 : x0);
+      const size_t xb = (size_t)(x0 + 1 < 0 ? 0 : x0 + 1 >= s.w ? s.w - 1 : x0 + 1);
+      const size_t plane = base + (size_t)ch * hw;
+      const size_t o00 = plane + ya * s.w + xa, o01 = plane + ya * s.w + xb;
+      const size_t o10 = plane + yb * s.w + xa, o11 = plane + yb * s.w + xb;
+      float v;
+      if (s.image_u8) {   // acc <= 255 * 65536 < 2^24: exact in fp32; one rounding, the division
+        const int t00 = r0 && c0 ? img8[o00] : 0, t01 = r0 && c1 ? img8[o01] : 0;
+        const int t10 = r1 && c0 ? img8[o10] : 0, t11 = r1 && c1 ? img8[o11] : 0;
+        const int acc = (256 - fy) * ((256 - fx) * t00 + fx * t01) +
+                        fy * ((256 - fx) * t10 + fx * t11);
+        v = __fdiv_rn((float)acc, 16711680.0f);   // 255 * 65536
+      } else {            // exact weights, every product and sum rounded on its own
+        const float t00 = r0 && c0 ? imgf[o00] : 0.f, t01 = r0 && c1 ? imgf[o01] : 0.f;
+        const float t10 = r1 && c0 ? imgf[o10] : 0.f, t11 = r1 && c1 ? imgf[o11] : 0.f;
+        const float wx1 = (float)fx * 0.00390625f, wx0 = (float)(256 - fx) * 0.00390625f;
+        const float wy1 = (float)fy * 0.00390625f, wy0 = (float)(256 - fy) * 0.00390625f;
+        v = blend(wy0, blend(wx0, t00, wx1, t01), wy1, blend(wx0, t10, wx1, t11));
+      }
+      dst[e] = v;
+    }
+    return d;
+  }
   if (s.affine) {   // nearest-neighbour through the inverse map, in integers
     const int ph = (s.H - s.h) / 2, pw = (s.W - s.w) / 2;
     for (int e = threadIdx.x; e < count; e += 256) {
@@ -154,6 +213,8 @@ inline int check(const scae_batch_source_desc *s, int B) {
   SCAE_REQUIRE((a.image_u8 == 0 || a.image_u8 == 1) && (a.label_u8 == 0 || a.label_u8 == 1));
   SCAE_REQUIRE(a.affine ? a.position + (int64_t)(a.rank + 1) * B <= a.affine_rows
                         : a.affine_rows == 0);
+  // (with a table `translate` is the sampling mode: 0 / 1 nearest, 2 bilinear)
+  SCAE_REQUIRE(a.translate >= 0 && a.translate <= (a.affine ? 2 : 1));
   if (a.C > 4) return SCAE_ERR_UNSUPPORTED;
   return 0;
 }

@@ -24,7 +24,10 @@ Every view also has a CPU path that computes the same order and shifts in
 integer torch ops.  A view's ``affine=`` adds the transform's other arguments
 (``degrees``, ``scale``, ``shear``) with nearest-neighbour resampling:
 ``affine_coefficients`` draws them and builds each position's fixed-point
-inverse map on the host, ``affine_warp`` is the CPU path of the sampling."""
+inverse map on the host, ``affine_warp`` is the CPU path of the sampling.  ``flip=`` and
+``max_shift=`` (RandomHorizontalFlip; a shift range other than the pads, as RandomCrop with
+padding) are composed into the same maps, and ``interpolation="bilinear"`` samples them with
+four taps and 8-bit weights."""
 import gzip
 import math
 
@@ -183,6 +186,36 @@ def translate_shifts(positions, epoch, seed, pads):
     return torch.stack([shift_rule(c[0] >> 8, pads[0]), shift_rule(c[1] >> 8, pads[1])], 1)
 
 
+def flip_bits(positions, epoch, seed):
+    """(len,) bool of epoch positions: True where ``flip=True`` mirrors the example
+    (RandomHorizontalFlip, p = 0.5) -- the top bit of word 2 of the Philox draw whose words 0
+    and 1 give the shifts (``translate_shifts``: counter (position, epoch, TAG_SHIFT), key =
+    ``seed``)."""
+    p = torch.as_tensor(positions).to(torch.int64)
+    c = _philox([p & _M32, _word(epoch, p), _word(epoch >> 32, p), _word(_TAG_SHIFT, p)],
+                seed & _M32, (seed >> 32) & _M32, _KEY_PHILOX_ROUNDS)
+    return (c[2] >> 31) == 1
+
+
+def shift_ranges(max_shift):
+    """``max_shift``: None, or (sy, sx) non-negative ints -- validated; -> None or (sy, sx).
+    ValueError on anything else."""
+    if max_shift is None:
+        return None
+    try:
+        sy, sx = max_shift
+    except (TypeError, ValueError):
+        raise ValueError(f"max_shift: (sy, sx) expected, got {max_shift!r}") from None
+    for v in (sy, sx):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"max_shift: non-negative ints expected, got {max_shift!r}")
+    return sy, sx
+
+
+INTERPOLATIONS = ("nearest", "bilinear")
+_IDENTITY = {"degrees": 0.0}     # (the table route of a view without ``affine``)
+
+
 def _range(v, name, symmetric=False):
     """(lo, hi) floats of a range argument; a number d means (-d, d) where ``symmetric``."""
     if isinstance(v, (int, float)) and not isinstance(v, bool):
@@ -227,7 +260,8 @@ def affine_ranges(affine):
     return {"degrees": deg, "scale": scale, "shear": shear}
 
 
-def affine_coefficients(positions, epoch, seed, pads, size, affine, translate=True):
+def affine_coefficients(positions, epoch, seed, pads, size, affine, translate=True, *,
+                        max_shift=None, flip=False, width=None):
     """(len, 6) int64 k0..k5 of epoch positions: each position's inverse affine map in 16.16
     fixed point, as Pillow's nearest-neighbour AFFINE path holds it (include/scae_hip.h,
     scae_batch_source_desc, has the definition).  One Philox draw keyed by ``seed`` at
@@ -238,8 +272,19 @@ def affine_coefficients(positions, epoch, seed, pads, size, affine, translate=Tr
     torchvision's ``_get_inverse_affine_matrix`` about (W / 2, H / 2) in fp64 and
     FIX(v) = floor(v 65536 + 0.5).  Every value is a function of (seed, epoch, position)
     alone.  ValueError where a coefficient leaves int32 (a scale too small, a shear too
-    close to 90 degrees)."""
+    close to 90 degrees).
+
+    ``max_shift`` = (sy, sx) replaces the pads as the translation's range (``shift_ranges``;
+    None: the pads).  ``flip``: positions whose ``flip_bits`` is set read the example mirrored
+    left to right -- composed into the map after FIX: with A1 = 2 pad_w + w (``width`` = w,
+    the example's width; default W - 2 pad_w, right where W - w is even),
+    k0' = -k0, k1' = -k1, k2' = 65536 A1 - 1 - k2, since for every integer K
+    (A1 - 1) - (K >> 16) == (65536 A1 - 1 - K) >> 16: exactly the mirrored column for the
+    nearest form, and the mirrored point less 2^-16 of a pixel for the bilinear one."""
     a = affine_ranges(affine)
+    max_shift = shift_ranges(max_shift)
+    if not isinstance(flip, bool):
+        raise ValueError(f"flip: a bool expected, got {flip!r}")
     p = torch.as_tensor(positions, dtype=torch.int64)
     H, W = size
     c = _philox([p & _M32, _word(epoch, p), _word(epoch >> 32, p), _word(_TAG_AFFINE, p)],
@@ -252,8 +297,8 @@ def affine_coefficients(positions, epoch, seed, pads, size, affine, translate=Tr
     scale = value(c[1], *a["scale"])
     sx = value(c[2], *a["shear"][:2]) * rad
     sy = value(c[3], *a["shear"][2:]) * rad
-    shifts = translate_shifts(p, epoch, seed, pads) if translate \
-        else torch.zeros(p.numel(), 2, dtype=torch.int64)
+    shifts = translate_shifts(p, epoch, seed, pads if max_shift is None else max_shift) \
+        if translate else torch.zeros(p.numel(), 2, dtype=torch.int64)
     ty, tx = shifts[:, 0].to(torch.float64), shifts[:, 1].to(torch.float64)
     cx, cy = W * 0.5, H * 0.5
     ma = torch.cos(rot - sy) / torch.cos(sy)
@@ -265,26 +310,75 @@ def affine_coefficients(positions, epoch, seed, pads, size, affine, translate=Tr
     m5 = m3 * (-cx - tx) + m4 * (-cy - ty) + cy
     k = torch.stack([m0, m1, m2 + m0 * 0.5 + m1 * 0.5, m3, m4, m5 + m3 * 0.5 + m4 * 0.5], 1)
     k = torch.floor(k * 65536.0 + 0.5)
+    if flip:
+        a1 = float(2 * pads[1] + (W - 2 * pads[1] if width is None else int(width)))
+        m = flip_bits(p, epoch, seed)
+        k[:, 0] = torch.where(m, -k[:, 0], k[:, 0])
+        k[:, 1] = torch.where(m, -k[:, 1], k[:, 1])
+        k[:, 2] = torch.where(m, a1 * 65536.0 - 1.0 - k[:, 2], k[:, 2])
     if not bool((torch.isfinite(k) & (k.abs() < float(1 << 31))).all()):
         raise ValueError("affine: a coefficient does not fit 16.16 fixed point in int32 "
                          "(scale too small or shear too close to 90 degrees)")
     return k.to(torch.int64)
 
 
-def affine_warp(images, coeffs, out_size):
+def _affine_warp_bilinear(images, k, out_size):
+    """``affine_warp``'s bilinear form (k: (B, 6, 1, 1) int64)."""
+    B, C, h, w = images.shape
+    H, W = out_size
+    ph, pw = (H - h) // 2, (W - w) // 2
+    i = torch.arange(H, device=images.device).view(1, H, 1)
+    j = torch.arange(W, device=images.device).view(1, 1, W)
+    U = k[:, 2] + k[:, 1] * i + k[:, 0] * j - 32768                     # (B,H,W)
+    V = k[:, 5] + k[:, 4] * i + k[:, 3] * j - 32768
+    x0, fx = (U >> 16) - pw, (U >> 8) & 255
+    y0, fy = (V >> 16) - ph, (V >> 8) & 255
+    u8 = not images.dtype.is_floating_point
+    src = (images.to(torch.int64) if u8 else images.to(torch.float32)).reshape(B, C, h * w)
+
+    def tap(y, x):
+        valid = (y >= 0) & (y < h) & (x >= 0) & (x < w)
+        flat = y.clamp(0, h - 1) * w + x.clamp(0, w - 1)
+        t = torch.gather(src, 2, flat.view(B, 1, H * W).expand(B, C, H * W))
+        return t.view(B, C, H, W) * valid.unsqueeze(1)
+    t00, t01, t10, t11 = tap(y0, x0), tap(y0, x0 + 1), tap(y0 + 1, x0), tap(y0 + 1, x0 + 1)
+    fx, fy = fx.unsqueeze(1), fy.unsqueeze(1)
+    if u8:      # an integer < 2^24: exact in fp32, then one correctly rounded division
+        acc = (256 - fy) * ((256 - fx) * t00 + fx * t01) + fy * ((256 - fx) * t10 + fx * t11)
+        return (acc.to(torch.float32) / 16711680.0).contiguous()        # 255 * 65536
+    wx1, wx0 = fx.to(torch.float32) / 256.0, (256 - fx).to(torch.float32) / 256.0
+    wy1, wy0 = fy.to(torch.float32) / 256.0, (256 - fy).to(torch.float32) / 256.0
+    top, bot = wx0 * t00 + wx1 * t01, wx0 * t10 + wx1 * t11   # (each op rounds on its own)
+    return (wy0 * top + wy1 * bot).contiguous()
+
+
+def affine_warp(images, coeffs, out_size, interpolation="nearest"):
     """images (B, C, h, w) uint8 or float, ``coeffs`` (B, 6) integer k0..k5
     (``affine_coefficients``) -> (B, C, H, W) float32: the example, zero-padded to
     ``out_size`` = (H, W), resampled through its inverse map with nearest-neighbour sampling
     in pure integers -- pixel (i, j) reads padded-image pixel (yin, xin) =
     ((k5 + k4 i + k3 j) >> 16, (k2 + k1 i + k0 j) >> 16), zero outside the example --
-    then ToTensor's division for uint8.  The CPU path of the device gather's affine form."""
+    then ToTensor's division for uint8.  The CPU path of the device gather's affine form.
+
+    ``interpolation="bilinear"``: the four taps around the same fixed-point point moved half
+    a pixel back, U = k2 + k1 i + k0 j - 32768 (x0 = (U >> 16) - pad_w, fx = (U >> 8) & 255;
+    V, y0, fy likewise), a tap outside the example 0, weighted with the 8-bit fractions:
+    uint8 data as an integer sum divided once by 255 * 65536, fp32 data with the exact weights
+    n / 256 and every product and sum rounded to fp32 on its own (include/scae_hip.h has the
+    rule) -- the device form's bits, and at integer coordinates the nearest form's.  Not
+    Pillow's bilinear, which computes in fp64 per pixel and treats edges differently."""
     B, C, h, w = images.shape
     H, W = out_size
     if H < h or W < w:
         raise ValueError("output smaller than the images")
+    if interpolation not in INTERPOLATIONS:
+        raise ValueError(f"interpolation: one of {INTERPOLATIONS} expected, "
+                         f"got {interpolation!r}")
     k = torch.as_tensor(coeffs).to(images.device, torch.int64)
     if tuple(k.shape) != (B, 6):
         raise ValueError(f"coeffs ({B}, 6) expected, got {tuple(k.shape)}")
+    if interpolation == "bilinear":
+        return _affine_warp_bilinear(images, k.view(B, 6, 1, 1), out_size)
     x = images.to(torch.float32)
     if not images.dtype.is_floating_point:
         x = x / 255.0                         # ToTensor
@@ -341,16 +435,17 @@ class ResidentDataset:
         return self.n
 
     def view(self, shuffle=False, translate=True, seed=0, rank=0, world=1, drop_last=True,
-             affine=None):
+             affine=None, flip=False, max_shift=None, interpolation="nearest"):
         """The whole dataset as one view (``DatasetView``)."""
         return DatasetView(self, None, shuffle, translate, seed, rank, world, drop_last,
-                           affine)
+                           affine, flip, max_shift, interpolation)
 
     def split(self, lengths, generator=None, **view_args):
         """Views over the rows ``torch.utils.data.random_split(range(N), lengths,
         generator)`` gives (``torch.randperm(N, generator=generator)`` cut in turn); lengths
         are integers summing to N.  ``view_args`` (shuffle, translate, seed, rank, world,
-        drop_last, affine) apply to every view; a view's attributes can be changed afterwards."""
+        drop_last, affine, flip, max_shift, interpolation) apply to every view; a view's
+        attributes can be changed afterwards."""
         lengths = [int(v) for v in lengths]
         if sum(lengths) != self.n or any(v <= 0 for v in lengths):
             raise ValueError("lengths must be positive and sum to the dataset's size")
@@ -393,11 +488,26 @@ class DatasetView:
     host-to-device copy, and every other step of the epoch stays "prologue launch + replay,
     no torch operator, no copy".  An affinely warped test view (affNIST-style viewpoint
     checks) is ``ds.view(translate=False, affine=...)``.
+
+    Three more arguments ride in the same table (without ``affine`` it is built with degrees
+    0, scale 1, shear 0) and cost the device nothing of their own:
+    ``flip=True`` is RandomHorizontalFlip(p = 0.5): the positions whose ``flip_bits`` is set
+    read their example mirrored left to right, before padding, shift or warp.
+    ``max_shift=(sy, sx)`` (non-negative ints) replaces the pads as the translation's range
+    where ``translate`` is on: dy = ``shift_rule(r, sy)``, dx = ``shift_rule(r, sx)`` of the
+    same draw; a range beyond the pad cuts off what leaves the frame and fills with zeros.
+    On an unpadded 32 x 32 dataset ``max_shift=(4, 4)`` is RandomCrop(32, padding=4) up to
+    the endpoint rule: ``shift_rule`` is round(U(-s, s)), so -s and +s each come up half as
+    often as the values between, where RandomCrop draws uniform integers.
+    ``interpolation="bilinear"`` samples the four neighbours with 8-bit weights instead of
+    the nearest pixel (``affine_warp`` has the rule; smooth strokes under rotation); at
+    integer coordinates -- ``degrees=0`` -- it is the nearest form bit for bit.
     ``epoch`` / ``cursor`` (steps taken in the epoch) advance with ``TrainStep.step_from``;
     ``state_dict`` carries them so that a resumed run continues in the same order."""
 
     def __init__(self, dataset, index=None, shuffle=False, translate=True, seed=0, rank=0,
-                 world=1, drop_last=True, affine=None):
+                 world=1, drop_last=True, affine=None, flip=False, max_shift=None,
+                 interpolation="nearest"):
         self.dataset = dataset
         if index is not None:
             index = torch.as_tensor(index).to("cpu", torch.int64).contiguous()
@@ -417,8 +527,25 @@ class DatasetView:
         if not self.drop_last and self.n < self.world:
             raise ValueError(f"{self.n} examples cannot give each of {self.world} ranks one")
         self.affine = affine_ranges(affine)
+        self.flip, self.max_shift, self.interpolation = \
+            self._options(flip, max_shift, interpolation)
         self._tables = {}               # (device coefficient tables: ``_affine_table``)
         self.epoch = self.cursor = 0
+
+    @staticmethod
+    def _options(flip, max_shift, interpolation):
+        if not isinstance(flip, bool):
+            raise ValueError(f"flip: a bool expected, got {flip!r}")
+        if interpolation not in INTERPOLATIONS:
+            raise ValueError(f"interpolation: one of {INTERPOLATIONS} expected, "
+                             f"got {interpolation!r}")
+        return flip, shift_ranges(max_shift), interpolation
+
+    @property
+    def uses_table(self):
+        """The view's examples are sampled through the epoch's coefficient table."""
+        return self.affine is not None or self.flip or self.max_shift is not None \
+            or self.interpolation != "nearest"
 
     def __len__(self):
         return self.n
@@ -457,7 +584,8 @@ class DatasetView:
         vr = feistel_order(q, self.n, self.seed, epoch) if self.shuffle else q
         rows = vr if self.index is None else self.index[vr]
         ds = self.dataset
-        shifts = translate_shifts(p, epoch, self.seed, ds.pads) if self.translate \
+        lim = ds.pads if self.max_shift is None else self.max_shift
+        shifts = translate_shifts(p, epoch, self.seed, lim) if self.translate \
             else torch.zeros(p.numel(), 2, dtype=torch.int64)
         return rows, shifts
 
@@ -465,18 +593,22 @@ class DatasetView:
         return self.rows_and_shifts(epoch, self.positions(step, batch))
 
     def coefficients(self, epoch, positions):
-        """(len, 6) int64 inverse-map coefficients of epoch positions (``affine`` views; a
-        position p >= n keeps p for its draw, as for its shift) -- the CPU path."""
+        """(len, 6) int64 inverse-map coefficients of epoch positions (views that use the
+        table: ``affine``, ``flip``, ``max_shift``, bilinear; a position p >= n keeps p for
+        its draws, as for its shift) -- the CPU path."""
         ds = self.dataset
         return affine_coefficients(positions, epoch, self.seed, ds.pads, (ds.H, ds.W),
-                                   self.affine, self.translate)
+                                   _IDENTITY if self.affine is None else self.affine,
+                                   self.translate, max_shift=self.max_shift, flip=self.flip,
+                                   width=ds.w)
 
     def _cpu_batch(self, epoch, positions):
         rows, shifts = self.rows_and_shifts(epoch, positions)
         ds = self.dataset
         src = ds.images[rows.to(ds.device)].cpu()
-        if self.affine is not None:
-            image = affine_warp(src, self.coefficients(epoch, positions), (ds.H, ds.W))
+        if self.uses_table:
+            image = affine_warp(src, self.coefficients(epoch, positions), (ds.H, ds.W),
+                                self.interpolation)
         else:
             image = pad_and_translate(src, (ds.H, ds.W), shifts=shifts)
         return image, ds.labels[rows.to(ds.device)].cpu().to(torch.int64)
@@ -502,7 +634,8 @@ class DatasetView:
         ds = self.dataset
         count = self.n + (0 if self.drop_last else self.world - 1)
         key = (int(epoch), self.seed, self.translate, count,
-               tuple(sorted(self.affine.items())))
+               None if self.affine is None else tuple(sorted(self.affine.items())),
+               self.flip, self.max_shift, self.interpolation)
         table = self._tables.get(key)
         if table is None:
             table = self.coefficients(epoch, torch.arange(count)).to(torch.int32) \
@@ -530,9 +663,11 @@ class DatasetView:
         d.seed, d.epoch, d.position = self.seed, int(epoch), int(position)
         d.rank, d.world = self.rank if rank is None else rank, self.world
         d.wrap = int(not self.drop_last)
-        if self.affine is not None:
+        if self.uses_table:
             table = self._affine_table(epoch)
             d.affine, d.affine_rows = table.data_ptr(), table.shape[0]
+            if self.interpolation == "bilinear":
+                d.translate = 2         # (with a table: the sampling mode)
         return d
 
     def check(self, batch, image_shape):
@@ -587,7 +722,9 @@ class DatasetView:
                 "shuffle": self.shuffle, "translate": self.translate, "n": self.n,
                 "rank": self.rank, "world": self.world, "drop_last": self.drop_last,
                 "affine": None if self.affine is None else
-                {k: list(v) for k, v in self.affine.items()}}
+                {k: list(v) for k, v in self.affine.items()},
+                "flip": self.flip, "interpolation": self.interpolation,
+                "max_shift": None if self.max_shift is None else list(self.max_shift)}
 
     def load_state_dict(self, sd):
         if sd.get("n", self.n) != self.n or sd.get("world", self.world) != self.world:
@@ -598,6 +735,10 @@ class DatasetView:
         self.drop_last = bool(sd.get("drop_last", self.drop_last))
         if "affine" in sd:
             self.affine = affine_ranges(sd["affine"])
+        # (a state written before these arguments existed leaves the view's own)
+        self.flip, self.max_shift, self.interpolation = self._options(
+            sd.get("flip", self.flip), sd.get("max_shift", self.max_shift),
+            sd.get("interpolation", self.interpolation))
         self.epoch, self.cursor = int(sd["epoch"]), int(sd["cursor"])
 
 

@@ -203,3 +203,26 @@ def make_train_step(model, cfg: dict, **kw):
         args["track_grad_norm"] = track_value(track)
     args.update(kw)
     return TrainStep(model, int(cfg["data_loader"]["batch_size"]), shape, **args)
+
+
+_AUGMENT_KEYS = ("translate", "max_shift", "flip", "affine", "interpolation")
+
+
+def make_train_view(dataset, cfg: dict, **kw):
+    """The training view of ``dataset`` (``data.ResidentDataset``) the plain-dict config asks
+    for: shuffled, seeded with ``cfg.get("seed", 0)``, transformed as ``dataset.augment`` says
+    -- a dict with any of ``translate``, ``max_shift``, ``flip``, ``affine``,
+    ``interpolation`` (``data.DatasetView``'s arguments; an unknown key raises ValueError).
+    Without the key the view is the reference's transform, ``translate=True`` alone
+    (mnist/experiment.py:23-40).  ``kw``: further view arguments (rank, world, drop_last, ...),
+    which override."""
+    augment = (cfg.get("dataset") or {}).get("augment")
+    if augment is None:
+        augment = dict(translate=True)
+    if not isinstance(augment, dict) or set(augment) - set(_AUGMENT_KEYS):
+        raise ValueError(f"dataset.augment: a dict with keys of {_AUGMENT_KEYS} expected, "
+                         f"got {augment!r}")
+    args = dict(shuffle=True, seed=int(cfg.get("seed", 0)))
+    args.update(augment)
+    args.update(kw)
+    return dataset.view(**args)
