@@ -333,7 +333,7 @@ class RMSpropFlat(_Accumulating):
     def __init__(self, flat: FlatParameters, lr=3e-5, alpha=0.99, eps=1e-8,
                  momentum=0.9, weight_decay=0.0, look_ahead=False,
                  look_ahead_k=5, look_ahead_alpha=0.5, gradient_clip_val=0.0,
-                 accumulate_grad_batches=1):
+                 accumulate_grad_batches=1, nonfinite=None):
         self.flat = flat
         self.lr, self.alpha, self.eps, self.momentum = lr, alpha, eps, momentum
         self.weight_decay = weight_decay
@@ -343,6 +343,7 @@ class RMSpropFlat(_Accumulating):
                                  dtype=flat.flat_param.dtype)
         _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
         _init_clip(self, gradient_clip_val)
+        _init_guard(self, nonfinite)
         _init_track(self)
         _init_accumulate(self, accumulate_grad_batches)
 
@@ -371,7 +372,7 @@ class RMSpropFlat(_Accumulating):
                         (self.momentum, self.alpha), grad_scale, sum_units,
                         self._cpu_update, acc)
             return
-        if self.max_norm:
+        if self.max_norm or self.nonfinite:
             self._clipped_step(grad_scale, sum_units, acc)
             return
         g = self.flat.flat_grad
@@ -458,7 +459,8 @@ class RMSpropFlat(_Accumulating):
         """``step`` with clipping by global norm: the norm launch (``sum_units`` ride in
         it), then scae_rmsprop_clip_step_f32 over each active range; on CPU tensors
         ``_cpu_update`` on the clipped gradient.  ``acc``: of acc + g (the accumulate
-        forms), acc -> 0."""
+        forms), acc -> 0.  On CPU tensors also the guarded step (``_init_guard``), with or
+        without clipping."""
         flat = self.flat
         g = flat.flat_grad
         seen = _group_seen(self)
@@ -470,8 +472,11 @@ class RMSpropFlat(_Accumulating):
             if acc is not None:
                 g = acc + g
                 acc.zero_()
+            g = _cpu_effective_grad(self, g, grad_scale, seen)
+            if g is None:      # (the guard: nothing is written)
+                return
             saved = _keep_inactive(self, ranges, [flat.flat_param, self.square_avg, self.buf])
-            self._cpu_update(_cpu_clipped_grad(self, g, grad_scale, seen), None)
+            self._cpu_update(g, None)
             _restore_inactive(saved)
             return
         from . import _lib
@@ -557,6 +562,71 @@ def _init_clip(opt, gradient_clip_val):
         from ._lib import GRAD_SQ_MAX_PARTIALS
         opt.grad_sq = torch.zeros(GRAD_SQ_MAX_PARTIALS, dtype=torch.float64, device=dev)
         opt.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+
+
+def nonfinite_value(v):
+    """``nonfinite`` -> None (off), "skip" or "raise"; anything else is an error."""
+    if v is None:
+        return None
+    if isinstance(v, str) and v.lower() in ("skip", "raise"):
+        return v.lower()
+    raise ValueError(f"nonfinite must be None, 'skip' or 'raise', got {v!r}")
+
+
+def _init_guard(opt, nonfinite):
+    """The non-finite guard (``nonfinite="skip"``; off by default): an optimiser step whose
+    gradient -- the one the step consumes: acc + g when accumulating, after the all-reduce --
+    holds a NaN or +-Inf element writes nothing.  Parameters, moments, LookAhead's slow
+    weights and ``step_state`` keep their bits, acc is zeroed (the group is dropped), and the
+    skip is counted in ``guard_state``, int64 {skipped, first, last, attempts}: attempts
+    counts guarded optimiser steps, first / last are the attempts values (0-based) of the
+    first and last skipped one, -1 before any.  The rule: the fp64 sum of squares is finite
+    exactly when every element is (the fp32 norm may overflow for finite gradients and does
+    not decide).  A finite step has the unguarded step's bits; ``grad_norm`` is written either
+    way, and a tracking optimiser's ``GradNorms`` row is still written for a skipped step.
+    CPU tensors only so far: there is no device form of the guard yet, and asking for it on a
+    HIP device raises (nothing falls back to an unguarded step)."""
+    if nonfinite not in (None, "skip"):
+        raise ValueError(f"an optimiser's nonfinite must be None or 'skip', got {nonfinite!r}")
+    opt.nonfinite = nonfinite
+    opt.guard_state = None
+    if nonfinite:
+        dev = opt.flat.flat_param.device
+        if dev.type != "cpu":
+            from ._lib import ScaeHipError
+            raise ScaeHipError("nonfinite='skip' has no device form yet: the guarded optimiser "
+                               "passes are not built, and the step does not run unguarded")
+        if opt.grad_norm is None:
+            opt.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+        opt.guard_state = torch.tensor([0, -1, -1, 0], dtype=torch.int64, device=dev)
+
+
+def _cpu_guard_skips(opt, g, grad_scale):
+    """(CPU forms) The guard's decision on ``g`` (acc already folded in and zeroed), counted
+    in ``guard_state``; on a skip, or without clipping, the norm into ``grad_norm``."""
+    sq = g.double().square().sum()
+    skip = not bool(torch.isfinite(sq))
+    gs = opt.guard_state
+    t = int(gs[3])
+    if skip:
+        gs[0] += 1
+        if int(gs[1]) < 0:
+            gs[1] = t
+        gs[2] = t
+    gs[3] = t + 1
+    if skip or not opt.max_norm:
+        opt.grad_norm.copy_((float(grad_scale) * sq.sqrt()).float())
+    return skip
+
+
+def _cpu_effective_grad(opt, g, grad_scale, seen=None):
+    """(CPU forms) The gradient the update consumes -- scaled, clipped when clipping -- or
+    None when the guard skips the step."""
+    if opt.nonfinite and _cpu_guard_skips(opt, g, grad_scale):
+        return None
+    if opt.max_norm:
+        return _cpu_clipped_grad(opt, g, grad_scale, seen)
+    return g * grad_scale if grad_scale != 1.0 else g
 
 
 def track_value(v):
@@ -667,7 +737,9 @@ class GradNorms:
     (``norm_segments``), then the total -- in a device ring of ``capacity`` rows whose cursor
     the launch itself advances (scae_segment_norms_f32; on CPU tensors ``segment_norms_host``).
     The segment table is fixed by the first ``build``: after a backward, outside any capture.
-    ``count``: the host's mirror of the cursor (the step that owns the optimiser counts)."""
+    ``count``: the host's mirror of the cursor (the step that owns the optimiser counts).
+    A step the non-finite guard skips (``_init_guard``) still writes its row, ahead of the pass:
+    the row shows which segment blew up, and its total is non-finite."""
 
     def __init__(self, flat, model, p, capacity=1, split_capsules=True):
         self.flat, self.model, self.p = flat, model, float(p)
@@ -861,7 +933,8 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update, acc=None):
     tensors: the host-logic tests).  Parameters without a gradient are left alone,
     like torch.optim does; without weight decay a zero gradient already is a no-op
     (zero moments stay zero, LookAhead's slow copy of such a parameter equals it).
-    ``acc``: the accumulate forms (scae_flat_opt_acc_*: the gradient is acc + g, acc -> 0)."""
+    ``acc``: the accumulate forms (scae_flat_opt_acc_*: the gradient is acc + g, acc -> 0).
+    On CPU tensors the guard (``_init_guard``) decides first."""
     flat = opt.flat
     g = flat.flat_grad
     clip = opt.max_norm and g.is_cuda
@@ -911,10 +984,9 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update, acc=None):
         acc.zero_()
     if not ranges:
         return
-    if opt.max_norm:
-        g = _cpu_clipped_grad(opt, g, grad_scale, seen)
-    elif grad_scale != 1.0:
-        g = g * grad_scale
+    g = _cpu_effective_grad(opt, g, grad_scale, seen)
+    if g is None:      # (the guard: nothing is written, the step count stays)
+        return
     bufs = [flat.flat_param, m, v] + ([opt.slow] if opt.slow is not None else [])
     if opt.weight_decay != 0:
         keep = torch.zeros_like(g, dtype=torch.bool)
@@ -949,7 +1021,8 @@ class _FlatAdamBase(_Accumulating):
 
     def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=0.0, look_ahead=False, look_ahead_k=5,
-                 look_ahead_alpha=0.5, gradient_clip_val=0.0, accumulate_grad_batches=1):
+                 look_ahead_alpha=0.5, gradient_clip_val=0.0, accumulate_grad_batches=1,
+                 nonfinite=None):
         b1, b2 = (float(b) for b in betas)
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
             raise ValueError(f"betas must lie in [0, 1), got {betas}")
@@ -962,6 +1035,7 @@ class _FlatAdamBase(_Accumulating):
                                  dtype=flat.flat_param.dtype)
         _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
         _init_clip(self, gradient_clip_val)
+        _init_guard(self, nonfinite)
         _init_track(self)
         _init_accumulate(self, accumulate_grad_batches)
 
@@ -1041,14 +1115,18 @@ class RAdamFlat(_FlatAdamBase):
 
 def make_optimizer(kind, flat, lr, eps, betas=(0.9, 0.999), momentum=0.9,
                    weight_decay=0.0, look_ahead=False, look_ahead_k=5,
-                   look_ahead_alpha=0.5, gradient_clip_val=0.0, accumulate_grad_batches=1):
+                   look_ahead_alpha=0.5, gradient_clip_val=0.0, accumulate_grad_batches=1,
+                   nonfinite=None):
     """``kind``: "rmsprop" | "adam" | "radam" (any case) -> the flat optimiser.
     ``gradient_clip_val`` > 0: every step clips the gradient to that global norm first.
-    ``accumulate_grad_batches`` > 1: the optimiser keeps an accumulator (``accumulate``)."""
+    ``accumulate_grad_batches`` > 1: the optimiser keeps an accumulator (``accumulate``).
+    ``nonfinite="skip"``: a step whose gradient holds a NaN or Inf writes nothing and is
+    counted (``_init_guard``: CPU tensors only so far, a HIP device raises); None (the
+    default): the step as it was."""
     name = str(kind).lower()
     la = dict(look_ahead=look_ahead, look_ahead_k=look_ahead_k,
               look_ahead_alpha=look_ahead_alpha, gradient_clip_val=gradient_clip_val,
-              accumulate_grad_batches=accumulate_grad_batches)
+              accumulate_grad_batches=accumulate_grad_batches, nonfinite=nonfinite)
     if name == "rmsprop":
         return RMSpropFlat(flat, lr=lr, momentum=momentum, eps=eps,
                            weight_decay=weight_decay, **la)

@@ -169,11 +169,15 @@ def make_train_step(model, cfg: dict, **kw):
     when absent or <= 0; a non-numeric or non-finite value raises ValueError) and
     ``trainer.accumulate_grad_batches`` (gradient accumulation over that many batches: 1 when
     absent; anything but an int >= 1 raises ValueError) and ``trainer.track_grad_norm`` (per-parameter
-    gradient norms: 1, 2 or 'inf'; off when absent, -1 or 0; anything else raises ValueError).  The reference reads LookAhead's k and alpha from
+    gradient norms: 1, 2 or 'inf'; off when absent, -1 or 0; anything else raises ValueError)
+    and the non-finite guard (``TrainStep(nonfinite=...)``): ``trainer.terminate_on_nan``
+    (Lightning's flag: true -> "raise", false or absent -> off; anything but a bool raises
+    ValueError) and ``trainer.nonfinite`` ("skip" | "raise"; null: off; anything else raises
+    ValueError; it wins over ``terminate_on_nan`` when both are set).  The reference reads LookAhead's k and alpha from
     ``cfg.optimizer``, where none of its yaml files defines them
     (base_experiment.py:67-70); they are read from ``meta_optimizer`` here,
     where config.yaml puts them.  ``kw``: further TrainStep arguments."""
-    from .data_parallel import accumulate_value, clip_value, track_value
+    from .data_parallel import accumulate_value, clip_value, nonfinite_value, track_value
     from .train_step import TrainStep
     opt = cfg["optimizer"]
     kind = _OPTIMIZERS.get(opt["type"])
@@ -201,6 +205,15 @@ def make_train_step(model, cfg: dict, **kw):
     track = trainer.get("track_grad_norm")
     if track is not None:
         args["track_grad_norm"] = track_value(track)
+    nan = trainer.get("terminate_on_nan")
+    if nan is not None:
+        if not isinstance(nan, bool):
+            raise ValueError(f"trainer.terminate_on_nan must be a bool, got {nan!r}")
+        if nan:
+            args["nonfinite"] = "raise"
+    mode = trainer.get("nonfinite")
+    if mode is not None:
+        args["nonfinite"] = nonfinite_value(mode)
     args.update(kw)
     return TrainStep(model, int(cfg["data_loader"]["batch_size"]), shape, **args)
 

@@ -15,8 +15,21 @@ from . import ops
 from . import replay as _replay   # (``replay`` is the steps' constructor argument)
 from .data_parallel import (FlatParameters, GradNorms, _group_seen, accumulate_value,
                             all_reduce_gradients, broadcast_parameters, clip_value,
-                            load_optimizer_state_dict, make_optimizer, optimizer_state_dict,
-                            segment_norms_host, track_value, world)
+                            load_optimizer_state_dict, make_optimizer, nonfinite_value,
+                            optimizer_state_dict, segment_norms_host, track_value, world)
+
+
+class NonFiniteGradientError(ValueError):
+    """``TrainStep(nonfinite="raise")``: optimiser steps were skipped because their gradient
+    held a NaN or Inf element.  ``skipped``, ``first``, ``last``, ``attempts``: the guard's
+    counters when it was raised."""
+
+    def __init__(self, counters):
+        self.__dict__.update(counters)
+        super().__init__(
+            "{skipped} of {attempts} optimiser steps had a non-finite gradient and were "
+            "skipped (the first: optimiser step {first}, the last: {last}, 0-based); the "
+            "parameters and the optimiser's state are those of the steps taken".format(**counters))
 
 
 # the remainder step's noise generators: keyed by torch's seed XOR this (step_plan.StepPlan.
@@ -132,6 +145,32 @@ class TrainStep:
     trained state equals the untracked step's bit for bit.  ``grad_norm_names()``,
     ``last_grad_norms()``, ``grad_norm_history()``; ``parameter_norms()`` for the weights'.  The
     remainder step and ``end_epoch``'s step on a pending group write to the same ring.
+
+    ``nonfinite``: what an optimiser step does whose gradient -- the one the optimiser
+    consumes: after the all-reduce, the group's sum when accumulating -- holds a NaN or +-Inf
+    element.  None (the default): nothing special, the step is exactly the one it was (and one
+    such element reaches the moments, then the parameters, then everything).  ``"skip"``: the
+    form of Lightning's ``Trainer(terminate_on_nan)`` that mixed-precision harnesses carry:
+    the step writes nothing -- parameters, both moment buffers, the momentum buffer,
+    LookAhead's slow weights, the step count and the slow-made flag keep their bits, a
+    poisoned accumulated group is dropped (acc zeroed) -- and is counted ({skipped, first,
+    last, attempts}, int64, beside the optimiser's state).  The fp64 sum of squares of the
+    gradient decides: finite exactly when every element is (the fp32 norm, which can overflow
+    for finite gradients, does not).  A finite step has the unguarded step's bits.  With a
+    collective the sum is taken after the all-reduce, so every rank decides alike.
+    ``"raise"``: the same, and ``end_epoch()`` reads the counters (one read per epoch, never
+    one per step) and raises ``NonFiniteGradientError`` when a step was skipped since the
+    last check; ``check_nonfinite()`` does so on demand.  ``nonfinite_steps()``: the counters.
+    The guard is on the GRADIENT: a non-finite loss whose gradients are all finite is not
+    detected.  A tracked ``GradNorms`` row is written for a skipped step too (its total is
+    non-finite: the row shows which segment blew up), and ``last_grad_norm()`` shows the NaN
+    or Inf.  ``steps`` and ``optimizer_steps`` stay HOST counts of batches and of ATTEMPTED
+    optimiser steps, skipped ones included; ``optimizer_state_dict()`` reports ``step`` as the
+    optimiser's own count where it keeps one and as ``optimizer_steps - skipped`` for plain
+    RMSprop.  ``snapshot()`` / ``restore()`` carry the counters.  So far the guard exists for
+    CPU tensors only (the flat optimisers' CPU forms): the guarded forms of the HIP optimiser
+    passes are not built, and a step on a HIP device that asks for the guard raises
+    ``ScaeHipError`` when it is constructed -- it never runs unguarded.
     """
 
     MODES = ("2 buckets", "1 bucket", "in graph")
@@ -144,7 +183,7 @@ class TrainStep:
                  replay="graph", betas=(0.9, 0.999),
                  look_ahead=False, look_ahead_k=5, look_ahead_alpha=0.5,
                  log_steps=0, gradient_clip_val=0.0, accumulate_grad_batches=1,
-                 track_grad_norm=None, split_capsules=True):
+                 track_grad_norm=None, split_capsules=True, nonfinite=None):
         if not isinstance(log_steps, int) or isinstance(log_steps, bool) or log_steps < 0:
             raise ValueError(f"log_steps must be an int >= 0, got {log_steps!r}")
         gradient_clip_val = clip_value(gradient_clip_val)
@@ -154,6 +193,11 @@ class TrainStep:
         if track_grad_norm is not None and optimizer in (None, False):
             raise ValueError("track_grad_norm needs an optimizer: the norms are those of the "
                              "gradient its step consumes")
+        self.nonfinite = nonfinite_value(nonfinite)
+        if self.nonfinite and optimizer in (None, False):
+            raise ValueError("nonfinite needs an optimizer: the guard is part of its step")
+        self._guard_checked = [0]   # skips already reported by "raise" (shared with the
+        #                             remainder step)
         self.accumulate_grad_batches = accumulate_value(accumulate_grad_batches)
         if self.accumulate_grad_batches > 1 and optimizer in (None, False):
             raise ValueError("accumulate_grad_batches needs an optimizer: it steps once a group")
@@ -226,7 +270,8 @@ class TrainStep:
             betas=betas, momentum=momentum, weight_decay=weight_decay,
             look_ahead=look_ahead, look_ahead_k=look_ahead_k,
             look_ahead_alpha=look_ahead_alpha, gradient_clip_val=gradient_clip_val,
-            accumulate_grad_batches=self.accumulate_grad_batches) \
+            accumulate_grad_batches=self.accumulate_grad_batches,
+            nonfinite="skip" if self.nonfinite else None) \
             if optimizer not in (None, False) else None
         # the tracked gradient norms (data_parallel.GradNorms): on the optimiser, whose step
         # launches them -- the remainder step shares both
@@ -652,6 +697,9 @@ class TrainStep:
                 snap["step_state"] = self.opt.step_state.clone()
             if self.opt.slow is not None:
                 snap["slow"] = self.opt.slow.clone()
+            if self.opt.guard_state is not None:
+                snap["guard_state"] = self.opt.guard_state.clone()
+                snap["guard_checked"] = self._guard_checked[0]
         return snap
 
     @torch.no_grad()
@@ -668,6 +716,9 @@ class TrainStep:
                 self.opt.step_state.copy_(snap["step_state"])
             if "slow" in snap:
                 self.opt.slow.copy_(snap["slow"])
+            if "guard_state" in snap and self.opt.guard_state is not None:
+                self.opt.guard_state.copy_(snap["guard_state"])
+                self._guard_checked[0] = snap["guard_checked"]
             if self.opt.lr != snap["lr"]:
                 self.opt.set_lr(snap["lr"])
 
@@ -676,12 +727,15 @@ class TrainStep:
         parameter's index in ``model.parameters()``): loads into the matching
         stock optimiser over the model's parameters
         (data_parallel.optimizer_state_dict; with LookAhead a ``slow_state``
-        keyed the same way)."""
+        keyed the same way).  ``step``: the device count for the optimisers that keep one
+        (skipped steps do not advance it); for plain RMSprop the host's count of optimiser
+        steps, less the guard's ``skipped`` when the guard is on (one more read)."""
         if self.opt is None:
             raise ValueError("this step has no optimiser")
-        return optimizer_state_dict(self.opt, list(self.model.parameters()),
-                                    steps=self.optimizer_steps
-                                    if self.accumulate_grad_batches > 1 else self.steps)
+        steps = self.optimizer_steps if self.accumulate_grad_batches > 1 else self.steps
+        if self.nonfinite and not self.opt.counts_steps:
+            steps -= self.nonfinite_steps()["skipped"]
+        return optimizer_state_dict(self.opt, list(self.model.parameters()), steps=steps)
 
     def load_optimizer_state_dict(self, sd):
         """Load a ``torch.optim``-schema state (``optimizer_state_dict``, or a
@@ -806,17 +860,38 @@ class TrainStep:
     def last_grad_norm(self):
         """The last step's total gradient L2 norm before clipping (the total that Lightning's
         ``track_grad_norm=2`` reports): a device scalar the next step overwrites, no read.  A
-        step that clips returns the clip's own norm; one that only tracks with p = 2 the
+        step that clips returns the clip's own norm, a guarded one (``nonfinite``) the guard's
+        -- NaN or Inf on a skipped step --; one that only tracks with p = 2 the
         tracked total (None before its first optimiser step); None otherwise."""
         opt = self.opt
         if opt is None:
             return None
-        if opt.max_norm:
+        if opt.max_norm or opt.nonfinite:
             return opt.grad_norm
         if opt.track is not None and opt.track.p == 2.0:
             row = opt.track.last()
             return None if row is None else row[-1]
         return None
+
+    # -- the non-finite guard (nonfinite) -----------------------------------------------------
+    def nonfinite_steps(self):
+        """-> {'skipped', 'first', 'last', 'attempts'}: the guard's counters (one host read).
+        attempts: guarded optimiser steps so far; first / last: the attempts values (0-based)
+        of the first and the last skipped one, -1 before any."""
+        if not self.nonfinite:
+            raise ValueError("this step has no non-finite guard (TrainStep(nonfinite=...))")
+        vals = self.opt.guard_state.cpu().tolist()
+        return dict(zip(("skipped", "first", "last", "attempts"), vals))
+
+    def check_nonfinite(self):
+        """``nonfinite="raise"``'s check, on demand (one host read): raises
+        ``NonFiniteGradientError`` when an optimiser step was skipped since the last check.
+        -> the counters otherwise."""
+        counters = self.nonfinite_steps()
+        if counters["skipped"] > self._guard_checked[0]:
+            self._guard_checked[0] = counters["skipped"]
+            raise NonFiniteGradientError(counters)
+        return counters
 
     # -- tracked gradient norms (track_grad_norm) ---------------------------------------------
     @property
@@ -927,7 +1002,9 @@ class TrainStep:
     def end_epoch(self):
         """Per-epoch ExponentialLR step (base_experiment.py:73-76); accumulating, a group
         still pending (``step(image, label)`` batches short of k) first steps the optimiser
-        on what it has: one eager pass over acc alone."""
+        on what it has: one eager pass over acc alone (guarded like any step).  With
+        ``nonfinite="raise"``: then ``check_nonfinite()``, after the learning rate's decay --
+        the one read of the epoch."""
         acc = self._acc_state
         if self.accumulate_grad_batches > 1 and acc["pending"]:
             scale = 1.0 / (self.accumulate_grad_batches * self.world)
@@ -944,3 +1021,5 @@ class TrainStep:
                 self.grad_norms.count += 1
         if self.opt is not None and self.lr_decay_rate:
             self.opt.decay_lr(self.lr_decay_rate)
+        if self.nonfinite == "raise":
+            self.check_nonfinite()
