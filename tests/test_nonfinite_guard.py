@@ -257,6 +257,28 @@ def test_flush_of_a_pending_group_is_guarded():
     assert run.opt.guard_state.tolist() == [1, 1, 1, 2]
 
 
+@pytest.mark.parametrize("clip", [0.0, CLIP])
+@pytest.mark.parametrize("kind", KINDS)
+def test_a_step_no_parameter_takes_counts_and_writes_nothing(kind, clip):
+    """Weight decay and no parameter with a gradient, in the last backward or the group: no
+    range is active, so -- as on the device, which launches no pass then -- the guard counts
+    no attempt, the norm is not written and every buffer keeps its bits; acc is zeroed."""
+    run = Run(kind, False, 2, clip, "skip", wd=1e-2)
+    run.step()
+    before, counted, norm = run.state(), run.opt.guard_state.clone(), run.opt.grad_norm.clone()
+    run.flat.clear_grads()
+    run.flat.gather_grads()                 # no backward: no parameter has a gradient
+    assert run.flat.active_ranges() == []
+    run.opt.acc.fill_(1.0)
+    run.opt.step(grad_scale=0.5)
+    after = run.state()
+    assert float(after.pop("acc").abs().max()) == 0.0
+    before.pop("acc")
+    same(before, after, kind)
+    assert torch.equal(run.opt.guard_state, counted) and counted.tolist() == [0, -1, -1, 1]
+    assert torch.equal(run.opt.grad_norm, norm)
+
+
 def test_a_tracked_row_is_written_for_a_skipped_step():
     from torch_scae_amd.data_parallel import GradNorms
     run = Run("adam", False, 1, 0.0, "skip")

@@ -225,14 +225,68 @@ def all_reduce_gradients(flat: FlatParameters, async_op=False, average=True,
     return dist.all_reduce(g, op=dist.ReduceOp.SUM, async_op=async_op)
 
 
-class _Accumulating:
-    """Gradient accumulation over k batches (Lightning's Trainer(accumulate_grad_batches=k)),
-    shared by the flat optimisers: ``acc``, a buffer laid out like ``flat_grad`` (None for
-    k = 1), collects the gradients of a group's batches (``accumulate``: acc += g, in batch
-    order, fp32); the group's last batch steps through the accumulate forms of the passes,
-    which read g_eff = grad_scale (acc + g) and leave acc = 0.  The caller folds 1/k into
-    ``grad_scale``.  Weight decay applies to the parameters that had a gradient in ANY batch
-    of the group (torch skips only ``grad is None`` parameters)."""
+def _stream(t):
+    """The current stream of ``t``'s device: a launcher's last argument."""
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _riding_units(sum_units, ride):
+    """The column-sum units (``ops._sum_rows_multi``) that ride in the coming launch: at most
+    the last 16, the rest are launched now; None when none ride (``ride`` false: the launch
+    hosts none, all are launched now)."""
+    if not sum_units:
+        return None
+    from . import ops
+    early = sum_units[:-16] if ride else sum_units
+    if early:
+        ops._launch_sum_units(early)
+    return sum_units[len(early):] or None
+
+
+class _FlatOptimizer:
+    """What the flat optimisers share: the learning rate in device memory, so that
+    ``decay_lr`` (the per-epoch ExponentialLR of base_experiment.py:73-76) takes effect inside
+    an already captured HIP graph; ``step``, one driver for every pass and its CPU form
+    (``_device_step`` / ``_cpu_step``; a class supplies ``_device_form`` and
+    ``_cpu_update``); and gradient accumulation over k batches (Lightning's
+    Trainer(accumulate_grad_batches=k)): ``acc``, a buffer laid out like ``flat_grad`` (None
+    for k = 1), collects the gradients of a group's batches (``accumulate``: acc += g, in
+    batch order, fp32); the group's last batch steps through the accumulate forms of the
+    passes, which read g_eff = grad_scale (acc + g) and leave acc = 0.  The caller folds 1/k
+    into ``grad_scale``.  Weight decay applies to the parameters that had a gradient in ANY
+    batch of the group (torch skips only ``grad is None`` parameters)."""
+
+    def _init_shared(self, look_ahead, look_ahead_k, look_ahead_alpha, gradient_clip_val,
+                     accumulate_grad_batches, nonfinite):
+        """The state beside the moments (``flat`` and ``lr`` are set)."""
+        p = self.flat.flat_param
+        self.lr_dev = torch.full((1,), self.lr, device=p.device, dtype=p.dtype)
+        _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
+        _init_clip(self, gradient_clip_val)
+        _init_guard(self, nonfinite)
+        _init_track(self)
+        _init_accumulate(self, accumulate_grad_batches)
+
+    def set_lr(self, lr):
+        self.lr = float(lr)
+        self.lr_dev.fill_(self.lr)
+
+    def decay_lr(self, gamma):
+        """One ExponentialLR step (call once per epoch, gamma = decay_rate)."""
+        self.set_lr(self.lr * gamma)
+
+    @torch.no_grad()
+    def step(self, grad_scale=1.0, sum_units=None, with_acc=True):
+        """``grad_scale`` multiplies the gradient on the fly (1/world after a SUM
+        all-reduce).  ``sum_units``: column-sum units (``ops._sum_rows_multi``) whose outputs
+        are slots of the flat gradient buffer and which have NOT been launched yet: they ride
+        in this step's launch (the ``_sums`` forms: the sum workgroups update the elements
+        they produce), bit for bit the two launches' result.  Accumulating (``acc``, unless
+        ``with_acc`` is False): the gradient is acc + g, and acc is 0 afterwards."""
+        acc = self.acc if with_acc else None
+        device = self.flat.flat_grad.is_cuda
+        sum_units = _track_first(self, grad_scale, sum_units, acc, device)
+        (_device_step if device else _cpu_step)(self, grad_scale, sum_units, acc)
 
     @torch.no_grad()
     def accumulate(self, sum_units=None):
@@ -240,29 +294,20 @@ class _Accumulating:
         sums not launched yet, ride in the launch: scae_grad_accumulate_sums_f32)."""
         if self.acc is None:
             raise ValueError("this optimiser does not accumulate (accumulate_grad_batches=1)")
-        flat = self.flat
-        g = flat.flat_grad
+        g = self.flat.flat_grad
         self._acc_seen = _group_seen(self)
-        if sum_units:
-            from . import ops
-            if not g.is_cuda:
-                ops._launch_sum_units(sum_units)
-                sum_units = None
-            elif len(sum_units) > 16:
-                ops._launch_sum_units(sum_units[:-16])
-                sum_units = sum_units[-16:]
+        sum_units = _riding_units(sum_units, g.is_cuda)
         if not g.is_cuda:
             self.acc.add_(g)
             return
         from . import _lib, ops
         P = ctypes.c_void_p
-        st = P(torch.cuda.current_stream(g.device).cuda_stream)
         if sum_units:
             _lib.call("scae_grad_accumulate_sums_f32", P(self.acc.data_ptr()), P(g.data_ptr()),
-                      g.numel(), ops._sum_job_array(sum_units), len(sum_units), st)
+                      g.numel(), ops._sum_job_array(sum_units), len(sum_units), _stream(g))
         else:
             _lib.call("scae_grad_accumulate_f32", P(self.acc.data_ptr()), P(g.data_ptr()),
-                      g.numel(), st)
+                      g.numel(), _stream(g))
 
     @torch.no_grad()
     def fold(self):
@@ -273,7 +318,7 @@ class _Accumulating:
             from . import _lib
             P = ctypes.c_void_p
             _lib.call("scae_grad_accumulate_f32", P(g.data_ptr()), P(self.acc.data_ptr()),
-                      g.numel(), P(torch.cuda.current_stream(g.device).cuda_stream))
+                      g.numel(), _stream(g))
         else:
             g.add_(self.acc)
         self.acc.zero_()
@@ -319,14 +364,12 @@ def _take_ranges(opt):
     return opt.flat.active_ranges(also=seen)
 
 
-class RMSpropFlat(_Accumulating):
+class RMSpropFlat(_FlatOptimizer):
     """RMSprop with momentum on the flat buffers -- the reference's default
     optimiser (torch.optim.RMSprop(lr, momentum=0.9, eps=1e-2/bs**2,
     weight_decay), base_experiment.py:44-77) as ONE fused pass over the flat
     buffers on a HIP device (a handful of whole-buffer ops on CPU tensors, which
-    only the host-logic tests use).  The learning rate lives in device memory
-    so that ``decay_lr`` (the per-epoch ExponentialLR of :73-76) takes effect
-    inside an already captured HIP graph."""
+    only the host-logic tests use)."""
 
     kind = 2      # scae_flat_opt_step_f32's kind (with LookAhead)
 
@@ -339,161 +382,16 @@ class RMSpropFlat(_Accumulating):
         self.weight_decay = weight_decay
         self.square_avg = torch.zeros_like(flat.flat_param)
         self.buf = torch.zeros_like(flat.flat_param)
-        self.lr_dev = torch.full((1,), lr, device=flat.flat_param.device,
-                                 dtype=flat.flat_param.dtype)
-        _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
-        _init_clip(self, gradient_clip_val)
-        _init_guard(self, nonfinite)
-        _init_track(self)
-        _init_accumulate(self, accumulate_grad_batches)
+        self._init_shared(look_ahead, look_ahead_k, look_ahead_alpha, gradient_clip_val,
+                          accumulate_grad_batches, nonfinite)
 
-    def set_lr(self, lr):
-        self.lr = float(lr)
-        self.lr_dev.fill_(self.lr)
-
-    def decay_lr(self, gamma):
-        """One ExponentialLR step (call once per epoch, gamma = decay_rate)."""
-        self.set_lr(self.lr * gamma)
-
-    @torch.no_grad()
-    def step(self, grad_scale=1.0, sum_units=None, with_acc=True):
-        """``grad_scale`` multiplies the gradient on the fly (1/world after a
-        SUM all-reduce).  ``sum_units``: column-sum units (``ops._sum_rows_multi``)
-        whose outputs are slots of the flat gradient buffer and which have NOT
-        been launched yet: they ride in this step's launch
-        (``scae_rmsprop_sums_step_f32``: the sum workgroups update the elements
-        they produce), bit for bit the two launches' result.  Accumulating
-        (``acc``, unless ``with_acc`` is False): the gradient is acc + g, and acc is 0
-        afterwards."""
-        acc = self.acc if with_acc else None
-        sum_units = _track_first(self, grad_scale, sum_units, acc)
-        if self.look_ahead_k:     # (the fused form that counts steps)
-            _fused_step(self, self.buf, self.square_avg,
-                        (self.momentum, self.alpha), grad_scale, sum_units,
-                        self._cpu_update, acc)
-            return
-        if self.max_norm or self.nonfinite:
-            self._clipped_step(grad_scale, sum_units, acc)
-            return
-        g = self.flat.flat_grad
-        if sum_units:
-            from . import ops
-            if not g.is_cuda or self.weight_decay != 0:
-                ops._launch_sum_units(sum_units)      # (the plain forms)
-                sum_units = None
-            elif len(sum_units) > 16:
-                ops._launch_sum_units(sum_units[:-16])
-                sum_units = sum_units[-16:]
-        # parameters without a gradient are left alone, like torch.optim does;
-        # without weight decay a zero gradient already is a no-op
-        ranges = _take_ranges(self)
-        if g.is_cuda and acc is not None:
-            self._acc_step(g, acc, ranges, grad_scale, sum_units)
-            return
-        if g.is_cuda:      # one fused pass over the four flat buffers
-            from . import _lib
-            P = ctypes.c_void_p
-            st = P(torch.cuda.current_stream(g.device).cuda_stream)
-            if sum_units:
-                from . import ops
-                arr = ops._sum_job_array(sum_units)
-                _lib.call("scae_rmsprop_sums_step_f32", P(self.flat.flat_param.data_ptr()),
-                          P(g.data_ptr()), P(self.square_avg.data_ptr()),
-                          P(self.buf.data_ptr()), g.numel(), self.lr,
-                          P(self.lr_dev.data_ptr()), self.alpha, self.eps, self.momentum,
-                          float(grad_scale), arr, len(sum_units), st)
-                return
-            for off, n in ranges:
-                ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
-                _lib.call("scae_rmsprop_step_f32", ptr(self.flat.flat_param),
-                          ptr(g), ptr(self.square_avg), ptr(self.buf), n,
-                          self.lr, P(self.lr_dev.data_ptr()), self.alpha,
-                          self.eps, self.momentum, self.weight_decay,
-                          float(grad_scale), st)
-            return
-        if acc is not None:
-            g = acc + g
-            acc.zero_()
-        if grad_scale != 1.0:
-            g = g * grad_scale
-        if self.weight_decay != 0:
-            keep = torch.zeros_like(g, dtype=torch.bool)
-            for off, n in ranges:
-                keep[off:off + n] = True
-            saved = (self.flat.flat_param.clone(), self.square_avg.clone(),
-                     self.buf.clone())
-            g = g.add(self.flat.flat_param, alpha=self.weight_decay)
-        self.square_avg.mul_(self.alpha).addcmul_(g, g, value=1 - self.alpha)
-        avg = self.square_avg.sqrt().add_(self.eps)
-        if self.momentum > 0:
-            self.buf.mul_(self.momentum).addcdiv_(g, avg)
-            self.flat.flat_param.add_(self.buf, alpha=-self.lr)
-        else:
-            self.flat.flat_param.addcdiv_(g, avg, value=-self.lr)
-        if self.weight_decay != 0:
-            for cur, old in zip((self.flat.flat_param, self.square_avg,
-                                 self.buf), saved):
-                cur.copy_(torch.where(keep, cur, old))
-
-    def _acc_step(self, g, acc, ranges, grad_scale, sum_units):
-        """The accumulate forms of the two plain launches above (g = acc + g, acc -> 0)."""
-        from . import _lib
-        P = ctypes.c_void_p
-        st = P(torch.cuda.current_stream(g.device).cuda_stream)
-        if sum_units:
-            from . import ops
-            _lib.call("scae_rmsprop_acc_sums_step_f32", P(self.flat.flat_param.data_ptr()),
-                      P(g.data_ptr()), P(acc.data_ptr()), P(self.square_avg.data_ptr()),
-                      P(self.buf.data_ptr()), g.numel(), self.lr, P(self.lr_dev.data_ptr()),
-                      self.alpha, self.eps, self.momentum, float(grad_scale),
-                      ops._sum_job_array(sum_units), len(sum_units), st)
-            return
-        for off, n in ranges:
-            ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
-            _lib.call("scae_rmsprop_acc_step_f32", ptr(self.flat.flat_param), ptr(g), ptr(acc),
-                      ptr(self.square_avg), ptr(self.buf), n, self.lr,
-                      P(self.lr_dev.data_ptr()), self.alpha, self.eps, self.momentum,
-                      self.weight_decay, float(grad_scale), st)
-
-    def _clipped_step(self, grad_scale, sum_units, acc=None):
-        """``step`` with clipping by global norm: the norm launch (``sum_units`` ride in
-        it), then scae_rmsprop_clip_step_f32 over each active range; on CPU tensors
-        ``_cpu_update`` on the clipped gradient.  ``acc``: of acc + g (the accumulate
-        forms), acc -> 0.  On CPU tensors also the guarded step (``_init_guard``), with or
-        without clipping."""
-        flat = self.flat
-        g = flat.flat_grad
-        seen = _group_seen(self)
-        ranges = _take_ranges(self)
-        if not g.is_cuda:
-            if sum_units:
-                from . import ops
-                ops._launch_sum_units(sum_units)
-            if acc is not None:
-                g = acc + g
-                acc.zero_()
-            g = _cpu_effective_grad(self, g, grad_scale, seen)
-            if g is None:      # (the guard: nothing is written)
-                return
-            saved = _keep_inactive(self, ranges, [flat.flat_param, self.square_avg, self.buf])
-            self._cpu_update(g, None)
-            _restore_inactive(saved)
-            return
-        from . import _lib
-        P = ctypes.c_void_p
-        st = P(torch.cuda.current_stream(g.device).cuda_stream)
-        n_partials = _launch_norm(self, g, sum_units, st, acc)
-        _track_after_norm(self, grad_scale, acc)
-        for i, (off, n) in enumerate(ranges):
-            ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
-            name, a = ("scae_rmsprop_clip_step_f32", ()) if acc is None else \
-                ("scae_rmsprop_acc_clip_step_f32", (ptr(acc),))
-            _lib.call(name, ptr(flat.flat_param), ptr(g), *a,
-                      ptr(self.square_avg), ptr(self.buf), n, self.lr,
-                      P(self.lr_dev.data_ptr()), self.alpha, self.eps, self.momentum,
-                      self.weight_decay, float(grad_scale), P(self.grad_sq.data_ptr()),
-                      n_partials, self.max_norm,
-                      P(self.grad_norm.data_ptr()) if i == 0 else None, st)
+    def _device_form(self):
+        if self.look_ahead_k:     # (the fused family: it counts the steps)
+            return _flat_opt_form(self, self.buf, self.square_avg,
+                                  (self.momentum, self.alpha))
+        return ("scae_rmsprop", (self.square_avg, self.buf),
+                (self.lr, ctypes.c_void_p(self.lr_dev.data_ptr()), self.alpha, self.eps,
+                 self.momentum))
 
     def _cpu_update(self, g, t):
         """The CPU form of the update (torch.optim.RMSprop's arithmetic) on
@@ -798,8 +696,7 @@ class GradNorms:
                   _lib.NORM_INF if math.isinf(p) else int(p), float(scale),
                   P(partials.data_ptr()), P(ring.data_ptr()),
                   None if cursor is None else P(cursor.data_ptr()),
-                  self.capacity if into is None else 1,
-                  P(torch.cuda.current_stream(x.device).cuda_stream))
+                  self.capacity if into is None else 1, _stream(x))
 
     def last(self):
         """The newest row (a device view, no read); None before the first one."""
@@ -812,24 +709,19 @@ def _init_track(opt):
     opt.track = None
 
 
-def _track_first(opt, grad_scale, sum_units, acc):
+def _track_first(opt, grad_scale, sum_units, acc, device):
     """A tracking optimiser's step, before its pass: the norms of the gradient the pass
     consumes.  The flat gradient is complete only once the step's last column sums
     (``sum_units``) have run, so they are launched on their own here -- the same bits as riding
     in the pass -- and the norms after them; -> the units still to launch.  A clipping step on
-    the device keeps them: they ride in its norm launch, and the norms follow that
-    (``_track_after_norm``)."""
+    the device (``device``: the step takes ``_device_step``) keeps them: they ride in its norm
+    launch, and the norms follow that (``_track_after_norm``)."""
     trk = opt.track
-    if trk is None:
+    if trk is None or (device and opt.max_norm):
         return sum_units
-    g = opt.flat.flat_grad
-    if g.is_cuda and opt.max_norm:
-        return sum_units
-    if sum_units:
-        from . import ops
-        ops._launch_sum_units(sum_units)
+    _riding_units(sum_units, False)
     trk.build(_group_seen(opt))
-    trk.launch(g, acc, grad_scale)
+    trk.launch(opt.flat.flat_grad, acc, grad_scale)
     return None
 
 
@@ -843,32 +735,19 @@ def _track_after_norm(opt, grad_scale, acc):
 
 
 def _launch_norm(opt, g, sum_units, st, acc=None):
-    """The gradient's fp64 partial sums of squares into ``opt.grad_sq`` (the last 16 column-sum
-    units ride in the launch, the rest are launched first); -> the partial count.  ``acc``: of
-    acc + g (the accumulate forms)."""
-    from . import _lib
+    """The gradient's fp64 partial sums of squares into ``opt.grad_sq`` (column-sum units ride
+    in the launch: ``_riding_units``); -> the partial count.  ``acc``: of acc + g (the
+    accumulate forms, which take acc right after grad)."""
+    from . import _lib, ops
     P = ctypes.c_void_p
     cnt = ctypes.c_int(0)
+    sum_units = _riding_units(sum_units, True)
+    args = [P(g.data_ptr())] + ([] if acc is None else [P(acc.data_ptr())]) + \
+        [g.numel(), P(opt.grad_sq.data_ptr()), opt.grad_sq.numel(), ctypes.byref(cnt)]
     if sum_units:
-        from . import ops
-        if len(sum_units) > 16:
-            ops._launch_sum_units(sum_units[:-16])
-            sum_units = sum_units[-16:]
-        if acc is not None:
-            _lib.call("scae_grad_sq_acc_partials_sums_f32", P(g.data_ptr()), P(acc.data_ptr()),
-                      g.numel(), P(opt.grad_sq.data_ptr()), opt.grad_sq.numel(),
-                      ctypes.byref(cnt), ops._sum_job_array(sum_units), len(sum_units), st)
-            return cnt.value
-        _lib.call("scae_grad_sq_partials_sums_f32", P(g.data_ptr()), g.numel(),
-                  P(opt.grad_sq.data_ptr()), opt.grad_sq.numel(), ctypes.byref(cnt),
-                  ops._sum_job_array(sum_units), len(sum_units), st)
-    elif acc is not None:
-        _lib.call("scae_grad_sq_acc_partials_f32", P(g.data_ptr()), P(acc.data_ptr()),
-                  g.numel(), P(opt.grad_sq.data_ptr()), opt.grad_sq.numel(), ctypes.byref(cnt),
-                  st)
-    else:
-        _lib.call("scae_grad_sq_partials_f32", P(g.data_ptr()), g.numel(),
-                  P(opt.grad_sq.data_ptr()), opt.grad_sq.numel(), ctypes.byref(cnt), st)
+        args += [ops._sum_job_array(sum_units), len(sum_units)]
+    _lib.call("scae_grad_sq%s_partials%s_f32" % ("" if acc is None else "_acc",
+                                                 "_sums" if sum_units else ""), *args, st)
     return cnt.value
 
 
@@ -911,75 +790,82 @@ def _restore_inactive(saved):
         cur.copy_(torch.where(keep, cur, old))
 
 
-def _split_sums(opt, g, sum_units):
-    """The column-sum units that may ride in the optimiser's launch (the rest
-    launched now); None when none ride."""
-    if not sum_units:
-        return None
-    from . import ops
-    if not g.is_cuda or opt.weight_decay != 0:
-        ops._launch_sum_units(sum_units)      # (the plain forms)
-        return None
-    if len(sum_units) > 16:
-        ops._launch_sum_units(sum_units[:-16])
-        return sum_units[-16:]
-    return sum_units
+def _flat_opt_form(opt, m, v, betas):
+    """``_device_form`` of the scae_flat_opt family (Adam, RAdam, RMSprop with LookAhead): its
+    buffers after grad -- both moments and LookAhead's slow weights (without LookAhead the
+    parameters stand in) -- and its fixed argument run."""
+    P = ctypes.c_void_p
+    slow = opt.slow if opt.slow is not None else opt.flat.flat_param
+    return ("scae_flat_opt", (m, v, slow),
+            (P(opt.lr_dev.data_ptr()), P(opt.step_state.data_ptr()), opt.kind,
+             float(betas[0]), float(betas[1]), float(opt.eps)))
 
 
-@torch.no_grad()
-def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update, acc=None):
-    """One step of ``opt`` through scae_flat_opt_step_f32 / scae_flat_opt_sums_step_f32
-    (HIP device) or ``cpu_update(g, t)`` + LookAhead in whole-buffer torch ops (CPU
-    tensors: the host-logic tests).  Parameters without a gradient are left alone,
-    like torch.optim does; without weight decay a zero gradient already is a no-op
-    (zero moments stay zero, LookAhead's slow copy of such a parameter equals it).
-    ``acc``: the accumulate forms (scae_flat_opt_acc_*: the gradient is acc + g, acc -> 0).
-    On CPU tensors the guard (``_init_guard``) decides first."""
+def _device_step(opt, grad_scale, sum_units, acc):
+    """One optimiser step on a HIP device, through scae_{family}[_acc][_sums|_clip]_step_f32
+    (``opt._device_form()`` -> family, buffers, fixed arguments).  Clipping: the norm launch
+    (the column sums ride in it), the tracked norms, then the ``_clip`` form over each active
+    range.  Else the column sums ride in the pass when there is no weight decay (the ``_sums``
+    form, over the whole buffer: the sum workgroups update the elements they produce), and
+    otherwise the plain form runs over each active range: parameters without a gradient are
+    left alone, like torch.optim does; without weight decay a zero gradient already is a
+    no-op (zero moments stay zero, LookAhead's slow copy of such a parameter equals it).
+    ``acc``: the accumulate forms (the gradient is acc + g, acc -> 0).  Reads the tensors'
+    addresses and sizes only."""
+    from . import _lib, ops
+    P = ctypes.c_void_p
     flat = opt.flat
     g = flat.flat_grad
-    clip = opt.max_norm and g.is_cuda
-    sum_units = _split_sums(opt, g, sum_units) if not clip else sum_units
+    st = _stream(g)
+    family, bufs, fixed = opt._device_form()
+    counts = family == "scae_flat_opt"     # (this family counts steps and syncs LookAhead)
+    clip = bool(opt.max_norm)
+    if clip:
+        n_partials = _launch_norm(opt, g, sum_units, st, acc)
+        _track_after_norm(opt, grad_scale, acc)
+        sum_units = None
+    else:
+        sum_units = _riding_units(sum_units, opt.weight_decay == 0)
+    ranges = _take_ranges(opt)
+    if sum_units:
+        ranges = [(0, g.numel())]
+    name = "%s%s%s_step_f32" % (family, "" if acc is None else "_acc",
+                                "_clip" if clip else "_sums" if sum_units else "")
+    for i, (off, n) in enumerate(ranges):
+        ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
+        # the accumulate forms take acc right after grad
+        args = [ptr(flat.flat_param), ptr(g)] + ([] if acc is None else [ptr(acc)]) + \
+            [ptr(b) for b in bufs] + [n, *fixed]
+        if not sum_units:
+            args.append(float(opt.weight_decay))
+        args.append(float(grad_scale))
+        if counts:
+            args += [opt.look_ahead_k, opt.look_ahead_alpha]
+            if not sum_units:
+                # (one launch per step advances the count: the last, so that every range
+                # reads the same t)
+                args.append(int(i == len(ranges) - 1))
+        if clip:
+            args += [P(opt.grad_sq.data_ptr()), n_partials, opt.max_norm,
+                     P(opt.grad_norm.data_ptr()) if i == 0 else None]
+        elif sum_units:
+            args += [ops._sum_job_array(sum_units), len(sum_units)]
+        _lib.call(name, *args, st)
+
+
+def _cpu_step(opt, grad_scale, sum_units, acc):
+    """One optimiser step on CPU tensors (the host-logic tests), in whole-buffer torch ops:
+    the guard (``_init_guard``) decides first, then the clip, ``opt._cpu_update(g, t)`` and,
+    where the optimiser counts steps, LookAhead's sync; parameters without a gradient are
+    put back afterwards.  When no parameter takes the step (weight decay, no gradient at
+    all) nothing is counted or written beyond acc -> 0, as on the device, which launches no
+    pass then."""
+    _riding_units(sum_units, False)
+    flat = opt.flat
+    g = flat.flat_grad
     seen = _group_seen(opt)
     ranges = _take_ranges(opt)
-    # the accumulate forms take acc right after grad
-    A = "" if acc is None else "_acc"
-    ac = lambda off: () if acc is None else (ctypes.c_void_p(acc.data_ptr() + 4 * off),)  # noqa: E731
-    if g.is_cuda:
-        from . import _lib
-        P = ctypes.c_void_p
-        st = P(torch.cuda.current_stream(g.device).cuda_stream)
-        slow = opt.slow if opt.slow is not None else flat.flat_param
-        common = (P(opt.lr_dev.data_ptr()), P(opt.step_state.data_ptr()),
-                  opt.kind, float(betas[0]), float(betas[1]), float(opt.eps))
-        if clip:     # the norm launch (the column sums ride in it), then the clip forms
-            n_partials = _launch_norm(opt, g, sum_units, st, acc)
-            _track_after_norm(opt, grad_scale, acc)
-            for i, (off, n) in enumerate(ranges):
-                ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
-                _lib.call(f"scae_flat_opt{A}_clip_step_f32", ptr(flat.flat_param), ptr(g),
-                          *ac(off), ptr(m), ptr(v), ptr(slow), n, *common, float(opt.weight_decay),
-                          float(grad_scale), opt.look_ahead_k, opt.look_ahead_alpha,
-                          int(i == len(ranges) - 1), P(opt.grad_sq.data_ptr()), n_partials,
-                          opt.max_norm, P(opt.grad_norm.data_ptr()) if i == 0 else None, st)
-            return
-        if sum_units:
-            from . import ops
-            arr = ops._sum_job_array(sum_units)
-            _lib.call(f"scae_flat_opt{A}_sums_step_f32", P(flat.flat_param.data_ptr()),
-                      P(g.data_ptr()), *ac(0), P(m.data_ptr()), P(v.data_ptr()),
-                      P(slow.data_ptr()), g.numel(), *common, float(grad_scale),
-                      opt.look_ahead_k, opt.look_ahead_alpha, arr, len(sum_units), st)
-            return
-        for i, (off, n) in enumerate(ranges):
-            ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
-            # (one launch per step advances the count: the last, so that every
-            # range reads the same t)
-            _lib.call(f"scae_flat_opt{A}_step_f32", ptr(flat.flat_param), ptr(g), *ac(off),
-                      ptr(m), ptr(v), ptr(slow), n, *common, float(opt.weight_decay),
-                      float(grad_scale), opt.look_ahead_k, opt.look_ahead_alpha,
-                      int(i == len(ranges) - 1), st)
-        return
-    if acc is not None:     # (acc -> 0 even when no parameter takes the step)
+    if acc is not None:
         g = acc + g
         acc.zero_()
     if not ranges:
@@ -987,14 +873,10 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update, acc=None):
     g = _cpu_effective_grad(opt, g, grad_scale, seen)
     if g is None:      # (the guard: nothing is written, the step count stays)
         return
-    bufs = [flat.flat_param, m, v] + ([opt.slow] if opt.slow is not None else [])
-    if opt.weight_decay != 0:
-        keep = torch.zeros_like(g, dtype=torch.bool)
-        for off, n in ranges:
-            keep[off:off + n] = True
-        saved = [b.clone() for b in bufs]
-    t = int(opt.step_state[0]) + 1
-    cpu_update(g, t)
+    saved = _keep_inactive(opt, ranges, [flat.flat_param] + [b for _, b in opt.state_buffers()]
+                           + ([opt.slow] if opt.slow is not None else []))
+    t = int(opt.step_state[0]) + 1 if opt.counts_steps else None
+    opt._cpu_update(g, t)
     k = opt.look_ahead_k
     if k and t % k == 0:        # optimizers.py:118-128, 136-142
         p = flat.flat_param
@@ -1004,17 +886,14 @@ def _fused_step(opt, m, v, betas, grad_scale, sum_units, cpu_update, acc=None):
         else:
             opt.slow.copy_(p)
         opt.step_state[1] = 1
-    if opt.weight_decay != 0:
-        for cur, old in zip(bufs, saved):
-            cur.copy_(torch.where(keep, cur, old))
-    opt.step_state[0] = t
+    if t is not None:
+        opt.step_state[0] = t
+    _restore_inactive(saved)
 
 
-class _FlatAdamBase(_Accumulating):
-    """What AdamFlat and RAdamFlat share: the surface of RMSpropFlat
-    (``step(grad_scale, sum_units)``, ``set_lr``, ``decay_lr``, ``lr``,
-    ``lr_dev``), two moment buffers, the step count in device memory and
-    optionally LookAhead(k, alpha) fused into the same pass."""
+class _FlatAdamBase(_FlatOptimizer):
+    """What AdamFlat and RAdamFlat share: two moment buffers, the step count in device
+    memory and optionally LookAhead(k, alpha) fused into the same pass."""
 
     kind = None
     counts_steps = True
@@ -1031,30 +910,11 @@ class _FlatAdamBase(_Accumulating):
         self.weight_decay = float(weight_decay)
         self.exp_avg = torch.zeros_like(flat.flat_param)
         self.exp_avg_sq = torch.zeros_like(flat.flat_param)
-        self.lr_dev = torch.full((1,), self.lr, device=flat.flat_param.device,
-                                 dtype=flat.flat_param.dtype)
-        _init_look_ahead(self, look_ahead, look_ahead_k, look_ahead_alpha)
-        _init_clip(self, gradient_clip_val)
-        _init_guard(self, nonfinite)
-        _init_track(self)
-        _init_accumulate(self, accumulate_grad_batches)
+        self._init_shared(look_ahead, look_ahead_k, look_ahead_alpha, gradient_clip_val,
+                          accumulate_grad_batches, nonfinite)
 
-    def set_lr(self, lr):
-        self.lr = float(lr)
-        self.lr_dev.fill_(self.lr)
-
-    def decay_lr(self, gamma):
-        """One ExponentialLR step (call once per epoch, gamma = decay_rate)."""
-        self.set_lr(self.lr * gamma)
-
-    def step(self, grad_scale=1.0, sum_units=None, with_acc=True):
-        """As ``RMSpropFlat.step``: ``grad_scale`` multiplies the gradient on
-        the fly, ``sum_units`` ride in the launch (scae_flat_opt_sums_step_f32);
-        accumulating, the gradient is acc + g and acc is 0 afterwards."""
-        acc = self.acc if with_acc else None
-        sum_units = _track_first(self, grad_scale, sum_units, acc)
-        _fused_step(self, self.exp_avg, self.exp_avg_sq, self.betas, grad_scale,
-                    sum_units, self._cpu_update, acc)
+    def _device_form(self):
+        return _flat_opt_form(self, self.exp_avg, self.exp_avg_sq, self.betas)
 
     def state_buffers(self):
         """(torch.optim's state key, flat buffer) pairs."""
