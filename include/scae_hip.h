@@ -905,6 +905,59 @@ int scae_flat_opt_acc_clip_step_f32(float *param, const float *grad, float *acc,
                                     int advance, const double *partials, int n_partials,
                                     float max_norm, float *norm_out, void *stream);
 
+/* The non-finite guard -- the form of Lightning's Trainer(terminate_on_nan) that skips: an
+ * optimiser step whose gradient (acc + grad in the accumulate forms) holds a NaN or +-Inf
+ * element writes nothing.  The guarded forms below are the clip forms above behind one
+ * decision, with the same arguments plus `guard_state` after `norm_out`.
+ *   The rule: every workgroup reduces the norm launch's `partials` in one fixed order, as the
+ *   clip forms do, and the step is skipped iff that fp64 sum is not finite.  The norm launch
+ *   squares in fp64, so the sum is NaN or +Inf exactly when an element is NaN or +-Inf: finite
+ *   fp32 gradients cannot overflow it (the fp32 norm can, and does not decide).  The sum has
+ *   the same bits in every workgroup of every launch of the step (one launch per active
+ *   range, all on the same partials), so all of them decide alike, with no synchronisation.
+ *   A skipped launch, per buffer:
+ *     param, both moments / square_avg, buf, slow    no store
+ *     step_state (scae_flat_opt)                     no store, no arrival: [0], [1] keep their
+ *                                                    values, every counter stays 0
+ *     acc (the accumulate forms)                     0 over the launch's n elements
+ *     norm_out                                       written as on a taken step: NaN or +Inf
+ *   A step that is taken equals the clip form's bit for bit.
+ *   max_norm = +inf: the guard without clipping.  The coefficient is then the constant 1 (not
+ *   max_norm / (total + 1e-6), which is NaN once a finite gradient's fp32 norm overflows),
+ *   and a step that is taken equals the plain pass's (the plain accumulate pass's) bit for bit.
+ *   guard_state (device int64[4], 8-byte aligned, may be NULL): {skipped, first, last,
+ *   attempts}, initialised by the caller to {0, -1, -1, 0}.  Thread 0 of the first workgroup
+ *   of a launch that is handed the pointer counts: t = attempts; on a skip skipped += 1,
+ *   first = t if first < 0, last = t; always attempts = t + 1.  Plain loads and stores: hand
+ *   the pointer (and norm_out) to ONE launch of a step, its first range's; the launches of
+ *   the other ranges take NULL and decide without counting. */
+int scae_rmsprop_guard_step_f32(float *param, const float *grad, float *square_avg, float *buf,
+                                int64_t n, float lr, const float *lr_dev, float alpha, float eps,
+                                float momentum, float weight_decay, float grad_scale,
+                                const double *partials, int n_partials, float max_norm,
+                                float *norm_out, int64_t *guard_state, void *stream);
+int scae_rmsprop_acc_guard_step_f32(float *param, const float *grad, float *acc,
+                                    float *square_avg, float *buf, int64_t n, float lr,
+                                    const float *lr_dev, float alpha, float eps, float momentum,
+                                    float weight_decay, float grad_scale, const double *partials,
+                                    int n_partials, float max_norm, float *norm_out,
+                                    int64_t *guard_state, void *stream);
+int scae_flat_opt_guard_step_f32(float *param, const float *grad, float *exp_avg,
+                                 float *exp_avg_sq, float *slow, int64_t n, const float *lr_dev,
+                                 int32_t *step_state, int kind, double beta1, double beta2,
+                                 float eps, float weight_decay, float grad_scale,
+                                 int look_ahead_k, float look_ahead_alpha, int advance,
+                                 const double *partials, int n_partials, float max_norm,
+                                 float *norm_out, int64_t *guard_state, void *stream);
+int scae_flat_opt_acc_guard_step_f32(float *param, const float *grad, float *acc,
+                                     float *exp_avg, float *exp_avg_sq, float *slow, int64_t n,
+                                     const float *lr_dev, int32_t *step_state, int kind,
+                                     double beta1, double beta2, float eps, float weight_decay,
+                                     float grad_scale, int look_ahead_k, float look_ahead_alpha,
+                                     int advance, const double *partials, int n_partials,
+                                     float max_norm, float *norm_out, int64_t *guard_state,
+                                     void *stream);
+
 /* Per-parameter gradient norms -- Lightning's Trainer(track_grad_norm=p): one p-norm per
  * segment of a flat buffer, and their total, as one row of a device ring.
  *   A segment is a run of elements [offset, offset + length) of src[0, n), length >= 1;

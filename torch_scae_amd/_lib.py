@@ -346,6 +346,17 @@ SIGNATURES = {
     "scae_flat_opt_acc_clip_step_f32": [P, P, P, P, P, P, c_int64, P, P, c_int, c_double,
                                         c_double, c_float, c_float, c_float, c_int, c_float,
                                         c_int, P, c_int, c_float, P, P],
+    # the non-finite guard: the clip forms' arguments, then guard_state after norm_out
+    "scae_rmsprop_guard_step_f32": [P, P, P, P, c_int64, c_float, P, c_float, c_float, c_float,
+                                    c_float, c_float, P, c_int, c_float, P, P, P],
+    "scae_rmsprop_acc_guard_step_f32": [P, P, P, P, P, c_int64, c_float, P, c_float, c_float,
+                                        c_float, c_float, c_float, P, c_int, c_float, P, P, P],
+    "scae_flat_opt_guard_step_f32": [P, P, P, P, P, c_int64, P, P, c_int, c_double, c_double,
+                                     c_float, c_float, c_float, c_int, c_float, c_int, P, c_int,
+                                     c_float, P, P, P],
+    "scae_flat_opt_acc_guard_step_f32": [P, P, P, P, P, P, c_int64, P, P, c_int, c_double,
+                                         c_double, c_float, c_float, c_float, c_int, c_float,
+                                         c_int, P, c_int, c_float, P, P, P],
     # per-segment norms of a flat buffer into a device ring (grad_norms.hip)
     "scae_segment_norms_chunk": [],
     "scae_segment_norms_f32": [P, P, c_int64, P, c_int, P, c_int, P, c_int, c_int, c_float,

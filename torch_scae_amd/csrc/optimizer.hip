@@ -11,6 +11,9 @@
 // the norm launch's partials (grad_clip_dev.h) after grad_scale, before the weight decay.
 // The accumulate forms (scae_rmsprop_acc_*: gradient accumulation, grad_accumulate.hip) read
 // g = acc + grad in place of grad and leave acc = 0 behind.
+// The guarded forms (scae_rmsprop[_acc]_guard_step_f32: the non-finite guard) are the clip
+// forms behind a decision on the partials' fp64 sum: not finite, and the launch stores nothing
+// (the accumulate form: acc = 0); finite, and it is the clip form bit for bit.
 #include "grad_clip_dev.h"
 
 namespace {
@@ -99,6 +102,32 @@ __global__ __launch_bounds__(256) void rmsprop_acc_kernel(OptArgs a, int head, f
 __global__ __launch_bounds__(256) void rmsprop_acc_clip_kernel(OptArgs a, int head,
                                                                scae_clip::Clip clip, float *acc) {
   rmsprop_pass<true, true>(a, head, scae_clip::clip_coef(clip, a.grad_scale), acc);
+}
+// the guarded forms of the two clip forms (the non-finite guard, grad_clip_dev.h): a workgroup
+// that finds the partials' fp64 sum not finite returns before the pass -- nothing is stored to
+// p, v or buf; the accumulate form leaves acc = 0 over its elements (the group is dropped)
+template <bool ACC>
+__device__ __forceinline__ void rmsprop_guard(const OptArgs &a, int head,
+                                              const scae_clip::Clip &clip,
+                                              const scae_clip::Guard &guard, float *acc) {
+  bool skip;
+  const float coef = scae_clip::guard_coef(clip, guard, a.grad_scale, skip);
+  if (skip) {   // workgroup-uniform, after the sum's barrier
+    if (ACC) scae_clip::zero_acc(acc, a.n, head);
+    return;
+  }
+  rmsprop_pass<true, ACC>(a, head, coef, acc);
+}
+__global__ __launch_bounds__(256) void rmsprop_guard_kernel(OptArgs a, int head,
+                                                            scae_clip::Clip clip,
+                                                            scae_clip::Guard guard) {
+  rmsprop_guard<false>(a, head, clip, guard, nullptr);
+}
+__global__ __launch_bounds__(256) void rmsprop_acc_guard_kernel(OptArgs a, int head,
+                                                                scae_clip::Clip clip,
+                                                                scae_clip::Guard guard,
+                                                                float *acc) {
+  rmsprop_guard<true>(a, head, clip, guard, acc);
 }
 // The step's LAST column sums and the optimiser in one launch.  A training step's backward
 // ends in one scae_sum_rows_multi launch whose outputs are slots of the flat gradient buffer
@@ -247,19 +276,21 @@ extern "C" int scae_rmsprop_step_f32(float *param, const float *grad, float *squ
   return scae_launch_status();
 }
 
-// scae_rmsprop_step_f32 with g scaled by clip_grad_norm_'s coefficient (grad_clip_dev.h)
-extern "C" int scae_rmsprop_clip_step_f32(float *param, const float *grad, float *square_avg,
-                                          float *buf, int64_t n, float lr, const float *lr_dev,
-                                          float alpha, float eps, float momentum,
-                                          float weight_decay, float grad_scale,
-                                          const double *partials, int n_partials, float max_norm,
-                                          float *norm_out, void *stream) {
+// scae_rmsprop_clip_step_f32 and scae_rmsprop_guard_step_f32 behind one set of checks and one
+// grid; GUARD: the guarded kernel, which also takes guard_state
+namespace {
+template <bool GUARD>
+int rmsprop_clip_launch(float *param, const float *grad, float *square_avg, float *buf, int64_t n,
+                        float lr, const float *lr_dev, float alpha, float eps, float momentum,
+                        float weight_decay, float grad_scale, const double *partials,
+                        int n_partials, float max_norm, float *norm_out, int64_t *guard_state,
+                        void *stream) {
   SCAE_REQUIRE(param && grad && square_avg && n > 0 && partials && n_partials > 0 &&
                n_partials <= SCAE_GRAD_SQ_MAX_PARTIALS && max_norm > 0.f);
   if (momentum > 0.f && !buf) return SCAE_ERR_BAD_ARG;
   const size_t phase = (size_t)param & 15;
   if ((phase & 3) || ((size_t)grad & 15) != phase || ((size_t)square_avg & 15) != phase ||
-      (momentum > 0.f && ((size_t)buf & 15) != phase))
+      (momentum > 0.f && ((size_t)buf & 15) != phase) || ((size_t)guard_state & 7))
     return SCAE_ERR_BAD_ARG;
   int head = (int)((16 - phase) & 15) / 4;
   if (head > n) head = (int)n;
@@ -267,9 +298,40 @@ extern "C" int scae_rmsprop_clip_step_f32(float *param, const float *grad, float
             eps, momentum, weight_decay, grad_scale};
   long blocks = (n / 4 + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-  scae::launch(rmsprop_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-               a, head, scae_clip::Clip{partials, n_partials, max_norm, norm_out});
+  const scae_clip::Clip clip{partials, n_partials, max_norm, norm_out};
+  if constexpr (GUARD)
+    scae::launch(rmsprop_guard_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                 a, head, clip, scae_clip::Guard{(long long *)guard_state});
+  else
+    scae::launch(rmsprop_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                 a, head, clip);
   return scae_launch_status();
+}
+}  // namespace
+
+// scae_rmsprop_step_f32 with g scaled by clip_grad_norm_'s coefficient (grad_clip_dev.h)
+extern "C" int scae_rmsprop_clip_step_f32(float *param, const float *grad, float *square_avg,
+                                          float *buf, int64_t n, float lr, const float *lr_dev,
+                                          float alpha, float eps, float momentum,
+                                          float weight_decay, float grad_scale,
+                                          const double *partials, int n_partials, float max_norm,
+                                          float *norm_out, void *stream) {
+  return rmsprop_clip_launch<false>(param, grad, square_avg, buf, n, lr, lr_dev, alpha, eps,
+                                    momentum, weight_decay, grad_scale, partials, n_partials,
+                                    max_norm, norm_out, nullptr, stream);
+}
+
+// scae_rmsprop_clip_step_f32 behind the non-finite guard (max_norm = +inf: the guard alone)
+extern "C" int scae_rmsprop_guard_step_f32(float *param, const float *grad, float *square_avg,
+                                           float *buf, int64_t n, float lr, const float *lr_dev,
+                                           float alpha, float eps, float momentum,
+                                           float weight_decay, float grad_scale,
+                                           const double *partials, int n_partials,
+                                           float max_norm, float *norm_out,
+                                           int64_t *guard_state, void *stream) {
+  return rmsprop_clip_launch<true>(param, grad, square_avg, buf, n, lr, lr_dev, alpha, eps,
+                                   momentum, weight_decay, grad_scale, partials, n_partials,
+                                   max_norm, norm_out, guard_state, stream);
 }
 
 // scae_sum_rows_multi_f32(jobs) followed by scae_rmsprop_step_f32(...) as ONE launch
@@ -341,6 +403,34 @@ extern "C" int scae_rmsprop_acc_step_f32(float *param, const float *grad, float 
   return scae_launch_status();
 }
 
+// ... of scae_rmsprop_acc_clip_step_f32 and scae_rmsprop_acc_guard_step_f32
+namespace {
+template <bool GUARD>
+int rmsprop_acc_clip_launch(float *param, const float *grad, float *acc, float *square_avg,
+                            float *buf, int64_t n, float lr, const float *lr_dev, float alpha,
+                            float eps, float momentum, float weight_decay, float grad_scale,
+                            const double *partials, int n_partials, float max_norm,
+                            float *norm_out, int64_t *guard_state, void *stream) {
+  OptArgs a;
+  const int head = acc_prepare(a, param, grad, acc, square_avg, buf, n, lr, lr_dev, alpha, eps,
+                               momentum, weight_decay, grad_scale);
+  if (head < 0 || ((size_t)guard_state & 7)) return SCAE_ERR_BAD_ARG;
+  SCAE_REQUIRE(partials && n_partials > 0 && n_partials <= SCAE_GRAD_SQ_MAX_PARTIALS &&
+               max_norm > 0.f);
+  long blocks = (n / 4 + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  const scae_clip::Clip clip{partials, n_partials, max_norm, norm_out};
+  if constexpr (GUARD)
+    scae::launch(rmsprop_acc_guard_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                 (hipStream_t)stream, a, head, clip, scae_clip::Guard{(long long *)guard_state},
+                 acc);
+  else
+    scae::launch(rmsprop_acc_clip_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                 (hipStream_t)stream, a, head, clip, acc);
+  return scae_launch_status();
+}
+}  // namespace
+
 extern "C" int scae_rmsprop_acc_clip_step_f32(float *param, const float *grad, float *acc,
                                               float *square_avg, float *buf, int64_t n, float lr,
                                               const float *lr_dev, float alpha, float eps,
@@ -348,18 +438,21 @@ extern "C" int scae_rmsprop_acc_clip_step_f32(float *param, const float *grad, f
                                               float grad_scale, const double *partials,
                                               int n_partials, float max_norm, float *norm_out,
                                               void *stream) {
-  OptArgs a;
-  const int head = acc_prepare(a, param, grad, acc, square_avg, buf, n, lr, lr_dev, alpha, eps,
-                               momentum, weight_decay, grad_scale);
-  if (head < 0) return SCAE_ERR_BAD_ARG;
-  SCAE_REQUIRE(partials && n_partials > 0 && n_partials <= SCAE_GRAD_SQ_MAX_PARTIALS &&
-               max_norm > 0.f);
-  long blocks = (n / 4 + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-  scae::launch(rmsprop_acc_clip_kernel, dim3((unsigned)blocks), dim3(256), 0,
-               (hipStream_t)stream, a, head,
-               scae_clip::Clip{partials, n_partials, max_norm, norm_out}, acc);
-  return scae_launch_status();
+  return rmsprop_acc_clip_launch<false>(param, grad, acc, square_avg, buf, n, lr, lr_dev, alpha,
+                                        eps, momentum, weight_decay, grad_scale, partials,
+                                        n_partials, max_norm, norm_out, nullptr, stream);
+}
+
+extern "C" int scae_rmsprop_acc_guard_step_f32(float *param, const float *grad, float *acc,
+                                               float *square_avg, float *buf, int64_t n,
+                                               float lr, const float *lr_dev, float alpha,
+                                               float eps, float momentum, float weight_decay,
+                                               float grad_scale, const double *partials,
+                                               int n_partials, float max_norm, float *norm_out,
+                                               int64_t *guard_state, void *stream) {
+  return rmsprop_acc_clip_launch<true>(param, grad, acc, square_avg, buf, n, lr, lr_dev, alpha,
+                                       eps, momentum, weight_decay, grad_scale, partials,
+                                       n_partials, max_norm, norm_out, guard_state, stream);
 }
 
 extern "C" int scae_rmsprop_acc_sums_step_f32(float *param, float *grad, float *acc,

@@ -23,6 +23,10 @@
 // the norm launch's partials (grad_clip_dev.h) after grad_scale, before the weight decay.
 // The accumulate forms (scae_flat_opt_acc_*: gradient accumulation, grad_accumulate.hip) read
 // g = acc + grad in place of grad and leave acc = 0 behind.
+// The guarded forms (scae_flat_opt[_acc]_guard_step_f32: the non-finite guard) are the clip
+// forms behind a decision on the partials' fp64 sum: not finite, and the launch stores nothing
+// and makes no arrival (the accumulate form: acc = 0); finite, and it is the clip form bit
+// for bit.
 #include "grad_clip_dev.h"
 
 namespace {
@@ -279,6 +283,41 @@ __global__ __launch_bounds__(256) void adam_acc_clip_kernel(AdamArgs a, int head
                                                             scae_clip::Clip clip, float *acc) {
   adam_pass<K, true, true>(a, head, shared_scalars<K, true>(a, &clip), acc);
 }
+// the guarded forms of the two clip forms (the non-finite guard, grad_clip_dev.h): a workgroup
+// that finds the partials' fp64 sum not finite returns before the pass and before arrive() --
+// nothing is stored to p, m, v or slow, step_state keeps every int (the count, the slow-made
+// flag, the arrival counters at 0); the accumulate form leaves acc = 0 over its elements
+template <int K, bool ACC>
+__device__ __forceinline__ void adam_guard(const AdamArgs &a, int head,
+                                           const scae_clip::Clip &clip,
+                                           const scae_clip::Guard &guard, float *acc) {
+  __shared__ StepScalars sh;
+  bool skip;
+  const float coef = scae_clip::guard_coef(clip, guard, a.grad_scale, skip);
+  if (skip) {   // workgroup-uniform, after the sum's barrier
+    if (ACC) scae_clip::zero_acc(acc, a.n, head);
+    return;
+  }
+  if (threadIdx.x == 0) {   // (as shared_scalars<K, true>)
+    sh = step_scalars<K>(a);
+    sh.coef = coef;
+  }
+  __syncthreads();
+  const StepScalars s = sh;
+  adam_pass<K, true, ACC>(a, head, s, acc);
+}
+template <int K>
+__global__ __launch_bounds__(256) void adam_guard_kernel(AdamArgs a, int head,
+                                                         scae_clip::Clip clip,
+                                                         scae_clip::Guard guard) {
+  adam_guard<K, false>(a, head, clip, guard, nullptr);
+}
+template <int K>
+__global__ __launch_bounds__(256) void adam_acc_guard_kernel(AdamArgs a, int head,
+                                                             scae_clip::Clip clip,
+                                                             scae_clip::Guard guard, float *acc) {
+  adam_guard<K, true>(a, head, clip, guard, acc);
+}
 
 // The step's last column sums and the optimiser in one launch, as optimizer.hip's
 // rmsprop_sums_kernel: the sum workgroups (the head of the grid) update the elements they
@@ -368,6 +407,8 @@ template <int K> struct Clipped { static constexpr auto fn = adam_clip_kernel<K>
 template <int K> struct AccPlain { static constexpr auto fn = adam_acc_kernel<K>; };
 template <int K> struct AccSums { static constexpr auto fn = adam_acc_sums_kernel<K>; };
 template <int K> struct AccClipped { static constexpr auto fn = adam_acc_clip_kernel<K>; };
+template <int K> struct Guarded { static constexpr auto fn = adam_guard_kernel<K>; };
+template <int K> struct AccGuarded { static constexpr auto fn = adam_acc_guard_kernel<K>; };
 
 extern "C" int scae_flat_opt_step_f32(float *param, const float *grad, float *exp_avg,
                                       float *exp_avg_sq, float *slow, int64_t n,
@@ -411,6 +452,46 @@ extern "C" int scae_flat_opt_sums_step_f32(float *param, float *grad, float *exp
   return scae_launch_status();
 }
 
+// scae_flat_opt[_acc]_clip_step_f32 and scae_flat_opt[_acc]_guard_step_f32 behind one set of
+// checks and one grid; acc: the accumulate forms; GUARD: the guarded kernels, which also take
+// guard_state
+namespace {
+template <bool GUARD>
+int clip_launch(float *param, const float *grad, float *acc, float *exp_avg, float *exp_avg_sq,
+                float *slow, int64_t n, const float *lr_dev, int32_t *step_state, int kind,
+                double beta1, double beta2, float eps, float weight_decay, float grad_scale,
+                int look_ahead_k, float look_ahead_alpha, int advance, const double *partials,
+                int n_partials, float max_norm, float *norm_out, int64_t *guard_state,
+                bool with_acc, void *stream) {
+  AdamArgs a;
+  const int head = prepare(a, param, grad, exp_avg, exp_avg_sq, slow, n, lr_dev, step_state,
+                           kind, beta1, beta2, eps, weight_decay, grad_scale, look_ahead_k,
+                           look_ahead_alpha, advance);
+  if (head < 0 || ((size_t)guard_state & 7)) return SCAE_ERR_BAD_ARG;
+  if (with_acc && !(acc && ((size_t)acc & 15) == ((size_t)param & 15))) return SCAE_ERR_BAD_ARG;
+  SCAE_REQUIRE(partials && n_partials > 0 && n_partials <= SCAE_GRAD_SQ_MAX_PARTIALS &&
+               max_norm > 0.f);
+  long blocks = (n / 4 + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  const dim3 grid((unsigned)blocks);
+  const hipStream_t st = (hipStream_t)stream;
+  const scae_clip::Clip clip{partials, n_partials, max_norm, norm_out};
+  if constexpr (GUARD) {
+    const scae_clip::Guard guard{(long long *)guard_state};
+    if (with_acc)
+      launch_kind<AccGuarded>(kind, grid, st, a, head, clip, guard, acc);
+    else
+      launch_kind<Guarded>(kind, grid, st, a, head, clip, guard);
+  } else {
+    if (with_acc)
+      launch_kind<AccClipped>(kind, grid, st, a, head, clip, acc);
+    else
+      launch_kind<Clipped>(kind, grid, st, a, head, clip);
+  }
+  return scae_launch_status();
+}
+}  // namespace
+
 // scae_flat_opt_step_f32 with g scaled by clip_grad_norm_'s coefficient (grad_clip_dev.h)
 extern "C" int scae_flat_opt_clip_step_f32(float *param, const float *grad, float *exp_avg,
                                            float *exp_avg_sq, float *slow, int64_t n,
@@ -420,18 +501,26 @@ extern "C" int scae_flat_opt_clip_step_f32(float *param, const float *grad, floa
                                            int look_ahead_k, float look_ahead_alpha, int advance,
                                            const double *partials, int n_partials,
                                            float max_norm, float *norm_out, void *stream) {
-  AdamArgs a;
-  const int head = prepare(a, param, grad, exp_avg, exp_avg_sq, slow, n, lr_dev, step_state,
-                           kind, beta1, beta2, eps, weight_decay, grad_scale, look_ahead_k,
-                           look_ahead_alpha, advance);
-  if (head < 0) return SCAE_ERR_BAD_ARG;
-  SCAE_REQUIRE(partials && n_partials > 0 && n_partials <= SCAE_GRAD_SQ_MAX_PARTIALS &&
-               max_norm > 0.f);
-  long blocks = (n / 4 + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-  launch_kind<Clipped>(kind, dim3((unsigned)blocks), (hipStream_t)stream, a, head,
-                       scae_clip::Clip{partials, n_partials, max_norm, norm_out});
-  return scae_launch_status();
+  return clip_launch<false>(param, grad, nullptr, exp_avg, exp_avg_sq, slow, n, lr_dev,
+                            step_state, kind, beta1, beta2, eps, weight_decay, grad_scale,
+                            look_ahead_k, look_ahead_alpha, advance, partials, n_partials,
+                            max_norm, norm_out, nullptr, false, stream);
+}
+
+// scae_flat_opt_clip_step_f32 behind the non-finite guard (max_norm = +inf: the guard alone)
+extern "C" int scae_flat_opt_guard_step_f32(float *param, const float *grad, float *exp_avg,
+                                            float *exp_avg_sq, float *slow, int64_t n,
+                                            const float *lr_dev, int32_t *step_state, int kind,
+                                            double beta1, double beta2, float eps,
+                                            float weight_decay, float grad_scale,
+                                            int look_ahead_k, float look_ahead_alpha,
+                                            int advance, const double *partials,
+                                            int n_partials, float max_norm, float *norm_out,
+                                            int64_t *guard_state, void *stream) {
+  return clip_launch<true>(param, grad, nullptr, exp_avg, exp_avg_sq, slow, n, lr_dev,
+                           step_state, kind, beta1, beta2, eps, weight_decay, grad_scale,
+                           look_ahead_k, look_ahead_alpha, advance, partials, n_partials,
+                           max_norm, norm_out, guard_state, false, stream);
 }
 
 // ---- the accumulate forms (gradient accumulation): the three entry points above with
@@ -491,16 +580,24 @@ extern "C" int scae_flat_opt_acc_clip_step_f32(float *param, const float *grad, 
                                                float look_ahead_alpha, int advance,
                                                const double *partials, int n_partials,
                                                float max_norm, float *norm_out, void *stream) {
-  AdamArgs a;
-  const int head = prepare(a, param, grad, exp_avg, exp_avg_sq, slow, n, lr_dev, step_state,
+  return clip_launch<false>(param, grad, acc, exp_avg, exp_avg_sq, slow, n, lr_dev, step_state,
+                            kind, beta1, beta2, eps, weight_decay, grad_scale, look_ahead_k,
+                            look_ahead_alpha, advance, partials, n_partials, max_norm, norm_out,
+                            nullptr, true, stream);
+}
+
+extern "C" int scae_flat_opt_acc_guard_step_f32(float *param, const float *grad, float *acc,
+                                                float *exp_avg, float *exp_avg_sq, float *slow,
+                                                int64_t n, const float *lr_dev,
+                                                int32_t *step_state, int kind, double beta1,
+                                                double beta2, float eps, float weight_decay,
+                                                float grad_scale, int look_ahead_k,
+                                                float look_ahead_alpha, int advance,
+                                                const double *partials, int n_partials,
+                                                float max_norm, float *norm_out,
+                                                int64_t *guard_state, void *stream) {
+  return clip_launch<true>(param, grad, acc, exp_avg, exp_avg_sq, slow, n, lr_dev, step_state,
                            kind, beta1, beta2, eps, weight_decay, grad_scale, look_ahead_k,
-                           look_ahead_alpha, advance);
-  if (head < 0 || !acc_ok(acc, param)) return SCAE_ERR_BAD_ARG;
-  SCAE_REQUIRE(partials && n_partials > 0 && n_partials <= SCAE_GRAD_SQ_MAX_PARTIALS &&
-               max_norm > 0.f);
-  long blocks = (n / 4 + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-  launch_kind<AccClipped>(kind, dim3((unsigned)blocks), (hipStream_t)stream, a, head,
-                          scae_clip::Clip{partials, n_partials, max_norm, norm_out}, acc);
-  return scae_launch_status();
+                           look_ahead_alpha, advance, partials, n_partials, max_norm, norm_out,
+                           guard_state, true, stream);
 }

@@ -482,20 +482,26 @@ def _init_guard(opt, nonfinite):
     exactly when every element is (the fp32 norm may overflow for finite gradients and does
     not decide).  A finite step has the unguarded step's bits; ``grad_norm`` is written either
     way, and a tracking optimiser's ``GradNorms`` row is still written for a skipped step.
-    CPU tensors only so far: there is no device form of the guard yet, and asking for it on a
-    HIP device raises (nothing falls back to an unguarded step)."""
+    On a HIP device the step takes the guarded forms of the passes (``_device_step``:
+    scae_*_guard_step_f32), which decide on the norm launch's partials: ``grad_sq`` is
+    allocated as clipping allocates it, and ``guard_state`` and ``grad_norm`` live in device
+    memory -- a replayed step reads nothing back.  Any other device type raises (nothing falls
+    back to an unguarded step)."""
     if nonfinite not in (None, "skip"):
         raise ValueError(f"an optimiser's nonfinite must be None or 'skip', got {nonfinite!r}")
     opt.nonfinite = nonfinite
     opt.guard_state = None
     if nonfinite:
         dev = opt.flat.flat_param.device
-        if dev.type != "cpu":
+        if dev.type not in ("cpu", "cuda"):
             from ._lib import ScaeHipError
-            raise ScaeHipError("nonfinite='skip' has no device form yet: the guarded optimiser "
-                               "passes are not built, and the step does not run unguarded")
+            raise ScaeHipError(f"nonfinite='skip' has a CPU form and a HIP device form, none for "
+                               f"a {dev.type!r} device, and the step does not run unguarded")
         if opt.grad_norm is None:
             opt.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+        if opt.grad_sq is None:       # (as _init_clip: the CPU forms do not read it)
+            from ._lib import GRAD_SQ_MAX_PARTIALS
+            opt.grad_sq = torch.zeros(GRAD_SQ_MAX_PARTIALS, dtype=torch.float64, device=dev)
         opt.guard_state = torch.tensor([0, -1, -1, 0], dtype=torch.int64, device=dev)
 
 
@@ -713,11 +719,11 @@ def _track_first(opt, grad_scale, sum_units, acc, device):
     """A tracking optimiser's step, before its pass: the norms of the gradient the pass
     consumes.  The flat gradient is complete only once the step's last column sums
     (``sum_units``) have run, so they are launched on their own here -- the same bits as riding
-    in the pass -- and the norms after them; -> the units still to launch.  A clipping step on
-    the device (``device``: the step takes ``_device_step``) keeps them: they ride in its norm
-    launch, and the norms follow that (``_track_after_norm``)."""
+    in the pass -- and the norms after them; -> the units still to launch.  A clipping or
+    guarded step on the device (``device``: the step takes ``_device_step``) keeps them: they
+    ride in its norm launch, and the norms follow that (``_track_after_norm``)."""
     trk = opt.track
-    if trk is None or (device and opt.max_norm):
+    if trk is None or (device and (opt.max_norm or opt.nonfinite)):
         return sum_units
     _riding_units(sum_units, False)
     trk.build(_group_seen(opt))
@@ -726,8 +732,9 @@ def _track_first(opt, grad_scale, sum_units, acc, device):
 
 
 def _track_after_norm(opt, grad_scale, acc):
-    """... of a clipping step on the device: after the clip's norm launch, which hosts the
-    column sums, and before the pass (whose accumulate form clears acc)."""
+    """... of a clipping or guarded step on the device: after the norm launch, which hosts the
+    column sums, and before the pass (whose accumulate form clears acc; a step the guard
+    skips has its row written here)."""
     trk = opt.track
     if trk is not None:
         trk.build(_group_seen(opt))
@@ -802,11 +809,15 @@ def _flat_opt_form(opt, m, v, betas):
 
 
 def _device_step(opt, grad_scale, sum_units, acc):
-    """One optimiser step on a HIP device, through scae_{family}[_acc][_sums|_clip]_step_f32
-    (``opt._device_form()`` -> family, buffers, fixed arguments).  Clipping: the norm launch
-    (the column sums ride in it), the tracked norms, then the ``_clip`` form over each active
-    range.  Else the column sums ride in the pass when there is no weight decay (the ``_sums``
-    form, over the whole buffer: the sum workgroups update the elements they produce), and
+    """One optimiser step on a HIP device, through
+    scae_{family}[_acc][_sums|_clip|_guard]_step_f32 (``opt._device_form()`` -> family, buffers,
+    fixed arguments).  Clipping: the norm launch (the column sums ride in it), the tracked
+    norms, then the ``_clip`` form over each active range.  Guarded (``_init_guard``): the same
+    path whether it clips or not, through the ``_guard`` form -- max_norm +inf when it does
+    not clip; the first range's launch writes the norm and counts in ``guard_state``, every
+    range's launch takes the same decision.  Else the column sums ride in the pass when there
+    is no weight decay (the ``_sums`` form, over the whole buffer: the sum workgroups update
+    the elements they produce), and
     otherwise the plain form runs over each active range: parameters without a gradient are
     left alone, like torch.optim does; without weight decay a zero gradient already is a
     no-op (zero moments stay zero, LookAhead's slow copy of such a parameter equals it).
@@ -819,7 +830,8 @@ def _device_step(opt, grad_scale, sum_units, acc):
     st = _stream(g)
     family, bufs, fixed = opt._device_form()
     counts = family == "scae_flat_opt"     # (this family counts steps and syncs LookAhead)
-    clip = bool(opt.max_norm)
+    guard = bool(opt.nonfinite)
+    clip = bool(opt.max_norm) or guard      # (the forms that follow a norm launch)
     if clip:
         n_partials = _launch_norm(opt, g, sum_units, st, acc)
         _track_after_norm(opt, grad_scale, acc)
@@ -830,7 +842,8 @@ def _device_step(opt, grad_scale, sum_units, acc):
     if sum_units:
         ranges = [(0, g.numel())]
     name = "%s%s%s_step_f32" % (family, "" if acc is None else "_acc",
-                                "_clip" if clip else "_sums" if sum_units else "")
+                                "_guard" if guard else "_clip" if clip else
+                                "_sums" if sum_units else "")
     for i, (off, n) in enumerate(ranges):
         ptr = lambda t: P(t.data_ptr() + 4 * off)   # noqa: E731
         # the accumulate forms take acc right after grad
@@ -846,8 +859,10 @@ def _device_step(opt, grad_scale, sum_units, acc):
                 # reads the same t)
                 args.append(int(i == len(ranges) - 1))
         if clip:
-            args += [P(opt.grad_sq.data_ptr()), n_partials, opt.max_norm,
+            args += [P(opt.grad_sq.data_ptr()), n_partials, opt.max_norm or math.inf,
                      P(opt.grad_norm.data_ptr()) if i == 0 else None]
+            if guard:
+                args.append(P(opt.guard_state.data_ptr()) if i == 0 else None)
         elif sum_units:
             args += [ops._sum_job_array(sum_units), len(sum_units)]
         _lib.call(name, *args, st)
@@ -981,8 +996,8 @@ def make_optimizer(kind, flat, lr, eps, betas=(0.9, 0.999), momentum=0.9,
     ``gradient_clip_val`` > 0: every step clips the gradient to that global norm first.
     ``accumulate_grad_batches`` > 1: the optimiser keeps an accumulator (``accumulate``).
     ``nonfinite="skip"``: a step whose gradient holds a NaN or Inf writes nothing and is
-    counted (``_init_guard``: CPU tensors only so far, a HIP device raises); None (the
-    default): the step as it was."""
+    counted (``_init_guard``; on a HIP device through the guarded forms of the passes); None
+    (the default): the step as it was."""
     name = str(kind).lower()
     la = dict(look_ahead=look_ahead, look_ahead_k=look_ahead_k,
               look_ahead_alpha=look_ahead_alpha, gradient_clip_val=gradient_clip_val,

@@ -167,10 +167,12 @@ class TrainStep:
     or Inf.  ``steps`` and ``optimizer_steps`` stay HOST counts of batches and of ATTEMPTED
     optimiser steps, skipped ones included; ``optimizer_state_dict()`` reports ``step`` as the
     optimiser's own count where it keeps one and as ``optimizer_steps - skipped`` for plain
-    RMSprop.  ``snapshot()`` / ``restore()`` carry the counters.  So far the guard exists for
-    CPU tensors only (the flat optimisers' CPU forms): the guarded forms of the HIP optimiser
-    passes are not built, and a step on a HIP device that asks for the guard raises
-    ``ScaeHipError`` when it is constructed -- it never runs unguarded.
+    RMSprop.  ``snapshot()`` / ``restore()`` carry the counters.  On a HIP device the
+    decision is taken inside the optimiser pass (the guarded forms, scae_*_guard_step_f32, on
+    the partial sums of the same norm launch clipping uses: one launch more per optimiser step
+    than the unguarded, unclipped step, none more than the clipped one), and the counters and
+    the norm live in device memory: one captured graph or launch list serves both outcomes,
+    and a replayed step reads nothing back.
     """
 
     MODES = ("2 buckets", "1 bucket", "in graph")
