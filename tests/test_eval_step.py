@@ -94,6 +94,45 @@ def test_epoch_means_are_unweighted_over_batches_with_a_remainder():
                                                                     "test_accuracy"}
 
 
+class CapsStub(StubModel):
+    """StubModel with the object-capsule surface ``encode`` reads as well."""
+
+    def __init__(self):
+        super().__init__()
+        self.obj_decoder = SimpleNamespace(n_obj_capsules=2)
+
+    def forward(self, image):
+        res = super().forward(image)
+        x = image.flatten(1) * self.w
+        res.caps_presence, res.posterior_mixing_prob = x[:, :2], x.view(-1, 2, 2)
+        return res
+
+
+@pytest.mark.parametrize("N", [10, 8])
+def test_evaluate_encode_and_predict_give_the_same_means(N):
+    """The three walk the split alike: identical means, with a remainder batch (N = 10) and
+    without (N = 8), and again on the same step (the tail step reused, accumulators cleared)."""
+    from torch_scae_amd import EvalStep
+    model = CapsStub()
+    images, labels = _batches(N, 3)
+    step = EvalStep(model, 4, (1, 2, 2))
+    rounds = []
+    for _ in range(2):
+        m = step.evaluate(images, labels)
+        assert m["batches"] == -(-N // 4)
+        for other in (step.encode(images, labels)["means"],
+                      step.predict(images, labels)["means"]):
+            assert set(other) == set(m)
+            for k in m:
+                assert torch.equal(torch.as_tensor(m[k]), torch.as_tensor(other[k])), k
+        for s in (step, step._tail_step):
+            assert s is None or float(s.acc.abs().sum()) == 0.0
+        rounds.append(m)
+    assert (step._tail_step is None) == (N % 4 == 0)
+    for k in rounds[0]:
+        assert torch.equal(torch.as_tensor(rounds[0][k]), torch.as_tensor(rounds[1][k])), k
+
+
 def test_epoch_means_keep_every_key_and_count():
     from torch_scae_amd import eval_step
     acc = torch.zeros(eval_step.ACC_DOUBLES, dtype=torch.float64)

@@ -346,3 +346,83 @@ def test_epilogue_combine_is_the_tail_combine_bit_for_bit(B, O, M):
     a = acc.cpu()
     assert a[0] == 1 and a[1] == float(outs[0][12]) and a[2] == float(best)
     assert a[5:].tolist() == outs[0][:12].double().cpu().tolist()
+
+
+# the model of the package's smoke run
+SMALL = dict(image_shape=(1, 16, 16), n_classes=4, n_part_caps=5, n_obj_caps=4,
+             pcae_cnn_encoder_params=dict(out_channels=[64, 64], kernel_sizes=[3, 3],
+                                          strides=[2, 1]),
+             pcae_template_generator_params=dict(template_size=(5, 5)),
+             ocae_encoder_set_transformer_params=dict(dim_hidden=8, dim_out=64, n_layers=2),
+             ocae_decoder_capsule_params=dict(dim_caps=4, hidden_sizes=(8,)),
+             scae_params=dict(reconstruct_alternatives=False))
+
+
+def _same(a, b):
+    if isinstance(a, dict):
+        return set(a) == set(b) and all(_same(a[k], b[k]) for k in a)
+    if a is None or b is None:
+        return a is b
+    return torch.equal(torch.as_tensor(a), torch.as_tensor(b))
+
+
+@pytest.mark.parametrize("source", ["tensors", "view"])
+def test_evaluate_encode_and_predict_share_the_walk_and_the_captured_graphs(source):
+    """evaluate, encode, predict, evaluate on one step, B = 4 and N = 10 (two full batches and
+    a tail of 2), round after round.  The first round captures: once, again when encode
+    attaches the sink, again when predict attaches the records, and not for the evaluate after
+    them.  Its batches draw the noise that follows the captures' warm-up draws, so its values
+    are no yardstick; the two rounds after it are the ones compared: the same graph objects
+    throughout (nothing recaptured), every result bit for bit the round before's, and
+    evaluate's means those of a fresh step that never had a descriptor attached."""
+    from torch_scae_amd import EvalStep, data, factory, ops
+    np.random.seed(0)
+    torch.manual_seed(0)
+    model = factory.make_scae(SMALL)
+    with torch.no_grad():
+        for p in model.parameters():
+            if float(p.abs().sum()) == 0.0:
+                p.normal_(0, 0.1)
+    model = model.cuda().train()
+    g = torch.Generator().manual_seed(11)
+    ds = data.ResidentDataset(torch.rand(10, 1, 16, 16, generator=g),
+                              torch.randint(0, 4, (10,), generator=g), out_size=(16, 16),
+                              device="cuda")
+    view = ds.view(shuffle=False, translate=False)
+    args = (view,) if source == "view" else tuple(t.cuda() for t in view.materialise())
+
+    def seeded(call):
+        torch.manual_seed(5)
+        ops.reset_noise()
+        return call(*args)
+
+    step = EvalStep(model, 4, (1, 16, 16), use_graph=True)
+
+    def one_round():
+        results, graphs = [], []
+        for call in (step.evaluate, step.encode, step.predict, step.evaluate):
+            results.append(seeded(call))
+            graphs.append((step.graph, step._tail_step.graph))
+        return results, graphs
+
+    _, graphs = one_round()
+    assert step._tail_step.batch_size == 2
+    for which in (0, 1):                   # the step and its tail step
+        a, b, c, d = (pair[which] for pair in graphs)
+        assert a is not None and b is not a and c is not b and d is c
+    captured = graphs[-1]
+    rounds = [one_round() for _ in range(2)]
+    for _, graphs in rounds:
+        for pair in graphs:
+            assert pair[0] is captured[0] and pair[1] is captured[1]
+    first, second = rounds[0][0], rounds[1][0]
+    assert first[0]["batches"] == 3 and first[1]["rows"] == first[2]["rows"] == 10
+    for a, b in zip(first, second):
+        assert _same(a, b)
+    fresh = EvalStep(model, 4, (1, 16, 16), use_graph=True)
+    fresh.evaluate(*args)                  # (captures the step and its tail step)
+    want = seeded(fresh.evaluate)
+    assert fresh.epi.sink is None and fresh.epi.records is None
+    for got in (first[0], first[3], first[1]["means"], first[2]["means"]):
+        assert _same(got, want)
+    assert float(step.acc.abs().sum()) == 0.0 and float(step._tail_step.acc.abs().sum()) == 0.0

@@ -215,10 +215,8 @@ class EvalStep:
         self._stream = None
         self._home = None        # parameter storage the capture read
         self._tail_step = None   # evaluate()'s remainder batch
-        self._cap_sink = None    # the feature sink the captured launches carry
-        self._cpu_rows = None    # encode() on the CPU: the batches' (B, 2, O) rows
-        self._cap_records = None    # the records the captured launches carry
-        self._cpu_records = None    # predict() on the CPU: (labelled, the batches' rows)
+        self._cap_desc = (None, None)   # the (sink, records) the captured launches carry
+        self._cpu_collect = None    # collecting on the CPU: (a batch's rows, the batches' rows)
         self._zero_labels = None
 
     # the captured batch, read-only (replay.Captured; _klist: its list's raw handle)
@@ -256,12 +254,9 @@ class EvalStep:
         if not self.cuda:
             res = model(self.image)
             loss, log = model.loss(res, self.image, label)
-            if self._cpu_rows is not None:
-                self._cpu_rows.append(torch.stack(
-                    [res.caps_presence, res.posterior_mixing_prob.sum(-1)], 1))
-            if self._cpu_records is not None:
-                self._cpu_records[1].append(records_host(res, self.image, label,
-                                                         self._cpu_records[0]))
+            if self._cpu_collect is not None:
+                rows_of, rows = self._cpu_collect
+                rows.append(rows_of(res, self.image, label))
             probs = (res.prior_cls_prob, res.posterior_cls_prob) if label is not None \
                 else (None, None)
             self.batch_acc.copy_(accumulate_host(self.acc, loss, out12_from_log(loss, log),
@@ -344,8 +339,7 @@ class EvalStep:
             self._cap = _replay.capture(s, self._batch, keep_graph=True, census_always=True,
                                         want_list=self.replay == "launches")
         self._home = self._storage()
-        self._cap_sink = self.epi.sink
-        self._cap_records = self.epi.records
+        self._cap_desc = (self.epi.sink, self.epi.records)
         self._refresh_prologue()
 
     def capture(self):
@@ -357,8 +351,8 @@ class EvalStep:
 
     def _stale(self):
         return self.graph is None or self._home != self._storage() or \
-            self._cap_sink is not self.epi.sink or \
-            self._cap_records is not self.epi.records
+            self._cap_desc[0] is not self.epi.sink or \
+            self._cap_desc[1] is not self.epi.records
 
     def __call__(self, image, label):
         """One evaluation batch: stage, run (replay), accumulate.  -> the batch loss."""
@@ -533,72 +527,40 @@ class EvalStep:
         tail.reset()
         return tail
 
-    def evaluate(self, images, labels=None):
-        """A whole split: every full batch replayed, the remainder through a second step of
-        the remainder's size (captured once, cached; not padded -- the between-example
-        terms depend on the batch size).  -> ``epoch_means()`` of the split: the unweighted
-        mean over its batches, as the reference's loop (and a ``drop_last=False`` loader)
-        gives.  Starts from a cleared accumulator and leaves it cleared.
-
-        ``images`` may be a data.DatasetView instead of (images, labels): its examples in
-        the order and with the shifts of its current epoch (``view.materialise()``), the
-        full batches gathered in the step's prologue launch, the remainder by the
-        standalone gather into the tail step; the view then moves on to its next epoch.
-        With world > 1 rank r takes slots [r*B, (r+1)*B) of each global batch of world*B
-        and rank 0 alone the remainder of the view."""
+    # -- a whole split: evaluate / encode / predict ---------------------------------------------
+    def _split(self, what, images, labels, need_labels=False, any_world=False):
+        """The one argument check of ``what`` ("evaluate", "encode", "predict"), before anything
+        is touched.  -> (view or None, N, full, rem): the examples of the split and this rank's
+        full batches and remainder."""
         from .data import DatasetView
+        B = self.batch_size
+        if not any_world and world()[1] > 1:
+            raise ValueError(f"{what} gathers one process's rows: world > 1 is not supported")
         if isinstance(images, DatasetView):
-            return self._evaluate_view(images)
-        N, B = images.shape[0], self.batch_size
-        if labels is None or labels.shape[0] != N or N == 0:
+            view, ds = images, images.dataset
+            if not self.cuda:
+                raise ValueError(f"{what} of a device-resident dataset needs a device step")
+            if (ds.C, ds.H, ds.W) != self.image_shape:
+                raise ValueError(f"the view gives ({ds.C}, {ds.H}, {ds.W}) images, the step "
+                                 f"takes {self.image_shape}")
+            full = view.steps_per_epoch(B)
+            rem = view.n - full * view.world * B if view.rank == 0 else 0
+            return view, view.n, full, rem
+        N = images.shape[0]
+        if N == 0 or (labels is None and need_labels) or \
+                (labels is not None and labels.shape[0] != N):
             raise ValueError("images and labels must hold the same number (> 0) of examples")
-        full, rem = divmod(N, B)
-        tail = self._tail(rem) if rem else None
-        self.reset()
-        for i in range(full):
-            self(images[i * B:(i + 1) * B], labels[i * B:(i + 1) * B])
-        sums = self._global_sums()
-        if tail is not None:
-            tail(images[full * B:], labels[full * B:])
-            sums = sums + tail._global_sums()
-            tail.reset()
-        self.reset()
-        return means(sums)
+        return (None, N) + divmod(N, B)
 
-    def _evaluate_view(self, view):
-        if not self.cuda:
-            raise ValueError("evaluating a device-resident dataset needs a device step")
-        B, W = self.batch_size, view.world
-        ds = view.dataset
-        if (ds.C, ds.H, ds.W) != self.image_shape:
-            raise ValueError(f"the view gives ({ds.C}, {ds.H}, {ds.W}) images, the step "
-                             f"takes {self.image_shape}")
-        full = view.steps_per_epoch(B)
-        done = full * W * B
-        rem = view.n - done if view.rank == 0 else 0
-        tail = self._tail(rem) if rem else None
-        epoch = view.epoch
-        self.reset()
-        for i in range(full):
-            self._run(lambda: self._stage_source(view, epoch, i * W * B))
-        sums = self.acc.clone()
-        if tail is not None:
-            tail._run(lambda: tail._stage_source(view, epoch, done, rank=0,
-                                                 standalone=True))
-            sums += tail.acc
-            tail.reset()
-        if world()[1] > 1:
-            all_reduce_sums(sums)
-        self.reset()
-        view.epoch, view.cursor = epoch + 1, 0
-        return means(sums)
-
-    # -- features for unsupervised classification (cluster.py) -------------------------------
-    def _attach_sink(self, sink):
-        """Aim this step's batches at ``sink`` (off while the capture's warm-ups run)."""
-        self.epi.sink = sink
-        if self.use_graph:
-            self.capture()
+    def _out_rows(self, out, N, shape):
+        """The (R, *shape) fp32 buffer the rows go to: ``out`` checked, or N rows."""
+        if out is None:
+            return torch.empty(N, *shape, device=self.device)
+        if tuple(out.shape[1:]) != shape or out.dtype != torch.float32 or \
+                out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous (R, {', '.join(map(str, shape))}) fp32 "
+                             f"tensor on {self.device}")
+        return out
 
     def _labels_for(self, labels, lo, hi):
         if labels is not None:
@@ -608,72 +570,35 @@ class EvalStep:
             self._zero_labels = torch.zeros(n, dtype=torch.long, device=self.device)
         return self._zero_labels
 
-    def encode(self, images, labels=None, out=None):
-        """The object-capsule features of a whole split, with its evaluation means: every
-        full batch replayed as ``evaluate`` runs it, the remainder through the cached tail
-        step, and each image's two classifier inputs -- ``caps_presence`` and the posterior
-        mass ``posterior_mixing_prob.sum(-1)`` -- stored into a device sink on the way (by the
-        loss tail's per-image launch where SCAE.forward's class probabilities ride in it, else
-        by one launch of its own per batch).  ``images`` may be a data.DatasetView: its rows
-        come out in ``view.materialise()`` order and the view moves on to its next epoch, as
-        with ``evaluate``.
+    def _walk(self, split, images, labels, collect=None):
+        """Run a checked split (``_split``): every full batch replayed, the remainder through
+        a second step of the remainder's size (``_tail``: captured once, cached by size; not
+        padded -- the between-example terms depend on the batch size).  Both accumulators are
+        cleared on entry and on exit.  -> (this step's fp64 sums, the tail step's or None,
+        ``_collecting``'s dict).
 
-        -> {"prior" (N, O), "posterior" (N, O), "label" (N,) int64 or None, "means"
-        (``evaluate``'s), "rows" (rows written), "overflow"}.  ``out``: an (R, 2, O) fp32
-        device buffer to write into (default: N rows); rows at or beyond R are dropped and
-        ``overflow`` is True.  Without labels the step's loss sees zeros and the accuracies
-        in ``means`` mean nothing."""
-        from .data import DatasetView
-        if world()[1] > 1:
-            raise ValueError("encode gathers one process's rows: world > 1 is not supported")
-        O = self.model.obj_decoder.n_obj_capsules
-        view = images if isinstance(images, DatasetView) else None
-        if view is not None:
-            if not self.cuda:
-                raise ValueError("encoding a device-resident dataset needs a device step")
-            ds = view.dataset
-            if (ds.C, ds.H, ds.W) != self.image_shape:
-                raise ValueError(f"the view gives ({ds.C}, {ds.H}, {ds.W}) images, the step "
-                                 f"takes {self.image_shape}")
-            N = view.n
-            rows, _ = view.rows_and_shifts(view.epoch, torch.arange(N))
-            label = ds.labels[rows.to(ds.device)].to(torch.int64)
-        else:
-            N = images.shape[0]
-            if N == 0 or (labels is not None and labels.shape[0] != N):
-                raise ValueError("images and labels must hold the same number (> 0) of "
-                                 "examples")
-            label = None if labels is None else labels.to(self.device, torch.int64)
-        if out is None:
-            out = torch.empty(N, 2, O, device=self.device)
-        elif out.dim() != 3 or tuple(out.shape[1:]) != (2, O) or \
-                out.dtype != torch.float32 or out.device != self.device or \
-                not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous (R, 2, {O}) fp32 tensor on "
-                             f"{self.device}")
+        Tensors are staged batch by batch, missing labels as cached zeros.  A data.DatasetView
+        gives its examples in the order and with the shifts of its current epoch
+        (``view.materialise()``): the full batches gathered in the step's prologue launch, the
+        remainder by the stand-alone gather into the tail step.  With ``view.world`` > 1 rank r
+        takes slots [r*B, (r+1)*B) of each global batch of world*B and rank 0 alone the
+        remainder.  The view moves on to its next epoch once every batch has run.
+
+        ``collect``: ``_collecting``'s arguments after the steps -- the rows the batches write
+        on the way."""
+        view, N, full, rem = split
         B = self.batch_size
-        full, rem = divmod(N, B)
         tail = self._tail(rem) if rem else None
         steps = [self] + ([tail] if tail is not None else [])
-        if self.cuda:
-            if self.epi.sink is None:
-                self.epi.sink = ops.EvalSink(self.device)
-            sink = self.epi.sink
-            sink.off()
-            for st in steps:
-                st._attach_sink(sink)
-            sink.point(out)
-        else:
-            for st in steps:
-                st._cpu_rows = []
-        try:
+        rows = self._collecting(steps, *collect) if collect else contextlib.nullcontext({})
+        with rows as got:
             self.reset()
             if view is not None:
-                epoch = view.epoch
+                epoch, stride = view.epoch, view.world * B
                 for i in range(full):
-                    self._run(lambda: self._stage_source(view, epoch, i * B))
+                    self._run(lambda: self._stage_source(view, epoch, i * stride))
                 if tail is not None:
-                    tail._run(lambda: tail._stage_source(view, epoch, full * B, rank=0,
+                    tail._run(lambda: tail._stage_source(view, epoch, full * stride, rank=0,
                                                          standalone=True))
                 view.epoch, view.cursor = epoch + 1, 0
             else:
@@ -682,45 +607,116 @@ class EvalStep:
                                                                      (i + 1) * B))
                 if tail is not None:
                     tail(images[full * B:], self._labels_for(labels, full * B, N))
-            sums = self.acc.clone()
+            sums, tail_sums = self.acc.clone(), None
             if tail is not None:
-                sums += tail.acc
+                tail_sums = tail.acc.clone()
                 tail.reset()
             self.reset()
-            if self.cuda:
-                cursor, overflow = sink.status()
-                written = min(cursor, out.shape[0])
-            else:
-                got = torch.cat([r for st in steps for r in st._cpu_rows])
-                written = min(N, out.shape[0])
-                out[:written].copy_(got[:written])
-                overflow = N > out.shape[0]
-        finally:
-            if self.cuda:
-                sink.off()
-            else:
-                for st in steps:
-                    st._cpu_rows = None
-        feats = out[:written]
-        return {"prior": feats[:, 0], "posterior": feats[:, 1], "label": label,
-                "means": means(sums), "rows": written, "overflow": overflow,
-                "features": feats}
+        return sums, tail_sums, got
 
-    # -- per-example predictions and confusion matrices ----------------------------------------
-    def _attach_records(self, records):
-        """Aim this step's batches at ``records`` (off while the capture's warm-ups run)."""
-        self.epi.records = records
+    def _attach(self, field, desc):
+        """Aim this step's batches at ``desc``, the epilogue's ``field`` ("sink", "records");
+        off while the capture's warm-ups run."""
+        setattr(self.epi, field, desc)
         if self.use_graph:
             self.capture()
 
+    @contextlib.contextmanager
+    def _collecting(self, steps, out, field, make, rows_of, aim=()):
+        """The rows ``steps``' batches write on the way, into ``out``.  -> a dict that holds
+        "rows" (rows written) and "overflow" on exit.  On the device through the epilogue's
+        descriptor ``field`` (made by ``make`` once, attached to every step -- a step whose
+        descriptor changed recaptures, ``_stale`` -- aimed by ``point(out, *aim)``, read once,
+        and off again whatever happens: it stays attached with capacity 0, so later calls
+        replay the same graphs).  On the CPU each batch appends ``rows_of(res, image, label)``
+        and the rows that fit are copied."""
+        if self.cuda:
+            desc = getattr(self.epi, field)
+            if desc is None:
+                desc = make(self.device)
+            desc.off()
+            for st in steps:
+                st._attach(field, desc)
+            desc.point(out, *aim)
+        else:
+            for st in steps:
+                st._cpu_collect = (rows_of, [])
+        got = {}
+        try:
+            yield got
+            if self.cuda:
+                cursor, overflow = desc.status()
+            else:
+                rows = torch.cat([r for st in steps for r in st._cpu_collect[1]])
+                cursor, overflow = rows.shape[0], rows.shape[0] > out.shape[0]
+            written = min(cursor, out.shape[0])
+            if not self.cuda:
+                out[:written].copy_(rows[:written])
+            got.update(rows=written, overflow=overflow)
+        finally:
+            if self.cuda:
+                desc.off()
+            else:
+                for st in steps:
+                    st._cpu_collect = None
+
+    def evaluate(self, images, labels=None):
+        """A whole split (``_walk``; ``images`` may be a data.DatasetView instead of (images,
+        labels)).  -> ``epoch_means()`` of the split: the unweighted mean over its batches, as
+        the reference's loop (and a ``drop_last=False`` loader) gives."""
+        split = self._split("evaluate", images, labels, need_labels=True, any_world=True)
+        sums, tail_sums, _ = self._walk(split, images, labels)
+        reduce = world()[1] > 1
+        if reduce and split[0] is None and tail_sums is not None:
+            # tensors: the two steps' sums are reduced each on its own and then added, a view's
+            # are added and then reduced.  The two orders can differ in the last fp64 bit, so
+            # each stays as it was
+            all_reduce_sums(sums)
+            all_reduce_sums(tail_sums)
+            reduce = False
+        if tail_sums is not None:
+            sums += tail_sums
+        if reduce:
+            all_reduce_sums(sums)
+        return means(sums)
+
+    def encode(self, images, labels=None, out=None):
+        """The object-capsule features of a whole split (``_walk``; ``images`` may be a
+        data.DatasetView), with its evaluation means: each image's two classifier inputs --
+        ``caps_presence`` and the posterior mass ``posterior_mixing_prob.sum(-1)`` -- stored
+        into a device sink on the way (by the loss tail's per-image launch where SCAE.forward's
+        class probabilities ride in it, else by one launch of its own per batch).
+
+        -> {"prior" (N, O), "posterior" (N, O), "label" (N,) int64 or None, "means"
+        (``evaluate``'s), "rows" (rows written), "overflow"}.  ``out``: an (R, 2, O) fp32
+        device buffer to write into (default: N rows); rows at or beyond R are dropped and
+        ``overflow`` is True.  Without labels the step's loss sees zeros and the accuracies
+        in ``means`` mean nothing."""
+        split = self._split("encode", images, labels)
+        view, N = split[:2]
+        O = self.model.obj_decoder.n_obj_capsules
+        out = self._out_rows(out, N, (2, O))
+        if view is not None:
+            ds = view.dataset
+            rows, _ = view.rows_and_shifts(view.epoch, torch.arange(N))
+            label = ds.labels[rows.to(ds.device)].to(torch.int64)
+        else:
+            label = None if labels is None else labels.to(self.device, torch.int64)
+        sums, tail_sums, got = self._walk(split, images, labels, (
+            out, "sink", ops.EvalSink, lambda res, image, lab: torch.stack(
+                [res.caps_presence, res.posterior_mixing_prob.sum(-1)], 1)))
+        if tail_sums is not None:
+            sums += tail_sums
+        feats = out[:got["rows"]]
+        return {"prior": feats[:, 0], "posterior": feats[:, 1], "label": label,
+                "means": means(sums), **got, "features": feats}
+
     def predict(self, images, labels=None, out=None):
-        """One record per image of a whole split, both heads' confusion matrices and the
-        split's evaluation means: every full batch replayed as ``evaluate`` runs it, the
-        remainder through the cached tail step, the records written on the way by the launch
-        that ends each batch (the fused epilogue's combine workgroup; for a model outside the
-        fused tail one launch of its own per batch).  ``images`` may be a data.DatasetView:
-        its rows come out in ``view.materialise()`` order and the view moves on to its next
-        epoch, as with ``evaluate`` and ``encode``.
+        """One record per image of a whole split (``_walk``; ``images`` may be a
+        data.DatasetView), both heads' confusion matrices and the split's evaluation means:
+        the records written on the way by the launch that ends each batch (the fused
+        epilogue's combine workgroup; for a model outside the fused tail one launch of its own
+        per batch).
 
         -> {"records": (N, 9) fp32 device tensor, one row per image --
               [0] label (-1 without labels)
@@ -740,88 +736,22 @@ class EvalStep:
         Without labels the step's loss sees zeros: the accuracies in ``means`` mean nothing,
         ``confusion`` stays zero and means nothing either.  A model without classes gives
         classes -1, probabilities 0 and an empty ``confusion``."""
-        from .data import DatasetView
-        if world()[1] > 1:
-            raise ValueError("predict gathers one process's rows: world > 1 is not supported")
+        split = self._split("predict", images, labels)
+        view, N = split[:2]
         ncls = getattr(self.model, "n_classes", None) or 0
-        view = images if isinstance(images, DatasetView) else None
-        if view is not None:
-            if not self.cuda:
-                raise ValueError("predicting a device-resident dataset needs a device step")
-            ds = view.dataset
-            if (ds.C, ds.H, ds.W) != self.image_shape:
-                raise ValueError(f"the view gives ({ds.C}, {ds.H}, {ds.W}) images, the step "
-                                 f"takes {self.image_shape}")
-            N = view.n
-        else:
-            N = images.shape[0]
-            if N == 0 or (labels is not None and labels.shape[0] != N):
-                raise ValueError("images and labels must hold the same number (> 0) of "
-                                 "examples")
         labelled = view is not None or labels is not None
-        if out is None:
-            out = torch.empty(N, RECORD_FLOATS, device=self.device)
-        elif out.dim() != 2 or out.shape[1] != RECORD_FLOATS or \
-                out.dtype != torch.float32 or out.device != self.device or \
-                not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous (R, {RECORD_FLOATS}) fp32 tensor on "
-                             f"{self.device}")
+        out = self._out_rows(out, N, (RECORD_FLOATS,))
         confusion = torch.zeros(2, ncls, ncls, dtype=torch.int64, device=self.device)
-        B = self.batch_size
-        full, rem = divmod(N, B)
-        tail = self._tail(rem) if rem else None
-        steps = [self] + ([tail] if tail is not None else [])
-        if self.cuda:
-            if self.epi.records is None:
-                self.epi.records = ops.EvalRecords(self.device)
-            records = self.epi.records
-            records.off()
-            for st in steps:
-                st._attach_records(records)
-            records.point(out, confusion, labelled)
-        else:
-            for st in steps:
-                st._cpu_records = (labelled, [])
-        try:
-            self.reset()
-            if view is not None:
-                epoch = view.epoch
-                for i in range(full):
-                    self._run(lambda: self._stage_source(view, epoch, i * B))
-                if tail is not None:
-                    tail._run(lambda: tail._stage_source(view, epoch, full * B, rank=0,
-                                                         standalone=True))
-                view.epoch, view.cursor = epoch + 1, 0
-            else:
-                for i in range(full):
-                    self(images[i * B:(i + 1) * B], self._labels_for(labels, i * B,
-                                                                     (i + 1) * B))
-                if tail is not None:
-                    tail(images[full * B:], self._labels_for(labels, full * B, N))
-            sums = self.acc.clone()
-            if tail is not None:
-                sums += tail.acc
-                tail.reset()
-            self.reset()
-            if self.cuda:
-                cursor, overflow = records.status()
-                written = min(cursor, out.shape[0])
-            else:
-                got = torch.cat([r for st in steps for r in st._cpu_records[1]])
-                written = min(N, out.shape[0])
-                out[:written].copy_(got[:written])
-                overflow = N > out.shape[0]
-                if labelled and ncls:
-                    confusion = confusion_of(out[:written], ncls)
-        finally:
-            if self.cuda:
-                records.off()
-            else:
-                for st in steps:
-                    st._cpu_records = None
-        rows = out[:written]
-        res = {"records": rows, "confusion": confusion, "means": means(sums),
-               "rows": written, "overflow": overflow}
+        sums, tail_sums, got = self._walk(split, images, labels, (
+            out, "records", ops.EvalRecords,
+            lambda res, image, label: records_host(res, image, label, labelled),
+            (confusion, labelled)))
+        if tail_sums is not None:
+            sums += tail_sums
+        rows = out[:got["rows"]]
+        if not self.cuda and labelled and ncls:
+            confusion = confusion_of(rows, ncls)
+        res = {"records": rows, "confusion": confusion, "means": means(sums), **got}
         for name, j in RECORD_COLUMNS.items():
             res[name] = rows[:, j]
         for name in ("label", "prior_class", "posterior_class"):

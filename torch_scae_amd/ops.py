@@ -3090,19 +3090,16 @@ class EvalEpilogue:
 
     def fused_launch(self, tail, prior, post, keep, stream_ref):
         _need_hip(prior, post)
+        # one entry point (csrc/eval_tail.hip): with records the combine workgroup writes the
+        # batch's records as well; without them it is the sink form, and without a sink the
+        # plain one
+        sink = ctypes.c_void_p(self.sink.ptr) if self.sink_written else None
+        records = None
         if self.records is not None:
-            # (the same launch: the combine workgroup writes the batch's records as well)
-            sink = ctypes.c_void_p(self.sink.ptr) if self.sink_written else None
-            _lib.call("scae_eval_tail_records_f32", *tail, _p(prior), _p(post), _p(self.acc),
-                      _p(self.batch3), sink, ctypes.c_void_p(self.records.ptr),
-                      _stream(stream_ref))
+            records = ctypes.c_void_p(self.records.ptr)
             self.records_alone = False
-        elif self.sink_written:
-            _lib.call("scae_eval_tail_sink_f32", *tail, _p(prior), _p(post), _p(self.acc),
-                      _p(self.batch3), ctypes.c_void_p(self.sink.ptr), _stream(stream_ref))
-        else:
-            _lib.call("scae_eval_tail_f32", *tail, _p(prior), _p(post), _p(self.acc),
-                      _p(self.batch3), _stream(stream_ref))
+        _lib.call("scae_eval_tail_records_f32", *tail, _p(prior), _p(post), _p(self.acc),
+                  _p(self.batch3), sink, records, _stream(stream_ref))
         self.fused, self._keep = True, (keep, prior, post)
 
     def accumulate(self, loss, out12, prior, post, label):
@@ -3118,29 +3115,28 @@ class EvalEpilogue:
         self._keep = (loss, out12, prior, post, label)
 
 
-class EvalSink:
-    """The evaluation feature sink (include/scae_hip.h, scae_eval_sink): a device descriptor
-    that captured launches reach by its address.  ``point(rows)`` aims it at an (N, 2, O)
-    fp32 output (rows [:, 0] prior presence, [:, 1] posterior mass) with the cursor at 0;
-    ``off()`` sets the capacity to 0 (nothing written, the cursor stays); ``status()`` reads
-    (cursor, overflow) in one transfer.  ``launch_alone``: the rows of a batch whose class
-    probabilities did not ride in the loss tail, and the cursor's advance."""
+class _EvalRows:
+    """What the evaluation's row descriptors share: ``int64s`` device words that captured
+    launches reach by their address, [0] the rows' address, [1] their capacity, [2] the
+    cursor, [3] overflow.  ``point(rows, ...)`` aims it with the cursor at 0; ``off()`` sets
+    the capacity to 0 (nothing written, the cursor stays); ``status()`` reads (cursor,
+    overflow) in one transfer."""
 
-    def __init__(self, device):
-        self.desc = torch.zeros(_lib.EVAL_SINK_INT64S, device=device, dtype=torch.int64)
+    def __init__(self, device, int64s):
+        self.desc = torch.zeros(int64s, device=device, dtype=torch.int64)
         self.ptr = self.desc.data_ptr()
         self.rows = None
 
-    def point(self, rows):
-        if rows is not None:
-            if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[1] != 2 \
-                    or not rows.is_contiguous() or rows.device != self.desc.device:
-                raise ValueError("sink rows must be a contiguous (N, 2, O) fp32 tensor on "
-                                 "the sink's device")
+    def _check(self, rows, shape_ok, what):
+        if rows.dtype != torch.float32 or not shape_ok or not rows.is_contiguous() \
+                or rows.device != self.desc.device:
+            raise ValueError(what)
+
+    def _set(self, rows, *more):
+        """The descriptor aimed at ``rows`` (None: off); ``more``: the words after the four."""
         self.rows = rows
-        n = 0 if rows is None else rows.shape[0]
-        self.desc.copy_(torch.tensor([0 if rows is None else rows.data_ptr(), n, 0, 0],
-                                     dtype=torch.int64))
+        head = [0, 0] if rows is None else [rows.data_ptr(), rows.shape[0]]
+        self.desc.copy_(torch.tensor(head + [0, 0, *more], dtype=torch.int64))
 
     def off(self):
         self.point(None)
@@ -3148,6 +3144,22 @@ class EvalSink:
     def status(self):
         v = self.desc[2:4].cpu()
         return int(v[0]), bool(v[1])
+
+
+class EvalSink(_EvalRows):
+    """The evaluation feature sink (include/scae_hip.h, scae_eval_sink).  ``point(rows)`` aims
+    it at an (N, 2, O) fp32 output (rows [:, 0] prior presence, [:, 1] posterior mass).
+    ``launch_alone``: the rows of a batch whose class probabilities did not ride in the loss
+    tail, and the cursor's advance."""
+
+    def __init__(self, device):
+        super().__init__(device, _lib.EVAL_SINK_INT64S)
+
+    def point(self, rows):
+        if rows is not None:
+            self._check(rows, rows.dim() == 3 and rows.shape[1] == 2, "sink rows must be a "
+                        "contiguous (N, 2, O) fp32 tensor on the sink's device")
+        self._set(rows)
 
     def launch_alone(self, caps_presence, posterior):
         """caps_presence (B, O), posterior (B, O + 1, M) (the object decoder's full
@@ -3160,49 +3172,34 @@ class EvalSink:
         self._keep = (cp, post)
 
 
-class EvalRecords:
-    """The evaluation records (include/scae_hip.h, scae_eval_records): a device descriptor
-    that captured launches reach by its address.  ``point(rows, confusion, labelled)`` aims it
-    at an (N, 9) fp32 output and a (2, ncls, ncls) int64 matrix indexed [head, label,
-    predicted], with the cursor at 0 (``labelled=False``: the labels the step stages are
-    placeholders); ``off()`` sets the capacity to 0 (nothing written, the cursor stays);
-    ``status()`` reads (cursor, overflow) in one transfer.  ``launch_alone``: the records of a
-    batch that did not end in the fused epilogue, and the cursor's advance."""
+class EvalRecords(_EvalRows):
+    """The evaluation records (include/scae_hip.h, scae_eval_records).  ``point(rows,
+    confusion, labelled)`` aims it at an (N, 9) fp32 output and a (2, ncls, ncls) int64 matrix
+    indexed [head, label, predicted] (``labelled=False``: the labels the step stages are
+    placeholders).  ``launch_alone``: the records of a batch that did not end in the fused
+    epilogue, and the cursor's advance."""
 
     def __init__(self, device):
-        self.desc = torch.zeros(_lib.EVAL_RECORDS_INT64S, device=device, dtype=torch.int64)
-        self.ptr = self.desc.data_ptr()
-        self.rows = self.confusion = None
+        super().__init__(device, _lib.EVAL_RECORDS_INT64S)
+        self.confusion = None
 
     def point(self, rows, confusion=None, labelled=True):
         R = _lib.EVAL_RECORD_FLOATS
-        dev = self.desc.device
-        if rows is not None:
-            if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != R \
-                    or not rows.is_contiguous() or rows.device != dev:
-                raise ValueError(f"records rows must be a contiguous (N, {R}) fp32 tensor on "
-                                 "the records' device")
+        if rows is None:
+            confusion = None
+        else:
+            self._check(rows, rows.dim() == 2 and rows.shape[1] == R,
+                        f"records rows must be a contiguous (N, {R}) fp32 tensor on the "
+                        "records' device")
             if confusion is not None and (
                     confusion.dtype != torch.int64 or confusion.dim() != 3
                     or confusion.shape[0] != 2 or confusion.shape[1] != confusion.shape[2]
-                    or not confusion.is_contiguous() or confusion.device != dev):
+                    or not confusion.is_contiguous() or confusion.device != self.desc.device):
                 raise ValueError("confusion must be a contiguous (2, ncls, ncls) int64 tensor "
                                  "on the records' device")
-        else:
-            confusion = None
-        self.rows, self.confusion = rows, confusion
-        self.desc.copy_(torch.tensor(
-            [0 if rows is None else rows.data_ptr(), 0 if rows is None else rows.shape[0], 0, 0,
-             0 if confusion is None else confusion.data_ptr(),
-             0 if confusion is None else confusion.shape[1], int(bool(labelled))],
-            dtype=torch.int64))
-
-    def off(self):
-        self.point(None)
-
-    def status(self):
-        v = self.desc[2:4].cpu()
-        return int(v[0]), bool(v[1])
+        self.confusion = confusion
+        self._set(rows, 0 if confusion is None else confusion.data_ptr(),
+                  0 if confusion is None else confusion.shape[1], int(bool(labelled)))
 
     def launch_alone(self, prior, post, label, lpp, rec_sums=None, rec_pixels=None):
         """prior / post (B, ncls) or None, label (B) int64 or None, lpp (B, M), and the
