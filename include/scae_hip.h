@@ -486,6 +486,16 @@ int scae_mlp_chain_votes_fwd_f32(const scae_mlp_chain_desc *desc, const scae_vot
                                  void *stream);
 int scae_mlp_chain_votes_bwd_f32(const scae_mlp_chain_desc *desc, const scae_votes_desc *votes,
                                  void *stream);
+/* The form the launchers above take for these descriptors (`votes` nullable: the plain
+ * chain; bwd != 0: the backward launchers); launches nothing.  rows: batch rows per
+ * workgroup, 16 | 32; narrow: each LDS activation buffer is as wide as what it holds, not
+ * both as wide as the widest layer; scratch_in_weights: the vote blocks take their LDS
+ * scratch in the weight tiles, not in an activation buffer. */
+typedef struct scae_mlp_chain_form {
+  int rows, narrow, scratch_in_weights;
+} scae_mlp_chain_form;
+int scae_mlp_chain_get_form(const scae_mlp_chain_desc *desc, const scae_votes_desc *votes, int bwd,
+                            scae_mlp_chain_form *form);
 
 /* bf16-operand forms of the GEMM-shaped launchers (BASELINE.json configs[2], "bs=1024
  * bf16"): same arguments, same fp32 tensors in memory; the operands are rounded to bf16

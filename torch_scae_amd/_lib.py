@@ -83,6 +83,12 @@ class VotesDesc(Structure):
                           "gall_param", "gcpr_in", "gall_param_gated")]
 
 
+class MlpChainForm(Structure):
+    """struct scae_mlp_chain_form"""
+    _fields_ = [("rows", c_int), ("narrow", c_int),
+                ("scratch_in_weights", c_int)]
+
+
 class SumSegment(Structure):
     """struct scae_sum_segment"""
     _fields_ = [("dst", P), ("begin", c_int64), ("end", c_int64),
@@ -267,6 +273,8 @@ SIGNATURES = {
     "scae_mlp_chain_bwd_f32": [POINTER(MlpChainDesc), P],
     "scae_mlp_chain_votes_fwd_f32": [POINTER(MlpChainDesc), POINTER(VotesDesc), P],
     "scae_mlp_chain_votes_bwd_f32": [POINTER(MlpChainDesc), POINTER(VotesDesc), P],
+    "scae_mlp_chain_get_form": [POINTER(MlpChainDesc), POINTER(VotesDesc), c_int,
+                                POINTER(MlpChainForm)],
     "scae_gemm_pair_bf16": [POINTER(GemmDesc), POINTER(GemmDesc), P],
     "scae_conv3x3_wf_floats": [c_int, c_int],
     "scae_conv3x3_relayout_f32": [P, P, P, c_int, c_int, P],

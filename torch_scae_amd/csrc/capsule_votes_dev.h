@@ -174,7 +174,9 @@ __device__ __forceinline__ void fwd_block(const VoteArgs &a, const VoteOut &w, c
 // Backward for the same 16 capsules: all_param rows from global memory (a.all_param), the
 // gradient rows into LDS at grows[i * ld] -- the gated ones when gall_gated is set, which is
 // what the data-gradient chain behind it consumes -- and to global memory (gall,
-// gall_gated, gcpr_in).  `red`: 16 * V * 7 floats of LDS scratch.  Ends with a barrier.
+// gall_gated, gcpr_in).  `red`: max(16 * V * 7, 127) floats of LDS scratch (the per-capsule sums
+// land at red[i * 8 + k]: past 16 * V * 7 at V = 1; both places the launcher hands out hold
+// more).  Ends with a barrier.
 template <int NTH>
 __device__ __forceinline__ void bwd_block(const VoteArgs &a, const VoteGrads &w, float *grows,
                                           int ld, float *red, int b0, int o) {

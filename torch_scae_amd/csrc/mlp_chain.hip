@@ -431,21 +431,22 @@ int launch_rb(const Chain &c, void *stream) {
   return c.bf16 ? launch_rb_bf<BWD, RBT, true>(c, stream) : launch_rb_bf<BWD, RBT, false>(c, stream);
 }
 
-template <bool BWD>
-int launch(const scae_mlp_chain_desc *d, const scae_votes_desc *v, void *stream) {
-  Chain c{};
-  int rc = fill(c, d, BWD, v);
-  if (rc) return rc;
+// The form a chain is launched in: batch rows per workgroup, whether each activation buffer
+// is as wide as what it holds (`narrow`: the strides of c2) or both as wide as the widest
+// layer, and with it where the vote blocks take their scratch (narrow: the weight tiles; else
+// activation buffer 1 / the buffer the last layer did not write).
+struct Form {
+  int rows, narrow;
+};
+Form choose_form(const Chain &c, bool bwd, int want, Chain &c2) {
   // Large batches: 32 rows per workgroup.  Buffer 0 holds the input block and the outputs
   // of the odd layers (the last layer's only when the vote kernel reads it from LDS),
   // buffer 1 the even layers' -- each as wide as what it holds; the vote blocks take their
   // scratch in the weight tiles.
-  const int want = d->row_tile;   // (16 | 32: a forced row tile -- tests, measurements; 0: by shape)
-  if (want != 0 && want != 16 && want != 32) return SCAE_ERR_BAD_ARG;
-  Chain c2 = c;
+  c2 = c;
   int dim[2] = {c.in_dim, 16};
   for (int i = 0; i < c.n; ++i)
-    if (i + 1 < c.n || (!BWD && c.votes)) dim[(i + 1) & 1] = dim[(i + 1) & 1] > c.l[i].N ? dim[(i + 1) & 1] : c.l[i].N;
+    if (i + 1 < c.n || (!bwd && c.votes)) dim[(i + 1) & 1] = dim[(i + 1) & 1] > c.l[i].N ? dim[(i + 1) & 1] : c.l[i].N;
   c2.stride[0] = ((dim[0] + 15) & ~15) + 4, c2.stride[1] = ((dim[1] + 15) & ~15) + 4;
   const size_t lds2 = ((size_t)32 * (c2.stride[0] + c2.stride[1]) + (size_t)NW * 16 * WLD) * sizeof(float);
   const bool scratch_ok = !c.votes || (size_t)16 * c.va.V * 7 <= (size_t)NW * 16 * WLD;
@@ -459,9 +460,22 @@ int launch(const scae_mlp_chain_desc *d, const scae_votes_desc *v, void *stream)
   const size_t lds1n = ((size_t)16 * (c2.stride[0] + c2.stride[1]) + (size_t)NW * 16 * WLD) * sizeof(float);
   const bool narrow16 = scratch_ok && lds1 > 80 * 1024 && lds1n <= 80 * 1024;
   if (lds2 <= 160 * 1024 && scratch_ok && want != 16 && (want == 32 || (big && !narrow16)))
-    return launch_rb<BWD, 2>(c2, stream);
-  if (narrow16) return launch_rb<BWD, 1>(c2, stream);
-  return launch_rb<BWD, 1>(c, stream);   // (one stride, scratch in buffer 1)
+    return Form{32, 1};
+  if (narrow16) return Form{16, 1};
+  return Form{16, 0};   // (one stride, scratch in buffer 1)
+}
+
+template <bool BWD>
+int launch(const scae_mlp_chain_desc *d, const scae_votes_desc *v, void *stream) {
+  Chain c{};
+  int rc = fill(c, d, BWD, v);
+  if (rc) return rc;
+  const int want = d->row_tile;   // (16 | 32: a forced row tile -- tests, measurements; 0: by shape)
+  if (want != 0 && want != 16 && want != 32) return SCAE_ERR_BAD_ARG;
+  Chain c2;
+  const Form f = choose_form(c, BWD, want, c2);
+  if (f.rows == 32) return launch_rb<BWD, 2>(c2, stream);
+  return launch_rb<BWD, 1>(f.narrow ? c2 : c, stream);
 }
 }  // namespace
 
@@ -473,6 +487,20 @@ extern "C" int scae_mlp_chain_fwd_f32(const scae_mlp_chain_desc *desc, void *str
 }
 extern "C" int scae_mlp_chain_bwd_f32(const scae_mlp_chain_desc *desc, void *stream) {
   return launch<true>(desc, nullptr, stream);
+}
+extern "C" int scae_mlp_chain_get_form(const scae_mlp_chain_desc *desc, const scae_votes_desc *votes,
+                                       int bwd, scae_mlp_chain_form *form) {
+  SCAE_REQUIRE(form);
+  Chain c{}, c2;
+  int rc = fill(c, desc, bwd != 0, votes);
+  if (rc) return rc;
+  const int want = desc->row_tile;
+  if (want != 0 && want != 16 && want != 32) return SCAE_ERR_BAD_ARG;
+  const Form f = choose_form(c, bwd != 0, want, c2);
+  form->rows = f.rows;
+  form->narrow = f.narrow;
+  form->scratch_in_weights = c.votes && f.narrow;
+  return SCAE_OK;
 }
 extern "C" int scae_mlp_chain_votes_fwd_f32(const scae_mlp_chain_desc *desc,
                                             const scae_votes_desc *votes, void *stream) {
