@@ -197,7 +197,7 @@ def kmeans(x, k, n_init=10, max_iter=300, seed=0, init="k-means++", check_every=
     part_inertia = torch.empty(R * G, device=dev, dtype=torch.float64)
     state = torch.zeros(R * _lib.KMEANS_STATE_INTS + 1, device=dev, dtype=torch.int32)
     inertia = torch.zeros(R, device=dev, dtype=torch.float64)
-    d = _lib.KMeansDesc()
+    d = _lib.KmeansDesc()
     d.x, d.N, d.F, d.k, d.R, d.G, d.max_iter = x.data_ptr(), N, F, k, R, G, max_iter
     d.centroids, d.labels = cent.data_ptr(), labels.data_ptr()
     d.part_sum, d.part_count = part_sum.data_ptr(), part_count.data_ptr()
