@@ -681,6 +681,10 @@ int scae_conv3x3_wgrad_reduce_batch_f32(int n_layers, const float *const *partia
  *   backward: g (B,A,P-1) -> dy (B,HW,A*P).
  * ---------------------------------------------------------------------- */
 int scae_attention_pool_supported(int HW, int A, int P);
+/* Host only: the capsule groups per image every K9 launcher below splits (B, A) into -- one
+ * workgroup per (image, group of A / groups capsules); 0 for B or A <= 0.  (K10's:
+ * scae_template_color_partial_rows(B, M) / B.) */
+int scae_attention_pool_groups(int B, int A);
 int scae_attention_pool_fwd_f32(const float *y, float *out, int B, int HW, int A, int P,
                                 void *stream);
 int scae_attention_pool_bwd_f32(const float *y, const float *g, float *dy, int B, int HW,

@@ -383,6 +383,11 @@ extern "C" int scae_attention_pool_supported(int HW, int A, int P) {
   return lds_floats(HW, A, P, true) * sizeof(float) <= 128 * 1024;
 }
 
+// host only: the capsule groups per image every K9 launcher splits (B, A) into
+extern "C" int scae_attention_pool_groups(int B, int A) {
+  return B > 0 && A > 0 ? pool_splits(B, A) : 0;
+}
+
 extern "C" int scae_attention_pool_fwd_f32(const float *y, float *out, int B, int HW, int A,
                                            int P, void *stream) {
   PoolArgs k{};
