@@ -39,8 +39,11 @@ extern "C" {
  * row_tile / bf16; scae_decoder_desc has bwd_resident; scae_first_layer_desc has out_h /
  * rwfh / rwdh
  * 3: launch lists record one stream -- scae_launch_list_side_stream / _order / _run2 /
- * _side_size are gone; scae_decoder_desc loses bwd_resident */
-#define SCAE_ABI_VERSION 3
+ * _side_size are gone; scae_decoder_desc loses bwd_resident
+ * 4: the library reads no environment variable -- scae_gemm_desc has form,
+ * scae_likelihood_bwd_desc has separate, scae_conv3x3_bwd_pair_forms_f32 is new and
+ * scae_conv3x3_bwd_pair_{reduce,fold}_f32 take dgrad_forms */
+#define SCAE_ABI_VERSION 4
 
 #define SCAE_OK 0
 #define SCAE_ERR_BAD_ARG (-1)      /* null pointer / non-positive size     */
@@ -356,7 +359,12 @@ typedef struct scae_gemm_desc {
   int64_t mask_batch, asum_batch;
   int relu, asum_ld;
   float *c_nomask; /* nullable, layout of C: the values before the mask gate */
+  int form;        /* 0 = chosen by the launcher from the shapes (the production setting);
+                      SCAE_GEMM_TILES forces the register-staged tiles of gemm_mfma.hip even
+                      where the wave-private K-split pipelines (gemm_ksplit.hip) would take the
+                      list (tests, measurements); anything else: SCAE_ERR_BAD_ARG */
 } scae_gemm_desc;
+#define SCAE_GEMM_TILES 1
 int scae_gemm_pair_f32(const scae_gemm_desc *first, const scae_gemm_desc *second, void *stream);
 /* Up to 4 independent GEMMs of that kind in ONE launch (the four weight-gradient
  * GEMMs of a capsule's MLP chain once the data-gradient chain has run). */
@@ -646,23 +654,37 @@ int scae_conv3x3_dgrad_f32(const float *dpre, const float *wd, const float *gate
 int scae_conv3x3_bwd_pair_f32(const float *dpre, const float *wd, const float *in, float *din,
                               float *partial, int B, int IH, int IW, int Cin, int Cout,
                               int stride, void *stream);
+/* ... with the data gradient's tile form chosen by the caller (tests, measurements).
+ * dgrad_forms is a set of the bits below; SCAE_DGRAD_BY_SHAPE is the production setting and
+ * what scae_conv3x3_bwd_pair_f32, _bf16 and scae_conv3x3_dgrad_f32 use.  SCAE_DGRAD_TILE with
+ * SCAE_DGRAD_NO_TILE, or any other bit: SCAE_ERR_BAD_ARG. */
+#define SCAE_DGRAD_BY_SHAPE 0
+#define SCAE_DGRAD_NO_TILE 1   /* never the DMA-fed 64 x 128 tile                        */
+#define SCAE_DGRAD_NO_KSPLIT 2 /* never the K-split tile                                 */
+#define SCAE_DGRAD_TILE 4      /* the DMA-fed tile wherever its shape limits hold,
+                                  whatever the tile count                                */
+int scae_conv3x3_bwd_pair_forms_f32(const float *dpre, const float *wd, const float *in,
+                                    float *din, float *partial, int B, int IH, int IW, int Cin,
+                                    int Cout, int stride, int dgrad_forms, void *stream);
 /* scae_conv3x3_bwd_pair_f32 with the workgroups of scae_seed_fold_bwd_f32(fold, fold_grads) as
  * the head of its grid: the folding products' backward writes parameter gradients only, so in
  * a training step it may wait for this launch (256-thread workgroups, tens of microseconds
  * of MFMA tiles to hide behind).  Same results, bit for bit, as the launch of its own.
  * scae_conv3x3_bwd_pair_reduce_f32: the same for scae_seed_attention_mfma_reduce_f32
  * (arguments rpartial .. C), whose outputs only the folding products' backward reads.
- * SCAE_ERR_UNSUPPORTED (folding width != 256, another tile form of the pair): launch both. */
+ * SCAE_ERR_UNSUPPORTED (folding width != 256, another tile form of the pair): launch both.
+ * dgrad_forms: as for scae_conv3x3_bwd_pair_forms_f32 (0 in production; tests, measurements). */
 int scae_conv3x3_bwd_pair_reduce_f32(const float *dpre, const float *wd, const float *in,
                                      float *din, float *partial, int B, int IH, int IW, int Cin,
                                      int Cout, int stride, const float *rpartial, int rows,
                                      const float *q, const float *wk, float *gq, float *gwk,
                                      float *gbk, float *gwv, float *gbv, int O, int C,
-                                     void *stream);
+                                     int dgrad_forms, void *stream);
 int scae_conv3x3_bwd_pair_fold_f32(const float *dpre, const float *wd, const float *in,
                                    float *din, float *partial, int B, int IH, int IW, int Cin,
                                    int Cout, int stride, const scae_seed_fold_desc *fold,
-                                   const scae_seed_fold_grads *fold_grads, void *stream);
+                                   const scae_seed_fold_grads *fold_grads, int dgrad_forms,
+                                   void *stream);
 int scae_conv3x3_wgrad_splits(int B, int OH, int OW, int Cin, int Cout);
 int scae_conv3x3_wgrad_f32(const float *dpre, const float *in, float *partial, float *dw,
                            float *db, int B, int IH, int IW, int Cin, int Cout, int stride,
@@ -1723,6 +1745,8 @@ typedef struct scae_likelihood_bwd_desc {
       *g_posterior, *g_mixing_log_prob, *g_mixing_logit;
   float *gvote, *gscale, *gvote_presence, *gx, *gpresence, *gdummy_partial;
   int B, O, M;
+  int separate; /* 0 = one launch where the shapes fit (the production setting); != 0 forces
+                   the two launches (tests, measurements) */
 } scae_likelihood_bwd_desc;
 int scae_render_gmm_sums_bwd_likelihood_f32(
     const scae_decoder_desc *d, const float *x, const float *lse_post, const float *lse_prior,

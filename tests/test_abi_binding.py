@@ -222,7 +222,7 @@ def test_public_names():
 def test_launchers_end_in_a_stream():
     protos = _lib.ABI.prototypes
     launchers = {n for n, p in protos.items() if _lib._is_launcher(p)}
-    assert len(launchers) == 149
+    assert len(launchers) == 150
     # host queries that end in an address, and the launch lists' own entry points, are none
     for name in ("scae_render_gmm_forms", "scae_render_gmm_parts_geometry",
                  "scae_mlp_chain_get_form", "scae_launch_list_run", "scae_launch_list_begin",

@@ -13,7 +13,7 @@ csrc/render_bwd_likelihood.hip): its group sums are 16- and 4-lane whatever the 
 so it must equal the 1024-thread launch bit for bit.  test_timed_path.py
 ``test_likelihood_riding_in_the_trunk_launch_changes_nothing`` pins that at cfg-2 (O = M = 24:
 M * 16 = 384, no multiple of 256); here the shape where it is one (M = 16), with the ride
-switched off by SCAE_FUSE_K1_K4_BWD=0 as the only difference, and the launch count to show
+switched off by scae_likelihood_bwd_desc.separate as the only difference, and the launch count to show
 that the ride was taken.
 
 Run with -s: each check prints its worst ratio against the bar."""
@@ -275,8 +275,8 @@ def test_backward_riding_in_the_decoder_launch_equals_its_own_launch_bitwise(mon
     """A medium-config TrainStep with an encoder-fed decoder and 16 part capsules
     (M * 16 = 256: every pass of the 256-thread loops is full; O = 6): K4's backward as the
     first block range of scae_render_gmm_sums_bwd_likelihood_f32's launch (256 threads)
-    against the same entry point splitting into its two launches (SCAE_FUSE_K1_K4_BWD=0:
-    K4 on 1024 threads) and against fuse_kernels off -- the likelihood's four incoming
+    against the same entry point splitting into its two launches (ops._K1_K4_SEPARATE, the
+    descriptor's ``separate``: K4 on 1024 threads) and against fuse_kernels off -- the likelihood's four incoming
     gradients (log_prob_per_point, posterior, mixing_log_prob, mixing_logit) and all that
     follows from them, bit for bit in every parameter gradient."""
     from tests.test_step_plan import _eager_step, _filled_state, _flat_grads, _medium_cfg
@@ -289,10 +289,7 @@ def test_backward_riding_in_the_decoder_launch_equals_its_own_launch_bitwise(mon
     lib = _lib.load()
     runs = {}
     for mode in ("ride", "split", "unfused"):
-        if mode == "split":
-            monkeypatch.setenv("SCAE_FUSE_K1_K4_BWD", "0")
-        else:
-            monkeypatch.delenv("SCAE_FUSE_K1_K4_BWD", raising=False)
+        monkeypatch.setattr(ops, "_K1_K4_SEPARATE", mode == "split")
         torch.manual_seed(99)       # (the noise streams: the same draws in every run)
         ops.reset_noise()
         model, step = _eager_step(cfg, sd, B, fuse_kernels=mode != "unfused")
@@ -315,7 +312,7 @@ def test_backward_riding_in_the_decoder_launch_equals_its_own_launch_bitwise(mon
         lib.scae_launch_list_free(P(lst))
         runs[mode] = (float(loss), {k: v.detach().clone() for k, v in _flat_grads(step).items()},
                       calls, n)
-    monkeypatch.delenv("SCAE_FUSE_K1_K4_BWD", raising=False)
+    monkeypatch.setattr(ops, "_K1_K4_SEPARATE", False)
     assert "scae_render_gmm_sums_bwd_likelihood_f32" in runs["ride"][2]
     assert "scae_render_gmm_sums_bwd_likelihood_f32" in runs["split"][2]
     assert "scae_capsule_likelihood_bwd_f32" in runs["unfused"][2]

@@ -1215,11 +1215,11 @@ def test_conv_stack_vs_conv2d(B, C0, HW, chans, strides):
     (130, 5, 5, 128, 128, 1),     # the smallest layer: one-pixel classes
 ])
 @pytest.mark.parametrize("form", ["tile", "ksplit"])
-def test_conv_data_gradient_dma_tile_vs_fp64(B, IH, IW, Ci, Co, stride, form, monkeypatch):
+def test_conv_data_gradient_dma_tile_vs_fp64(B, IH, IW, Ci, Co, stride, form):
     """The DMA-fed data-gradient tiles of the pair launch (conv_mfma.hip; fp32 rows by LDS-DMA,
     six exact bf16 products per fragment pair) forced onto shapes of every tap-class structure
-    -- "tile": DMODE 4, 64 x 128, SCAE_K8_DGX=1 (any layer takes it); "ksplit": DMODE 5, 32 x 64
-    with the K loop split over the waves, SCAE_K8_DGK=1 --: the gated input gradient against
+    -- "tile": DMODE 4, 64 x 128, SCAE_DGRAD_TILE (any layer takes it); "ksplit": DMODE 5, 32 x 64
+    with the K loop split over the waves, SCAE_DGRAD_NO_TILE alone --: the gated input gradient against
     conv2d in fp64 at 2e-6 of its largest entry, and against the first-generation tiles of the
     same launch; the weight-gradient partials of the launch are the same bits either way
     ("ksplit": to round-off -- its launch always takes the 32-pixel ring)."""
@@ -1238,13 +1238,13 @@ def test_conv_data_gradient_dma_tile_vs_fp64(B, IH, IW, Ci, Co, stride, form, mo
     dpre = torch.randn(B, OH, OW, Co, generator=g).cuda()
     splits = lib.scae_conv3x3_wgrad_splits(B, OH, OW, Ci, Co)
     outs = {}
-    for mode in ("1", "0"):
-        monkeypatch.setenv("SCAE_K8_DGX", mode if form == "tile" else "0")
-        monkeypatch.setenv("SCAE_K8_DGK", mode if form == "ksplit" else "0")
+    forced = _lib.DGRAD_TILE | _lib.DGRAD_NO_KSPLIT if form == "tile" else _lib.DGRAD_NO_TILE
+    for mode, forms in (("1", forced), ("0", _lib.DGRAD_NO_TILE | _lib.DGRAD_NO_KSPLIT)):
         din = torch.full((B, IH, IW, Ci), 7.0, device="cuda")
         part = torch.full((splits * (9 * Co * Ci + Co),), 3.0, device="cuda")
-        _lib.call("scae_conv3x3_bwd_pair_f32", P(dpre.data_ptr()), P(wd.data_ptr()),
-                  P(x.data_ptr()), P(din.data_ptr()), P(part.data_ptr()), B, IH, IW, Ci, Co, s, st)
+        _lib.call("scae_conv3x3_bwd_pair_forms_f32", P(dpre.data_ptr()), P(wd.data_ptr()),
+                  P(x.data_ptr()), P(din.data_ptr()), P(part.data_ptr()), B, IH, IW, Ci, Co, s,
+                  forms, st)
         torch.cuda.synchronize()
         outs[mode] = (din, part)
     xr = x.double().permute(0, 3, 1, 2).cpu().requires_grad_(True)
@@ -1504,7 +1504,7 @@ def test_conv_backward_carrying_reduce_and_fold_backward_equals_separate_launche
                 red = (ops._p(partial_rows), rows, ops._p(q), ops._p(wk),
                        *[ops._p(t) for t in red_out], O, C)
                 if carried:
-                    _lib.call("scae_conv3x3_bwd_pair_reduce_f32", *pair, *red, st)
+                    _lib.call("scae_conv3x3_bwd_pair_reduce_f32", *pair, *red, 0, st)
                 else:
                     _lib.call("scae_conv3x3_bwd_pair_f32", *pair, st)
                     _lib.call("scae_seed_attention_mfma_reduce_f32", *red, st)
@@ -1520,7 +1520,7 @@ def test_conv_backward_carrying_reduce_and_fold_backward_equals_separate_launche
                     setattr(gr, "d_" + name, t.data_ptr())
                 if carried:
                     _lib.call("scae_conv3x3_bwd_pair_fold_f32", *pair,
-                              ctypes.byref(desc), ctypes.byref(gr), st)
+                              ctypes.byref(desc), ctypes.byref(gr), 0, st)
                 else:
                     _lib.call("scae_conv3x3_bwd_pair_f32", *pair, st)
                     _lib.call("scae_seed_fold_bwd_f32", ctypes.byref(desc),
@@ -2836,12 +2836,12 @@ def test_conv_bf16_resident_kernels_vs_fp64(B, IH, IW, stride):
     (32, 25, 64, 128, 8),       # a ragged last K chunk of the k-strided pair (K = 200)
     (64, 9, 128, 160, 32),      # five K chunks: waves with one and with two
 ])
-def test_gemm_pair_on_wave_private_pipelines_vs_fp64(B, HW, C, AP, gsz, monkeypatch):
+def test_gemm_pair_on_wave_private_pipelines_vs_fp64(B, HW, C, AP, gsz):
     """csrc/gemm_ksplit.hip through scae_gemm_pair_f32: the backward of the 1 x 1 attention
     convolution -- dx = dy W with the ReLU gate and the ungated copy (A k-contiguous), dW per
     group of images = dy^T x with its bias sums (both operands k-strided, batch > 1) -- against
     fp64 at 2e-6 of each result's largest entry, and against the register-staged tiles
-    (SCAE_GEMM_KSPLIT=0).  The fast form must actually take these shapes: the two runs differ
+    (form = SCAE_GEMM_TILES).  The fast form must actually take these shapes: the two runs differ
     somewhere in the last bits."""
     import ctypes
     from torch_scae_amd import _lib, ops
@@ -2853,7 +2853,6 @@ def test_gemm_pair_on_wave_private_pipelines_vs_fp64(B, HW, C, AP, gsz, monkeypa
     dy = torch.randn(B, HW, AP, generator=g).cuda()
     outs = {}
     for mode in ("1", "0"):
-        monkeypatch.setenv("SCAE_GEMM_KSPLIT", mode)
         part = torch.full((S, slab), 7.0, device="cuda")
         dx, raw = torch.full_like(x, 7.0), torch.full_like(x, 7.0)
         dgrad = ops._gemm_desc(ops._p(dy), ops._p(w), ops._p(dx), 1, B * HW, C, AP, True, AP, 0,
@@ -2862,6 +2861,7 @@ def test_gemm_pair_on_wave_private_pipelines_vs_fp64(B, HW, C, AP, gsz, monkeypa
         wgrad = ops._gemm_desc(ops._p(dy), ops._p(x), ops._p(part), S, AP, C, kper, False, AP,
                                kper * AP, False, C, kper * C, C, slab,
                                asum=ops._off(part, AP * C), asum_b=slab)
+        wgrad.form = dgrad.form = 0 if mode == "1" else _lib.GEMM_TILES
         ops._gemm_pair(wgrad, dgrad, x)
         torch.cuda.synchronize()
         outs[mode] = (dx, raw, part)

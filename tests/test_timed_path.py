@@ -510,26 +510,27 @@ def test_replayed_step_equals_eager_step_bitwise():
         assert torch.equal(s0[k], s1[k]), k
 
 
-@pytest.mark.parametrize("knob,off,on,may_differ", [
-    ("SCAE_K8_DGX", "0", "500", ("part_encoder.encoder.network.0.",)),
-    ("SCAE_K8_DGK", "0", "1", ("part_encoder.encoder.network.",)),
-])
-def test_dma_data_gradient_tiles_change_only_the_encoders_gradients(knob, off, on, may_differ,
-                                                                   monkeypatch):
+@pytest.mark.parametrize("off,may_differ", [
+    ("NO_TILE", ("part_encoder.encoder.network.0.",)),
+    ("NO_KSPLIT", ("part_encoder.encoder.network.",)),
+], ids=["NO_TILE", "NO_KSPLIT"])
+def test_dma_data_gradient_tiles_change_only_the_encoders_gradients(off, may_differ, monkeypatch):
     """The replayed cfg-2 step with a convolution layer's data gradient on a DMA-fed tile
     (conv_mfma.hip; DMODE 4 for the second layer, the default for a layer of >= 500 such tiles;
     DMODE 5, the K loop split over the waves, for the third and fourth) and on the
-    first-generation tiles (SCAE_K8_DGX=0 / SCAE_K8_DGK=0): same state, noise and batch.  A
-    data gradient only feeds the layers below it (and DMODE 5's launch sums its weight-gradient
-    partials in other groups), so the loss and every gradient outside the convolution stack --
-    the riders of the same launches included -- are the same bits, and the stack's own agree to
-    round-off: nothing else is touched."""
+    first-generation tiles (ops._K8_DGRAD_FORMS = SCAE_DGRAD_NO_TILE / SCAE_DGRAD_NO_KSPLIT):
+    same state, noise and batch.  A data gradient only feeds the layers below it (and DMODE 5's
+    launch sums its weight-gradient partials in other groups), so the loss and every gradient
+    outside the convolution stack -- the riders of the same launches included -- are the same
+    bits, and the stack's own agree to round-off: nothing else is touched."""
+    from torch_scae_amd import _lib, ops
+    off, on = getattr(_lib, "DGRAD_" + off), 0
     cfg, B, sd, g = full_size_params("cfg2")
     images = torch.rand(1, B, *cfg["image_shape"], generator=g).cuda()
     labels = torch.randint(0, 10, (1, B), generator=g).cuda()
     out = {}
     for mode in (off, on):
-        monkeypatch.setenv(knob, mode)
+        monkeypatch.setattr(ops, "_K8_DGRAD_FORMS", mode)
         model, step = build_step(cfg, B, sd)
         step.capture()
         _set_counter(step, 1000)

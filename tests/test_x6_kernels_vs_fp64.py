@@ -15,15 +15,17 @@ MFMA adds two of them.  Both sides are made sparse in turn: the filter (K8r's is
 Forms and how each is reached (conv_mfma.hip ``plan_dgrad`` / ``conv_bwd_pair_impl``,
 restated by ``x6_emulate.dgrad_mode`` and asserted there):
   * forward: conv_fwd_pipe_kernel<PipeC2> is the only fp32 form of scae_conv3x3_fwd_f32;
-  * data gradient: DMODE 4 where (Cin/128) x 64-pixel tiles >= SCAE_K8_DGX (500; forced
-    with SCAE_K8_DGX=1), else DMODE 5 (SCAE_K8_DGK, default on), else the first-generation
+  * data gradient: DMODE 4 where (Cin/128) x 64-pixel tiles >= 500 (forced by SCAE_DGRAD_TILE
+    in scae_conv3x3_bwd_pair_forms_f32's dgrad_forms, barred by SCAE_DGRAD_NO_TILE), else
+    DMODE 5 (barred by SCAE_DGRAD_NO_KSPLIT), else the first-generation
     tiles on fp32 MFMAs (v_mfma_f32_16x16x4_f32, mfma_tile.h): DMODE 0 when (Cin/64) x
     64-pixel tiles >= 1024, DMODE 2 when (Cin/64) x 32-pixel tiles >= 600, else DMODE 1;
   * weight gradient: scae_conv3x3_wgrad_f32 always takes PipeW (32-pixel ring); inside the
     pair launch PipeW16 (16-pixel ring) when the data gradient is not DMODE 5 and
     B*OH*OW < SCAE_WGRAD_SHORT_CHUNK_PIXELS (8192), else PipeW;
-  * gemm_ksplit.hip (x6k) under SCAE_GEMM_KSPLIT=1, gemm_mfma.hip's fp32 tiles under =0.
-Where a knob switches the form, the two runs must differ in their bits.
+  * gemm_ksplit.hip (x6k) by shape (scae_gemm_desc.form = 0), gemm_mfma.hip's fp32 tiles
+    with form = SCAE_GEMM_TILES.
+Where a selector switches the form, the two runs must differ in their bits.
 fwd_fold, bwd_pair_reduce and bwd_pair_fold equal separate launches bit for bit
 (test_hip_ops.py), so the rows here cover them.
 """
@@ -217,19 +219,19 @@ def _check_partials(part, t, dpre, splits, Co, Ci, what):
 
 
 PAIR = [
-    # form, B, IH, IW, Ci, Co, stride, knobs
-    ("DMODE 0 + PipeW16", 48, 19, 19, 256, 64, 2, {"SCAE_K8_DGX": "0", "SCAE_K8_DGK": "0"}),
-    ("DMODE 2 + PipeW16 (cfg-2 layer 3)", 128, 9, 9, 128, 128, 1, {"SCAE_K8_DGK": "0"}),
-    ("DMODE 1 + PipeW16 (cfg-2 layer 4)", 128, 7, 7, 128, 128, 1, {"SCAE_K8_DGK": "0"}),
-    ("DMODE 4 + PipeW16", 3, 9, 11, 128, 64, 2, {"SCAE_K8_DGX": "1"}),
-    ("DMODE 5 + PipeW", 2, 10, 12, 256, 64, 2, {}),
+    # form, B, IH, IW, Ci, Co, stride, dgrad_forms
+    ("DMODE 0 + PipeW16", 48, 19, 19, 256, 64, 2, E.NO_TILE | E.NO_KSPLIT),
+    ("DMODE 2 + PipeW16 (cfg-2 layer 3)", 128, 9, 9, 128, 128, 1, E.NO_KSPLIT),
+    ("DMODE 1 + PipeW16 (cfg-2 layer 4)", 128, 7, 7, 128, 128, 1, E.NO_KSPLIT),
+    ("DMODE 4 + PipeW16", 3, 9, 11, 128, 64, 2, E.TILE),
+    ("DMODE 5 + PipeW", 2, 10, 12, 256, 64, 2, 0),
 ]
 
 
-@pytest.mark.parametrize("form,B,IH,IW,Ci,Co,s,knobs", PAIR, ids=[p[0] for p in PAIR])
+@pytest.mark.parametrize("form,B,IH,IW,Ci,Co,s,forms", PAIR, ids=[p[0] for p in PAIR])
 @pytest.mark.parametrize("side", ["dpre", "input"])
-def test_conv_backward_pair_vs_fp64(form, B, IH, IW, Ci, Co, s, knobs, side, monkeypatch):
-    """scae_conv3x3_bwd_pair_f32: the gated input gradient (gate = the input > 0) and the
+def test_conv_backward_pair_vs_fp64(form, B, IH, IW, Ci, Co, s, forms, side):
+    """scae_conv3x3_bwd_pair_forms_f32: the gated input gradient (gate = the input > 0) and the
     weight-gradient partials.  side 'dpre': the pre-activation gradient sparse (both passes'
     premise), the input positive (gate open everywhere) -- and one shape with a signed input
     (a gate); side 'input': the input sparse and positive, dpre dense: the partials only (the
@@ -238,8 +240,9 @@ def test_conv_backward_pair_vs_fp64(form, B, IH, IW, Ci, Co, s, knobs, side, mon
     lib = _lib.load()
     OH, OW = (IH - 3) // s + 1, (IW - 3) // s + 1
     M = B * OH * OW
-    dg = dict(dgx=int(knobs.get("SCAE_K8_DGX", 500)), dgk=int(knobs.get("SCAE_K8_DGK", 1)))
-    mode = E.dgrad_mode(B, IH, IW, Ci, Co, s, pair=True, **dg)
+    assert (E.NO_TILE, E.NO_KSPLIT, E.TILE) == (_lib.DGRAD_NO_TILE, _lib.DGRAD_NO_KSPLIT,
+                                                _lib.DGRAD_TILE)
+    mode = E.dgrad_mode(B, IH, IW, Ci, Co, s, pair=True, forms=forms)
     assert f"DMODE {mode} " in form + " "
     w16 = mode != 5 and M < 8192
     assert ("PipeW16" in form) == w16
@@ -259,20 +262,16 @@ def test_conv_backward_pair_vs_fp64(form, B, IH, IW, Ci, Co, s, knobs, side, mon
     xd, dd = _dev(x), _dev(dpre)
     outs = {}
     # the other run: the first-generation tiles (DMODE 4 / 5), or the default form (0 - 2)
-    alt = {"SCAE_K8_DGX": "0", "SCAE_K8_DGK": "0"} if mode >= 4 else {}
-    for run, env in (("form", knobs), ("other", alt)):
-        for k in ("SCAE_K8_DGX", "SCAE_K8_DGK"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+    alt = E.NO_TILE | E.NO_KSPLIT if mode >= 4 else 0
+    for run, dgrad_forms in (("form", forms), ("other", alt)):
         din = torch.full((B * IH * IW + 5, Ci), SENT, device="cuda")
         part = torch.full((splits * (9 * Co * Ci + Co) + 5,), SENT, device="cuda")
-        _call("scae_conv3x3_bwd_pair_f32", _p(dd), _p(wd), _p(xd), _p(din), _p(part),
-              B, IH, IW, Ci, Co, s, _st())
+        _call("scae_conv3x3_bwd_pair_forms_f32", _p(dd), _p(wd), _p(xd), _p(din), _p(part),
+              B, IH, IW, Ci, Co, s, dgrad_forms, _st())
         torch.cuda.synchronize()
         assert bool((din[-5:] == SENT).all()) and bool((part[-5:] == SENT).all())
         outs[run] = (din, part)
-    assert not torch.equal(outs["form"][0], outs["other"][0])   # the knob switched the form
+    assert not torch.equal(outs["form"][0], outs["other"][0])   # the selector switched the form
     din, part = outs["form"]
     if side == "dpre":
         t = E.kind_terms(E.op_dgrad(s, (IH, IW)), dpre, w, fp32=mode < 4)
@@ -287,7 +286,7 @@ def test_conv_backward_pair_vs_fp64(form, B, IH, IW, Ci, Co, s, knobs, side, mon
 @pytest.mark.parametrize("side,gate", [("filter", False), ("dpre", False), ("filter", True)])
 def test_conv_dgrad_standalone_vs_fp64(side, gate):
     """scae_conv3x3_dgrad_f32 in its default form at this shape (DMODE 5: 50 tiles of 64 x 128
-    < SCAE_K8_DGX, SCAE_K8_DGK on), with the sparse filter (Wd rows) and the sparse dpre, and
+    < 500), with the sparse filter (Wd rows) and the sparse dpre, and
     one run with a gate."""
     B, IH, IW, Ci, Co, s = 2, 9, 9, 128, 128, 1
     assert E.dgrad_mode(B, IH, IW, Ci, Co, s, pair=False) == 5
@@ -396,14 +395,14 @@ def test_conv_first_layer_vs_fp64(C0, s):
     (64, 9, 128, 160, 32),      # five K chunks: waves with one and with two
 ])
 @pytest.mark.parametrize("side", ["dy", "operands"])
-def test_gemm_pair_x6k_and_fp32_tiles_vs_fp64(B, HW, C, AP, gsz, side, monkeypatch):
+def test_gemm_pair_x6k_and_fp32_tiles_vs_fp64(B, HW, C, AP, gsz, side):
     """scae_gemm_pair_f32 on the 1 x 1 attention convolution's backward: dx = dy W gated (+ the
-    ungated copy), dW per group = dy^T x (+ bias sums) -- x6k (SCAE_GEMM_KSPLIT=1: four
+    ungated copy), dW per group = dy^T x (+ bias sums) -- x6k (form = 0, mode "1": four
     wave-private pipelines summed in LDS, x = 3) against the kind sum, gemm_mfma.hip's fp32
-    tiles (=0) against the exact product; the two differ in their bits.  side 'dy': dy sparse
+    tiles (form = SCAE_GEMM_TILES, mode "0") against the exact product; the two differ in their bits.  side 'dy': dy sparse
     (one term per row, 1 .. 4 per column in different 32-row blocks); 'operands': W and x
     sparse, dy dense."""
-    from torch_scae_amd import ops
+    from torch_scae_amd import _lib, ops
     g = torch.Generator().manual_seed(B + HW + (side == "dy"))
     S, kper, slab = B // gsz, HW * gsz, AP * C + AP
     if side == "dy":
@@ -417,7 +416,6 @@ def test_gemm_pair_x6k_and_fp32_tiles_vs_fp64(B, HW, C, AP, gsz, side, monkeypat
     d_dy, d_w, d_x, d_g = _dev(dy), _dev(w), _dev(x), _dev(gate)
     outs = {}
     for mode in ("1", "0"):
-        monkeypatch.setenv("SCAE_GEMM_KSPLIT", mode)
         part = torch.full((S * slab + 5,), SENT, device="cuda")
         dx = torch.full((B * HW * C + 5,), SENT, device="cuda")
         raw = torch.full((B * HW * C + 5,), SENT, device="cuda")
@@ -427,6 +425,7 @@ def test_gemm_pair_x6k_and_fp32_tiles_vs_fp64(B, HW, C, AP, gsz, side, monkeypat
         wgrad = ops._gemm_desc(ops._p(d_dy), ops._p(d_x), ops._p(part), S, AP, C, kper, False,
                                AP, kper * AP, False, C, kper * C, C, slab,
                                asum=ops._off(part, AP * C), asum_b=slab)
+        wgrad.form = dgrad.form = 0 if mode == "1" else _lib.GEMM_TILES
         ops._gemm_pair(wgrad, dgrad, d_x)
         torch.cuda.synchronize()
         for t in (part, dx, raw):
@@ -452,10 +451,10 @@ def test_gemm_pair_x6k_and_fp32_tiles_vs_fp64(B, HW, C, AP, gsz, side, monkeypat
 
 
 @pytest.mark.parametrize("nprob", [1, 3, 4])
-def test_gemm_multi_x6k_vs_fp64(nprob, monkeypatch):
+def test_gemm_multi_x6k_vs_fp64(nprob):
     """scae_gemm_multi_f32 with 1, 3 and 4 weight-gradient problems of the capsule head's form
-    (both operands k-strided, groups of images): x6k at SCAE_GEMM_KSPLIT=1, the fp32 tiles at
-    0, each problem against its own reference."""
+    (both operands k-strided, groups of images): x6k at form = 0 (mode "1"), the fp32 tiles at
+    form = SCAE_GEMM_TILES (mode "0"), each problem against its own reference."""
     from torch_scae_amd import _lib, ops
     g = torch.Generator().manual_seed(40 + nprob)
     shapes = [(4, 96, 64, 800), (2, 64, 128, 288), (3, 32, 64, 224), (1, 128, 64, 128)][:nprob]
@@ -465,7 +464,6 @@ def test_gemm_multi_x6k_vs_fp64(nprob, monkeypatch):
         probs.append((G, n, k, rows, a, b))
     outs = {}
     for mode in ("1", "0"):
-        monkeypatch.setenv("SCAE_GEMM_KSPLIT", mode)
         descs = (_lib.GemmDesc * nprob)()
         keep = []
         for i, (G, n, k, rows, a, b) in enumerate(probs):
@@ -474,6 +472,7 @@ def test_gemm_multi_x6k_vs_fp64(nprob, monkeypatch):
             keep += [da, db_, c]
             descs[i] = ops._gemm_desc(ops._p(da), ops._p(db_), ops._p(c), G, n, k, rows, False,
                                       n, rows * n, False, k, rows * k, k, n * k)
+            descs[i].form = 0 if mode == "1" else _lib.GEMM_TILES
         _call("scae_gemm_multi_f32", descs, nprob, _st())
         torch.cuda.synchronize()
         outs[mode] = [keep[3 * i + 2] for i in range(nprob)]

@@ -394,12 +394,17 @@ def chunk_counts_ok(x_nhwc, w, dpre, stride):
     return ok
 
 
-def dgrad_mode(B, IH, IW, Ci, Co, stride, pair, dgx=500, dgk=1):
+NO_TILE, NO_KSPLIT, TILE = 1, 2, 4      # scae_hip.h's SCAE_DGRAD_* bits
+
+
+def dgrad_mode(B, IH, IW, Ci, Co, stride, pair, forms=0):
     """conv_mfma.hip's plan_dgrad restated (the tap-class tables of dgrad_axis and the
     tile-count thresholds SCAE_DGX_MIN_TILES = 500, SCAE_DGK_DEFAULT, SCAE_SMALL_TILES =
     SCAE_PAIR_SMALL_TILES = 1024, SCAE_PAIR_WIDE_MIN = 600): the data-gradient form a layer
-    takes.  dgx / dgk: the values of SCAE_K8_DGX / SCAE_K8_DGK."""
+    takes.  forms: the dgrad_forms argument (a set of the bits above, 0 = by shape)."""
     OH, OW = (IH - 3) // stride + 1, (IW - 3) // stride + 1
+    dgx = 0 if forms & NO_TILE else 1 if forms & TILE else 500
+    dgk = not forms & NO_KSPLIT
 
     def classes(I, O):
         def taps(i):

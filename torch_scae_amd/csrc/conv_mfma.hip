@@ -22,7 +22,6 @@
 //     without a workgroup, 32 x 32 split-K tiles give 4x as many).
 // Either way the accumulators leave through LDS as float4 rows (coalesced NHWC
 // stores).  The first layer (C_in <= 4: nine-tap dot products) is a direct kernel.
-#include <cstdlib>
 
 #include "mfma_tile.h"
 #include "mfma_pipe.h"
@@ -1581,7 +1580,13 @@ struct DgradLaunch {
 #ifndef SCAE_PAIR_WIDE_MIN
 #define SCAE_PAIR_WIDE_MIN 600
 #endif
-static DgradLaunch plan_dgrad(const ConvGeom &g, bool pair = false, bool bf16 = false) {
+// forms: the SCAE_DGRAD_* bits of scae_hip.h, 0 = by shape (the entry points check them)
+static bool dgrad_forms_ok(int forms) {
+  return !(forms & ~(SCAE_DGRAD_NO_TILE | SCAE_DGRAD_NO_KSPLIT | SCAE_DGRAD_TILE)) &&
+         !((forms & SCAE_DGRAD_TILE) && (forms & SCAE_DGRAD_NO_TILE));
+}
+static DgradLaunch plan_dgrad(const ConvGeom &g, bool pair = false, bool bf16 = false,
+                              int forms = SCAE_DGRAD_BY_SHAPE) {
   DgradLaunch d;
   DgradPlan &pl = d.pl;
   pl.nrc = dgrad_axis(g.IH, g.OH, g.stride, pl.rmask, pl.rcount, pl.rstart, pl.rlist);
@@ -1602,27 +1607,24 @@ static DgradLaunch plan_dgrad(const ConvGeom &g, bool pair = false, bool bf16 = 
     d.gx = g.Cin / 128;
     return d;
   }
-  // the DMA-fed exact-split tile (DMODE 4): SCAE_K8_DGX = minimal number of its 64 x 128 tiles
-  // for a layer to take it (0 = never)
+  // the DMA-fed exact-split tile (DMODE 4): for the layers with at least SCAE_DGX_MIN_TILES of its
+  // 64 x 128 tiles (0 = never), or as `forms` says
   if (g.Cin % dgx::TN == 0 && g.Cout % dgx::BKF == 0 &&
       (size_t)g.B * g.IH * g.IW * g.Cin * 4 < (1u << 31)) {
-    const char *xe = getenv("SCAE_K8_DGX");
-    const long min_tiles = xe && *xe ? atol(xe) : SCAE_DGX_MIN_TILES;
+    const long min_tiles = forms & SCAE_DGRAD_NO_TILE ? 0
+                           : forms & SCAE_DGRAD_TILE  ? 1
+                                                      : SCAE_DGX_MIN_TILES;
     const long tx = (long)(g.Cin / dgx::TN) * tiles(dgx::TM);
     if (min_tiles > 0 && tx >= min_tiles) {
       d.mode = 4, d.ny = tiles(dgx::TM), d.gx = g.Cin / dgx::TN;
       return d;
     }
   }
-  // ... and for the layers below that, the form with the K loop split over the waves (DMODE 5):
-  // SCAE_K8_DGK = 1 / 0
-  if (g.Cin % dgk::TN == 0 && g.Cout % dgk::BKF == 0 &&
-      (size_t)g.B * g.IH * g.IW * g.Cin * 4 < (1u << 31)) {
-    const char *ke = getenv("SCAE_K8_DGK");
-    if (ke && *ke ? atoi(ke) != 0 : SCAE_DGK_DEFAULT != 0) {
-      d.mode = 5, d.ny = tiles(dgk::TM), d.gx = g.Cin / dgk::TN;
-      return d;
-    }
+  // ... and for the layers below that, the form with the K loop split over the waves (DMODE 5)
+  if (SCAE_DGK_DEFAULT != 0 && !(forms & SCAE_DGRAD_NO_KSPLIT) && g.Cin % dgk::TN == 0 &&
+      g.Cout % dgk::BKF == 0 && (size_t)g.B * g.IH * g.IW * g.Cin * 4 < (1u << 31)) {
+    d.mode = 5, d.ny = tiles(dgk::TM), d.gx = g.Cin / dgk::TN;
+    return d;
   }
   // otherwise the first-generation tiles (DMODE 0 - 2; see conv_bwd_pair_mixed_kernel)
   const long t64 = (long)(g.Cin / 64) * tiles(64), t32 = (long)(g.Cin / 64) * tiles(32);
@@ -1659,15 +1661,15 @@ extern "C" int scae_conv3x3_dgrad_f32(const float *dpre, const float *wd, const 
 
 static int conv_bwd_pair_impl(const float *dpre, const float *wd, const float *in, float *din,
                               float *partial, int B, int IH, int IW, int Cin, int Cout,
-                              int stride, bool bf16, void *stream,
+                              int stride, bool bf16, int dgrad_forms, void *stream,
                               const PairRider *rider = nullptr) {
   ConvGeom g{B, IH, IW, (IH - 3) / stride + 1, (IW - 3) / stride + 1, Cin, Cout, stride};
   int rc = check_geom(g, true);
   if (rc) return rc;
-  SCAE_REQUIRE(dpre && wd && in && din && partial);
+  SCAE_REQUIRE(dpre && wd && in && din && partial && dgrad_forms_ok(dgrad_forms));
   if (IH > DG_MAXDIM || IW > DG_MAXDIM) return SCAE_ERR_UNSUPPORTED;
   bf16 = bf16 && conv_bf16_shape((long)B * IH * IW, Cin, Cout);
-  const DgradLaunch d = plan_dgrad(g, true, bf16);
+  const DgradLaunch d = plan_dgrad(g, true, bf16, dgrad_forms);
   const int splits = wgrad_splits(B * g.OH * g.OW, Cin, Cout);
   if (rider && bf16) return SCAE_ERR_UNSUPPORTED;   // only the mixed form below carries one
   hipStream_t st = (hipStream_t)stream;
@@ -1705,11 +1707,18 @@ static int conv_bwd_pair_impl(const float *dpre, const float *wd, const float *i
   return scae_launch_status();
 }
 
+extern "C" int scae_conv3x3_bwd_pair_forms_f32(const float *dpre, const float *wd,
+                                               const float *in, float *din, float *partial,
+                                               int B, int IH, int IW, int Cin, int Cout,
+                                               int stride, int dgrad_forms, void *stream) {
+  return conv_bwd_pair_impl(dpre, wd, in, din, partial, B, IH, IW, Cin, Cout, stride, false,
+                            dgrad_forms, stream);
+}
 extern "C" int scae_conv3x3_bwd_pair_f32(const float *dpre, const float *wd, const float *in,
                                          float *din, float *partial, int B, int IH, int IW,
                                          int Cin, int Cout, int stride, void *stream) {
-  return conv_bwd_pair_impl(dpre, wd, in, din, partial, B, IH, IW, Cin, Cout, stride, false,
-                            stream);
+  return scae_conv3x3_bwd_pair_forms_f32(dpre, wd, in, din, partial, B, IH, IW, Cin, Cout, stride,
+                                         SCAE_DGRAD_BY_SHAPE, stream);
 }
 // scae_conv3x3_bwd_pair_f32 carrying scae_seed_fold_bwd_f32(fold, fold_grads) in the same
 // launch (C = 256 folding width, the mixed tile form of the pair): else SCAE_ERR_UNSUPPORTED
@@ -1718,7 +1727,7 @@ extern "C" int scae_conv3x3_bwd_pair_fold_f32(const float *dpre, const float *wd
                                               int Cin, int Cout, int stride,
                                               const scae_seed_fold_desc *fold,
                                               const scae_seed_fold_grads *fold_grads,
-                                              void *stream) {
+                                              int dgrad_forms, void *stream) {
   int rc = scae_sf::check(fold);
   if (rc) return rc;
   rc = scae_sf::check_grads(fold_grads);
@@ -1733,7 +1742,7 @@ extern "C" int scae_conv3x3_bwd_pair_fold_f32(const float *dpre, const float *wd
   if (parts != 4 || lds > 24 * 1024) return SCAE_ERR_UNSUPPORTED;
   r.n = r.pl.ncol + fold->C;
   return conv_bwd_pair_impl(dpre, wd, in, din, partial, B, IH, IW, Cin, Cout, stride, false,
-                            stream, &r);
+                            dgrad_forms, stream, &r);
 }
 // ... carrying scae_seed_attention_mfma_reduce_f32(rpartial .. C) instead
 extern "C" int scae_conv3x3_bwd_pair_reduce_f32(const float *dpre, const float *wd,
@@ -1742,20 +1751,20 @@ extern "C" int scae_conv3x3_bwd_pair_reduce_f32(const float *dpre, const float *
                                                 int stride, const float *rpartial, int rows,
                                                 const float *q, const float *wk, float *gq,
                                                 float *gwk, float *gbk, float *gwv, float *gbv,
-                                                int O, int C, void *stream) {
+                                                int O, int C, int dgrad_forms, void *stream) {
   PairRider r{};
   r.kind = 1;
   int rc = scae_saw::reduce_args(r.red, rpartial, rows, q, wk, gq, gwk, gbk, gwv, gbv, O, C);
   if (rc) return rc;
   r.n = scae_saw::reduce_blocks(r.red, NT);
   return conv_bwd_pair_impl(dpre, wd, in, din, partial, B, IH, IW, Cin, Cout, stride, false,
-                            stream, &r);
+                            dgrad_forms, stream, &r);
 }
 extern "C" int scae_conv3x3_bwd_pair_bf16(const float *dpre, const float *wd, const float *in,
                                           float *din, float *partial, int B, int IH, int IW,
                                           int Cin, int Cout, int stride, void *stream) {
   return conv_bwd_pair_impl(dpre, wd, in, din, partial, B, IH, IW, Cin, Cout, stride, true,
-                            stream);
+                            SCAE_DGRAD_BY_SHAPE, stream);
 }
 
 #ifdef SCAE_FWD_PROF

@@ -24,8 +24,6 @@
 //     layer at B = 128, one per CU, equal work each.
 // The image's layout and the swizzle that keeps the row-per-lane fragment reads free of bank
 // conflicts are described at the kernel.
-#include <cstdlib>
-
 #include "bf16x6.h"
 #include "mfma_pipe.h"
 #include "conv_first_dev.h"

@@ -13,12 +13,10 @@
 // rows past K of k-strided operands are DMA zeros), 16-byte aligned rows,
 // no bias / ReLU.  Anything else: SCAE_ERR_UNSUPPORTED, and the caller (gemm_mfma.hip) takes the
 // register-staged tiles of mfma_tile.h.
-#include <cstdlib>
-
 #include "mfma_pipe.h"
 
 #ifndef SCAE_GEMM_KSPLIT_DEFAULT
-#define SCAE_GEMM_KSPLIT_DEFAULT 1   // SCAE_GEMM_KSPLIT = 1 / 0 at run time
+#define SCAE_GEMM_KSPLIT_DEFAULT 1   // 0: a build whose lists all take the tiles (A/B library)
 #endif
 
 namespace {
@@ -204,8 +202,7 @@ bool aligned16(const void *p) { return ((size_t)p & 15) == 0; }
 // (called by gemm_mfma.hip's problem-list launcher before it plans its own tiles)
 int scae_gemm_x6k_try(const scae_gemm_desc *descs, int n, void *stream) {
   if (!descs || n < 1 || n > 4) return SCAE_ERR_BAD_ARG;
-  const char *e = getenv("SCAE_GEMM_KSPLIT");
-  if (e && *e ? atoi(e) == 0 : SCAE_GEMM_KSPLIT_DEFAULT == 0) return SCAE_ERR_UNSUPPORTED;
+  if (SCAE_GEMM_KSPLIT_DEFAULT == 0) return SCAE_ERR_UNSUPPORTED;
   Probs ps{};
   ps.n = n;
   int first = 0;
@@ -213,6 +210,7 @@ int scae_gemm_x6k_try(const scae_gemm_desc *descs, int n, void *stream) {
     const scae_gemm_desc &d = descs[k];
     if (!d.A || !d.B || !d.C || d.batch <= 0 || d.M <= 0 || d.N <= 0 || d.K <= 0)
       return SCAE_ERR_BAD_ARG;
+    if (d.form) return d.form == SCAE_GEMM_TILES ? SCAE_ERR_UNSUPPORTED : SCAE_ERR_BAD_ARG;
     // the shapes this form exists for: few tiles, a long K
     if (d.b_kcontig || d.bias || d.relu || d.M % TM || d.N % TN || d.K < 4 * BKF ||
         (d.a_kcontig && d.K % BKF) || (d.asum && d.a_kcontig))

@@ -248,7 +248,8 @@ __global__ __launch_bounds__(NT) void gemm_multi_kernel(GemmMulti p) {
 constexpr long kSplitKBelow = SCAE_GEMM_SK_BELOW;
 
 int fill_args(GemmArgs &g, const scae_gemm_desc *d) {
-  if (!d || !d->A || !d->B || !d->C || d->batch <= 0 || d->M <= 0 || d->N <= 0 || d->K <= 0)
+  if (!d || !d->A || !d->B || !d->C || d->batch <= 0 || d->M <= 0 || d->N <= 0 || d->K <= 0 ||
+      (d->form != 0 && d->form != SCAE_GEMM_TILES))
     return SCAE_ERR_BAD_ARG;
   if (d->asum && d->a_kcontig) return SCAE_ERR_UNSUPPORTED;
   g = GemmArgs{d->A, d->B, d->bias, d->mask, d->C, d->asum, d->c_nomask, (long)d->a_batch, (long)d->b_batch,

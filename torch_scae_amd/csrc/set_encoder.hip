@@ -21,7 +21,6 @@
 // weight-gradient entry has one owning lane; per-workgroup partial sums are
 // reduced by the caller) and is bit-reproducible.
 #include <algorithm>
-#include <cstdlib>
 
 #include "common.h"
 #include "set_encoder_args.h"
@@ -34,6 +33,7 @@ using scae_st::MAXSEG;
 using scae_st::NMAX;
 using scae_st::Seg;
 using scae_st::StArgs;
+using scae_st::wave_supported;
 
 // packed GLOBAL parameter layout (floats), D = hidden width:
 //   W1 [D][Din], b1 [D]
@@ -746,14 +746,6 @@ int fill_args(StArgs &a, int nseg, const float *const *seg_ptr, const int *seg_w
   a.sqrt_d = sqrtf((float)D);
   return SCAE_OK;
 }
-
-
-// the wave-per-set MFMA kernels (set_encoder_wave.hip) where they apply; the
-// environment variable SCAE_ST_WAVE=0 keeps the workgroup-per-set kernels (A/B timing)
-bool use_wave(const StArgs &a, int D) {
-  const char *e = getenv("SCAE_ST_WAVE");
-  return !(e && *e == '0') && scae_st::wave_supported(a, D);
-}
 }  // namespace
 
 extern "C" int scae_set_encoder_param_count(int D, int Din, int Dout, int L, int layer_norm) {
@@ -786,7 +778,7 @@ extern "C" int scae_set_encoder_bf16_supported(int N, int D, int Din, int Dout, 
   if (N <= 0 || N > NMAX || Din <= 0 || Dout < 0 || L < 0) return 0;
   StArgs a{};
   a.N = N, a.Din = Din, a.Dout = Dout, a.L = L, a.layer_norm = layer_norm;
-  return use_wave(a, D) ? 1 : 0;
+  return wave_supported(a, D) ? 1 : 0;
 }
 
 namespace scae_fused {   // trunk_logprob.hip
@@ -813,8 +805,7 @@ static int encoder_fwd_logprob(bool bf16, int nseg, const float *const *seg_ptr,
   a.z = z;
   a.hsave = hsave;
   a.bf16_attention = bf16;
-  const char *e = getenv("SCAE_FUSE_TRUNK_LOGPROB");
-  if (!(e && *e == '0') && use_wave(a, D) && scae_fused::trunk_logprob_supported(a, D, d) &&
+  if (wave_supported(a, D) && scae_fused::trunk_logprob_supported(a, D, d) &&
       scae_render_gmm_logprob_tiles(d) > 0)
     return scae_fused::trunk_logprob_launch(a, scae_set_encoder_grid(B), d, x, tile_sums,
                                             lse_post, lse_prior, (hipStream_t)stream);
@@ -860,7 +851,7 @@ int encoder_fwd(bool bf16, int nseg, const float *const *seg_ptr, const int *seg
   a.hsave = hsave;
   a.bf16_attention = bf16;
   const int grid = scae_set_encoder_grid(B);
-  if (use_wave(a, D)) return scae_st::wave_launch(a, false, grid, (hipStream_t)stream);
+  if (wave_supported(a, D)) return scae_st::wave_launch(a, false, grid, (hipStream_t)stream);
   if (bf16) return SCAE_ERR_UNSUPPORTED;   // only the matrix-core kernels have the bf16 form
   switch (D) {
     case 8: return launch<8>(a, false, grid, (hipStream_t)stream);
@@ -884,7 +875,7 @@ int encoder_bwd(bool bf16, int nseg, const float *const *seg_ptr, const int *seg
   a.pg_partial = pg_partial;
   a.bf16_attention = bf16;
   const int grid = scae_set_encoder_grid(B);
-  if (use_wave(a, D)) return scae_st::wave_launch(a, true, grid, (hipStream_t)stream);
+  if (wave_supported(a, D)) return scae_st::wave_launch(a, true, grid, (hipStream_t)stream);
   if (bf16) return SCAE_ERR_UNSUPPORTED;
   switch (D) {
     case 8: return launch<8>(a, true, grid, (hipStream_t)stream);
@@ -911,7 +902,7 @@ int scae_st::wave_bwd_args(StArgs &a, bool bf16, int nseg, const float *const *s
   a.hsave = const_cast<float *>(hsave);
   a.pg_partial = pg_partial;
   a.bf16_attention = bf16;
-  return use_wave(a, D) ? SCAE_OK : SCAE_ERR_UNSUPPORTED;
+  return wave_supported(a, D) ? SCAE_OK : SCAE_ERR_UNSUPPORTED;
 }
 bool scae_st::wave_bwd_shape(int N, int D, int Din, int Dout, int L, int layer_norm) {
   return scae_set_encoder_bf16_supported(N, D, Din, Dout, L, layer_norm) != 0;

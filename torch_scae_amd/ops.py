@@ -148,7 +148,12 @@ def _prec(name):
 # where a training step's folding products of the output attention ride: "conv" = the second
 # convolution layer's forward launch, "prologue" = the step prologue's (measured per kernel
 # generation: DESIGN.md section 5)
-_FOLD_RIDES = __import__("os").environ.get("SCAE_FOLD_RIDES", "conv")
+_FOLD_RIDES = "conv"
+# Kernel forms that tests and measurements force; production leaves both as they are:
+# SCAE_DGRAD_* bits (scae_hip.h) for the data-gradient tiles of ``_conv_stack_bwd``'s pairs
+_K8_DGRAD_FORMS = 0
+# True: K4's backward never rides in K1's backward launch (scae_likelihood_bwd_desc.separate)
+_K1_K4_SEPARATE = False
 
 
 class StepPrologue:
@@ -177,7 +182,7 @@ class StepPrologue:
         # that launch has shown it can carry them (``_conv_stack_fwd``): the
         # prologue then leaves them out (they were its longest part)
         self.fold_rides_conv = False
-        # False: that launch cannot -- or (SCAE_FOLD_RIDES=prologue) shall not -- carry them
+        # False: that launch cannot -- or (_FOLD_RIDES == "prologue") shall not -- carry them
         self.fold_conv_ok = False if _FOLD_RIDES == "prologue" else None
 
     def _first_desc(self, image):
@@ -1295,8 +1300,8 @@ def _conv_stack_fwd(image, strides, weights, biases, post_bias=None):
     return acts, wds, x_post
 
 
-_CONV_BF16R = __import__("os").environ.get("SCAE_CONV_BF16R", "1") != "0"
-
+# False: the encoder's operands stay fp32 in HBM inside ``mfma_bf16()`` too (tests)
+_CONV_BF16R = True
 
 
 def _conv_bf16_resident(B, ih, iw, weights, strides):
@@ -1414,7 +1419,8 @@ def _conv_stack_bwd(image, acts, wds, strides, wshapes, dpre, gout,
             parked = plan.take("reduce")
             if parked is not None:
                 rc = lib.scae_conv3x3_bwd_pair_reduce_f32(
-                    *pair, *parked.args, st) if l == 2 else _lib.ERR_UNSUPPORTED
+                    *pair, *parked.args, _K8_DGRAD_FORMS,
+                    st) if l == 2 else _lib.ERR_UNSUPPORTED
                 if rc == _lib.ERR_UNSUPPORTED:
                     parked.launch_alone()
                 else:
@@ -1424,13 +1430,16 @@ def _conv_stack_bwd(image, acts, wds, strides, wshapes, dpre, gout,
             if parked is not None:
                 rc = lib.scae_conv3x3_bwd_pair_fold_f32(
                     *pair, ctypes.byref(parked.desc),
-                    ctypes.byref(parked.grads), st)
+                    ctypes.byref(parked.grads), _K8_DGRAD_FORMS, st)
                 if rc == _lib.ERR_UNSUPPORTED:
                     parked.launch_alone()
                 else:
                     _lib.check(rc, "scae_conv3x3_bwd_pair_fold_f32")
                     carried = True
-        if not carried:
+        if not carried and _K8_DGRAD_FORMS and not plan.bf16:
+            _lib.call("scae_conv3x3_bwd_pair_forms_f32", *pair, _K8_DGRAD_FORMS,
+                      st)
+        elif not carried:
             _lib.call(_prec("scae_conv3x3_bwd_pair_f32"), *pair, st)
         pending.append((partial, gw, gb, co, ci, splits))
         gws[l], gbs[l] = gw, gb
@@ -1502,7 +1511,7 @@ def attention_pool_supported(HW, A, P):
 
 
 # longest reduction (pixels) of one weight-gradient group of the 1x1 conv
-_CONV1X1_KMAX = int(__import__("os").environ.get("SCAE_CONV1X1_KMAX", "1024"))
+_CONV1X1_KMAX = 1024
 
 
 def _conv1x1_fwd(x, weight, bias):
@@ -2870,7 +2879,7 @@ class _CapsuleLikelihood(torch.autograd.Function):
                     (vote, scale, vp, dummy_vote, x, presence, post, widx,
                      *gin, gvote, gscale, gvp, gx, gpres, gdummy)):
                 setattr(k, name, None if t is None else t.data_ptr())
-            k.B, k.O, k.M = B, O, M
+            k.B, k.O, k.M, k.separate = B, O, M, int(_K1_K4_SEPARATE)
             _lib.call("scae_render_gmm_sums_bwd_likelihood_f32",
                       ctypes.byref(pending.desc), *pending.ptrs,
                       ctypes.byref(k), _stream(vote))

@@ -6,7 +6,6 @@ removing the per-launch host cost matters more than any single kernel.
 Mirrors the semantics of the reference's BaseExperiment.training_step
 (torch_scae_experiments/base_experiment.py:109-126)."""
 import contextlib
-import os
 import weakref
 
 import torch
@@ -69,10 +68,8 @@ class TrainStep:
       graphs with the collective between them.)
     * ``"1 bucket"``: one graph, one all-reduce of the whole flat buffer after
       it (``overlap=False``, or a model without the cut).
-    * ``"in graph"`` (``collective_mode="in graph"`` or env
-      ``SCAE_GRAPH_ALLREDUCE=1``): the all-reduce and the RMSprop step captured
-      inside the one graph -- no host-side stream hand-off at all, nothing
-      overlapped.
+    * ``"in graph"``: the all-reduce and the RMSprop step captured inside the
+      one graph -- no host-side stream hand-off at all, nothing overlapped.
     ``collective_mode``: one of the three names (``"2 buckets"`` falls back to
     ``"1 bucket"`` for a model without the backward cut), ``"off"`` (no
     collective even with ranks: measurements only -- the ranks' parameters
@@ -217,9 +214,6 @@ class TrainStep:
             raise ValueError("log_steps needs a model on a HIP device (the log's epilogue "
                              "is a device kernel)")
         self.world = world()[1]
-        if collective_mode is None and \
-                os.environ.get("SCAE_GRAPH_ALLREDUCE", "0") == "1":
-            collective_mode = "in graph"
         if collective_mode not in (None, "off") + self.MODES:
             raise ValueError(f"collective_mode must be one of {self.MODES}, "
                              f"'off' or None, got {collective_mode!r}")
