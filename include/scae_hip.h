@@ -42,7 +42,10 @@ extern "C" {
  * _side_size are gone; scae_decoder_desc loses bwd_resident
  * 4: the library reads no environment variable -- scae_gemm_desc has form,
  * scae_likelihood_bwd_desc has separate, scae_conv3x3_bwd_pair_forms_f32 is new and
- * scae_conv3x3_bwd_pair_{reduce,fold}_f32 take dgrad_forms */
+ * scae_conv3x3_bwd_pair_{reduce,fold}_f32 take dgrad_forms
+ * (4, added since, no signature changed: scae_conv3x3_bwd_pair_tile_f32,
+ * scae_conv3x3_wgrad_tile_f32 and scae_conv3x3_wgrad_tile_plan -- the weight gradient's tile
+ * form as an argument) */
 #define SCAE_ABI_VERSION 4
 
 #define SCAE_OK 0
@@ -692,6 +695,31 @@ int scae_conv3x3_wgrad_f32(const float *dpre, const float *in, float *partial, f
 int scae_conv3x3_wgrad_reduce_batch_f32(int n_layers, const float *const *partial,
                                         float *const *dw, float *const *db, const int *Cout,
                                         const int *Cin, const int *splits, void *stream);
+/* The weight gradient's tile form chosen by the caller (tests, measurements): output x input
+ * channels of one workgroup's tile, plus SCAE_WGRAD_HEAD for a pair launch whose
+ * weight-gradient workgroups lead the grid instead of following the data gradient's.  Every
+ * form runs on the splits of scae_conv3x3_wgrad_splits and writes the same partial slabs bit
+ * for bit; 128 x 64 with output channels that 128 does not divide falls back to 64 x 64.
+ * SCAE_WGRAD_TILE_BY_SHAPE is the production setting: what the entry points without this
+ * argument use, the pair launches with a rider among them, and what
+ * scae_conv3x3_wgrad_tile_plan returns for a layer's pair launch under dgrad_forms (a shape
+ * code, + SCAE_WGRAD_HEAD; or a negative SCAE_ERR_*).  Anything else: SCAE_ERR_BAD_ARG.
+ * These two are not launchers of a training step: the selector follows the stream, and the
+ * binding's launch recorder, which takes a launcher's last argument for its stream, leaves
+ * them alone. */
+#define SCAE_WGRAD_TILE_BY_SHAPE 0
+#define SCAE_WGRAD_TILE_64x64 1
+#define SCAE_WGRAD_TILE_128x64 2
+#define SCAE_WGRAD_HEAD 64
+int scae_conv3x3_bwd_pair_tile_f32(const float *dpre, const float *wd, const float *in,
+                                   float *din, float *partial, int B, int IH, int IW, int Cin,
+                                   int Cout, int stride, int dgrad_forms, void *stream,
+                                   int wgrad_tile);
+int scae_conv3x3_wgrad_tile_f32(const float *dpre, const float *in, float *partial, float *dw,
+                                float *db, int B, int IH, int IW, int Cin, int Cout, int stride,
+                                void *stream, int wgrad_tile);
+int scae_conv3x3_wgrad_tile_plan(int B, int IH, int IW, int Cin, int Cout, int stride,
+                                 int dgrad_forms);
 
 /* ------------------------------------------------------------------------
  * K9  attention pooling of the part-capsule head

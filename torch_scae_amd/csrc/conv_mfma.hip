@@ -344,6 +344,7 @@ __device__ __forceinline__ void wgrad_tile(float *smem, int bx, int by, int bz,
 // weight-gradient grid (wx, wy, 9 * splits).
 struct PairGrid {
   int nd, gx, wx, wy;
+  int nwh;   // mixed pairs: weight-gradient workgroups that run AHEAD of the nd (0 or all)
 };
 template <int DMODE, int WSK>
 __global__ __launch_bounds__(NT) void conv_bwd_pair_kernel(
@@ -504,7 +505,10 @@ __global__ __launch_bounds__(pipe::NT, 4) void conv_fwd_pipe_fold_kernel(
 }
 
 // ---- weight gradient: tile (bx, by) of tap / split bz ------------------------------------
-template <class T>
+// PERQ: the pixel quantum of a split's range (`per`) and of its loop length.  A ring of 16-pixel
+// chunks under PERQ = 32 walks the very 16-k batches, zero batches at a ragged end included, that
+// a ring of 32-pixel chunks walks: the partial slabs do not depend on T, only on PERQ.
+template <class T, int PERQ = T::BKW>
 __device__ __forceinline__ void wgrad_pipe_tile(float *smem, int bx, int by, int bz,
                                                 const float *__restrict__ dpre,
                                                 const float *__restrict__ in,
@@ -514,7 +518,8 @@ __device__ __forceinline__ void wgrad_pipe_tile(float *smem, int bx, int by, int
             li = lane & 31, lk = lane >> 5, wm = wid >> 1, wn = wid & 1;
   const int M = g.B * g.OH * g.OW;
   const int tap = bz % 9, split = bz / 9, kh = tap / 3, kw = tap - kh * 3;
-  const int per = ((M + splits - 1) / splits + T::BKW - 1) / T::BKW * T::BKW;
+  static_assert(PERQ % T::BKW == 0, "whole chunks per quantum");
+  const int per = ((M + splits - 1) / splits + PERQ - 1) / PERQ * PERQ;
   const int kbeg = split * per, kend = min(M, kbeg + per);
   const int co0 = by * T::TA, ci0 = bx * T::TB;
   const bool want_bias = tap == 0 && bx == 0;   // workgroup-uniform
@@ -562,7 +567,7 @@ __device__ __forceinline__ void wgrad_pipe_tile(float *smem, int bx, int by, int
       while (poh[jb] >= g.OH) poh[jb] -= g.OH, ++pn[jb];
     }
   };
-  const int nchunk = kbeg < kend ? (kend - kbeg + T::BKW - 1) / T::BKW : 0;
+  const int nchunk = kbeg < kend ? (kend - kbeg + PERQ - 1) / PERQ * (PERQ / T::BKW) : 0;
   pipe::f32x16 acc[T::MI][T::NI];
 #pragma unroll
   for (int a = 0; a < T::MI; ++a)
@@ -592,12 +597,12 @@ __device__ __forceinline__ void wgrad_pipe_tile(float *smem, int bx, int by, int
     partial[(size_t)splits * 9 * g.Cout * g.Cin + (size_t)split * g.Cout + co0 + tid] = bsum;
 }
 
-template <class T>
+template <class T, int PERQ>
 __global__ __launch_bounds__(pipe::NT) void conv_wgrad_pipe_kernel(
     const float *__restrict__ dpre, const float *__restrict__ in, float *__restrict__ partial,
     ConvGeom g, int splits) {
   __shared__ __attribute__((aligned(1024))) float smem[T::SMEM];
-  wgrad_pipe_tile<T>(smem, blockIdx.x, blockIdx.y, blockIdx.z, dpre, in, partial, g, splits);
+  wgrad_pipe_tile<T, PERQ>(smem, blockIdx.x, blockIdx.y, blockIdx.z, dpre, in, partial, g, splits);
 }
 
 // ---- data-gradient tile, third form (DMODE 4) ------------------------------------------------
@@ -1036,22 +1041,28 @@ __device__ unsigned long long g_conv_prof[6][4096][2];
 #define CV_STAMP(mode, i)
 #endif
 
+// workgroups per CU the register allocation must leave room for: left alone, the 128 x 64
+// tiles take 172 registers, four above what three waves per SIMD allow
+template <class TW>
+constexpr int pair_min_wgs() {
+  return TW::TA == 128 ? 3 : 1;
+}
 // first-generation data-gradient tiles (many small workgroups per CU suit the short K
 // loops of the tap classes) beside second-generation weight-gradient tiles
-template <int DMODE, class TW>
-__global__ __launch_bounds__(NT) void conv_bwd_pair_mixed_kernel(
+template <int DMODE, class TW, int PERQ>
+__global__ __launch_bounds__(NT, pair_min_wgs<TW>()) void conv_bwd_pair_mixed_kernel(
     const float *__restrict__ dpre, const float *__restrict__ wd, const float *__restrict__ gate,
     float *__restrict__ din, const float *__restrict__ in, float *__restrict__ partial,
     ConvGeom g, DgradPlan pl, int splits, PairGrid pg) {
   constexpr int SM = DgradShape<DMODE>::SMEM > TW::SMEM ? DgradShape<DMODE>::SMEM : TW::SMEM;
   __shared__ __attribute__((aligned(1024))) float smem[SM];
-  const int bid = blockIdx.x;
+  const int bid = (int)blockIdx.x - pg.nwh;
   CV_STAMP(DMODE, 0);
-  if (bid < pg.nd) {   // workgroup-uniform
+  if (bid >= 0 && bid < pg.nd) {   // workgroup-uniform
     dgrad_any_tile<DMODE, SM>(smem, bid % pg.gx, bid / pg.gx, dpre, wd, gate, din, g, pl);
   } else {
-    const int w = bid - pg.nd, bx = w % pg.wx, t = w / pg.wx;
-    wgrad_pipe_tile<TW>(smem, bx, t % pg.wy, t / pg.wy, dpre, in, partial, g, splits);
+    const int w = bid < 0 ? (int)blockIdx.x : bid - pg.nd, bx = w % pg.wx, t = w / pg.wx;
+    wgrad_pipe_tile<TW, PERQ>(smem, bx, t % pg.wy, t / pg.wy, dpre, in, partial, g, splits);
   }
   CV_STAMP(DMODE, 1);
 }
@@ -1074,8 +1085,8 @@ struct PairRider {
   scae_seed_fold_grads g;
   scae_sf::BwdPlan pl;
 };
-template <int DMODE, class TW>
-__global__ __launch_bounds__(NT) void conv_bwd_pair_mixed_rider_kernel(
+template <int DMODE, class TW, int PERQ>
+__global__ __launch_bounds__(NT, pair_min_wgs<TW>()) void conv_bwd_pair_mixed_rider_kernel(
     const float *__restrict__ dpre, const float *__restrict__ wd, const float *__restrict__ gate,
     float *__restrict__ din, const float *__restrict__ in, float *__restrict__ partial,
     ConvGeom g, DgradPlan pl, int splits, PairGrid pg, PairRider r) {
@@ -1091,12 +1102,12 @@ __global__ __launch_bounds__(NT) void conv_bwd_pair_mixed_rider_kernel(
     CV_STAMP(DMODE, 1);
     return;
   }
-  const int bid = (int)blockIdx.x - r.n;
-  if (bid < pg.nd) {
+  const int bid = (int)blockIdx.x - r.n - pg.nwh;
+  if (bid >= 0 && bid < pg.nd) {
     dgrad_any_tile<DMODE, SM>(smem, bid % pg.gx, bid / pg.gx, dpre, wd, gate, din, g, pl);
   } else {
-    const int w = bid - pg.nd, bx = w % pg.wx, t = w / pg.wx;
-    wgrad_pipe_tile<TW>(smem, bx, t % pg.wy, t / pg.wy, dpre, in, partial, g, splits);
+    const int w = bid < 0 ? bid + pg.nwh : bid - pg.nd, bx = w % pg.wx, t = w / pg.wx;
+    wgrad_pipe_tile<TW, PERQ>(smem, bx, t % pg.wy, t / pg.wy, dpre, in, partial, g, splits);
   }
   CV_STAMP(DMODE, 1);
 #ifdef SCAE_CONV_PROF
@@ -1342,6 +1353,47 @@ using PipeW16 = pipe::SS<64, 64, 16, SCAE_PIPE_NS>;
 #ifndef SCAE_WGRAD_SHORT_CHUNK_PIXELS
 #define SCAE_WGRAD_SHORT_CHUNK_PIXELS 8192   // layers with fewer output pixels take PipeW16
 #endif
+
+// The weight-gradient tile of a layer, on the splits and the pixel quantum (`perq`: 32, or 16
+// for the short layers above) of the 64 x 64 tile, so that every form writes the same partial
+// slabs bit for bit (wgrad_pipe_tile):
+//   64 x 64 (PipeW / PipeW16), or
+//   128 output x 64 input channels on 16-pixel chunks -- four stages under perq = 32 (the 48 KiB
+//   of PipeW), three under perq = 16 --, 172 -> 163 registers (pair_min_wgs): three workgroups a
+//   CU as before, 192 staged operand rows per 8192 outputs instead of 256;
+//   head: the weight-gradient workgroups, the longest jobs of the launch, lead the pair's grid.
+// By shape (cfg-2 at B = 128, the three pair launches in the step, profiles/r18): beside the
+// DMA-fed data-gradient tiles (modes 4 and 5) on the 32-pixel quantum the tiles lead, 128 x 64
+// where the output channels divide; every other layer keeps the 64 x 64 tiles behind the
+// data gradient's, which is all that was measured for it.
+struct WgradForm {
+  int ta, perq;   // (x 64 input channels)
+  bool head;
+};
+using PipeW128 = pipe::SS<128, 64, 16, 4>;
+using PipeW128s = pipe::SS<128, 64, 16, 3>;
+inline bool wgrad_tile_ok(int code) {
+  const int shape = code & ~SCAE_WGRAD_HEAD;
+  return code == SCAE_WGRAD_TILE_BY_SHAPE || shape == SCAE_WGRAD_TILE_64x64 ||
+         shape == SCAE_WGRAD_TILE_128x64;
+}
+inline int wgrad_tile_code(const WgradForm &f) {
+  return (f.ta == 128 ? SCAE_WGRAD_TILE_128x64 : SCAE_WGRAD_TILE_64x64) |
+         (f.head ? SCAE_WGRAD_HEAD : 0);
+}
+// dmode: the data-gradient form of the pair launch (plan_dgrad); code: SCAE_WGRAD_TILE_*
+WgradForm plan_wgrad(const ConvGeom &g, int dmode, int code) {
+  const long M = (long)g.B * g.OH * g.OW;
+  WgradForm f{64, dmode != 5 && M < SCAE_WGRAD_SHORT_CHUNK_PIXELS ? 16 : 32, false};
+  if (code == SCAE_WGRAD_TILE_BY_SHAPE) {
+    if ((dmode != 4 && dmode != 5) || f.perq != 32) return f;
+    code = SCAE_WGRAD_TILE_128x64 | SCAE_WGRAD_HEAD;
+  }
+  // (a tile the output channels do not divide: 64 x 64)
+  if ((code & ~SCAE_WGRAD_HEAD) == SCAE_WGRAD_TILE_128x64 && g.Cout % 128 == 0) f.ta = 128;
+  f.head = (code & SCAE_WGRAD_HEAD) != 0;
+  return f;
+}
 
 }  // namespace
 
@@ -1659,14 +1711,47 @@ extern "C" int scae_conv3x3_dgrad_f32(const float *dpre, const float *wd, const 
   return scae_launch_status();
 }
 
+// one mixed pair launch: the arguments every tile form takes
+struct PairCall {
+  const float *dpre, *wd, *in;
+  float *din, *partial;
+  ConvGeom g;
+  DgradPlan pl;
+  int splits;
+  PairGrid pg;
+  const PairRider *rider;
+  hipStream_t st;
+};
+template <int DM, class TW, int PERQ>
+static void launch_pair_mixed(const PairCall &c) {
+  const dim3 grid(c.pg.nd + c.pg.wx * c.pg.wy * 9 * c.splits);
+  if (c.rider)
+    scae::launch((conv_bwd_pair_mixed_rider_kernel<DM, TW, PERQ>), dim3(grid.x + c.rider->n),
+                 dim3(NT), 0, c.st, c.dpre, c.wd, c.in, c.din, c.in, c.partial, c.g, c.pl,
+                 c.splits, c.pg, *c.rider);
+  else
+    scae::launch((conv_bwd_pair_mixed_kernel<DM, TW, PERQ>), grid, dim3(NT), 0, c.st, c.dpre,
+                 c.wd, c.in, c.din, c.in, c.partial, c.g, c.pl, c.splits, c.pg);
+}
+template <int DM>
+static void launch_pair_tile(const PairCall &c, const WgradForm &f) {
+  if constexpr (DM != 5)
+    if (f.perq == 16)
+      return f.ta == 128 ? launch_pair_mixed<DM, PipeW128s, 16>(c)
+                         : launch_pair_mixed<DM, PipeW16, 16>(c);
+  f.ta == 128 ? launch_pair_mixed<DM, PipeW128, 32>(c) : launch_pair_mixed<DM, PipeW, 32>(c);
+}
+
 static int conv_bwd_pair_impl(const float *dpre, const float *wd, const float *in, float *din,
                               float *partial, int B, int IH, int IW, int Cin, int Cout,
                               int stride, bool bf16, int dgrad_forms, void *stream,
-                              const PairRider *rider = nullptr) {
+                              const PairRider *rider = nullptr,
+                              int wgrad_tile = SCAE_WGRAD_TILE_BY_SHAPE) {
   ConvGeom g{B, IH, IW, (IH - 3) / stride + 1, (IW - 3) / stride + 1, Cin, Cout, stride};
   int rc = check_geom(g, true);
   if (rc) return rc;
-  SCAE_REQUIRE(dpre && wd && in && din && partial && dgrad_forms_ok(dgrad_forms));
+  SCAE_REQUIRE(dpre && wd && in && din && partial && dgrad_forms_ok(dgrad_forms) &&
+               wgrad_tile_ok(wgrad_tile));
   if (IH > DG_MAXDIM || IW > DG_MAXDIM) return SCAE_ERR_UNSUPPORTED;
   bf16 = bf16 && conv_bf16_shape((long)B * IH * IW, Cin, Cout);
   const DgradLaunch d = plan_dgrad(g, true, bf16, dgrad_forms);
@@ -1679,34 +1764,43 @@ static int conv_bwd_pair_impl(const float *dpre, const float *wd, const float *i
                  0, st, dpre, wd, in, din, in, partial, g, d.pl, splits, bg);
     return scae_launch_status();
   }
-  // the data-gradient tiles of d.mode beside second-generation weight-gradient tiles (64 x 64),
-  // whose ring holds 16-pixel chunks for the layers with few output pixels (the K-split
-  // data-gradient tile brings 48 KiB of LDS to the launch anyway: the short ring would buy no
-  // workgroup)
-  const PairGrid pg{d.gx * d.ny, d.gx, Cin / 64, Cout / 64};
-  const dim3 grid(pg.nd + pg.wx * pg.wy * 9 * splits);
-  const bool w16 = d.mode != 5 && (long)B * g.OH * g.OW < SCAE_WGRAD_SHORT_CHUNK_PIXELS;
-#define SCAE_PAIR_MIXED(DM, TW)                                                                  \
-  if (rider)                                                                                    \
-    scae::launch((conv_bwd_pair_mixed_rider_kernel<DM, TW>), dim3(grid.x + rider->n), dim3(NT), \
-                 0, st, dpre, wd, in, din, in, partial, g, d.pl, splits, pg, *rider);           \
-  else                                                                                          \
-    scae::launch((conv_bwd_pair_mixed_kernel<DM, TW>), grid, dim3(NT), 0, st, dpre, wd, in,     \
-                 din, in, partial, g, d.pl, splits, pg)
-#define SCAE_PAIR_RING(DM) \
-  if (w16) { SCAE_PAIR_MIXED(DM, PipeW16); } else { SCAE_PAIR_MIXED(DM, PipeW); }
+  // the data-gradient tiles of d.mode beside second-generation weight-gradient tiles of the
+  // planned form (plan_wgrad).  Their ring holds 16-pixel chunks for the layers with few output
+  // pixels (the K-split data-gradient tile brings 48 KiB of LDS to the launch anyway: the short
+  // ring would buy no workgroup)
+  const WgradForm f = plan_wgrad(g, d.mode, wgrad_tile);
+  PairCall c{dpre, wd, in, din, partial, g, d.pl, splits,
+             PairGrid{d.gx * d.ny, d.gx, Cin / 64, Cout / f.ta, 0}, rider, st};
+  if (f.head) c.pg.nwh = c.pg.wx * c.pg.wy * 9 * splits;
   switch (d.mode) {
-    case 0: SCAE_PAIR_RING(0) break;
-    case 2: SCAE_PAIR_RING(2) break;
-    case 4: SCAE_PAIR_RING(4) break;
-    case 5: SCAE_PAIR_MIXED(5, PipeW); break;
-    default: SCAE_PAIR_RING(1)
+    case 0: launch_pair_tile<0>(c, f); break;
+    case 2: launch_pair_tile<2>(c, f); break;
+    case 4: launch_pair_tile<4>(c, f); break;
+    case 5: launch_pair_tile<5>(c, f); break;
+    default: launch_pair_tile<1>(c, f);
   }
-#undef SCAE_PAIR_RING
-#undef SCAE_PAIR_MIXED
   return scae_launch_status();
 }
 
+extern "C" int scae_conv3x3_bwd_pair_tile_f32(const float *dpre, const float *wd,
+                                              const float *in, float *din, float *partial,
+                                              int B, int IH, int IW, int Cin, int Cout,
+                                              int stride, int dgrad_forms, void *stream,
+                                              int wgrad_tile) {
+  return conv_bwd_pair_impl(dpre, wd, in, din, partial, B, IH, IW, Cin, Cout, stride, false,
+                            dgrad_forms, stream, nullptr, wgrad_tile);
+}
+extern "C" int scae_conv3x3_wgrad_tile_plan(int B, int IH, int IW, int Cin, int Cout, int stride,
+                                            int dgrad_forms) {
+  if (stride <= 0 || IH < 3 || IW < 3) return SCAE_ERR_BAD_ARG;
+  ConvGeom g{B, IH, IW, (IH - 3) / stride + 1, (IW - 3) / stride + 1, Cin, Cout, stride};
+  int rc = check_geom(g, true);
+  if (rc) return rc;
+  SCAE_REQUIRE(dgrad_forms_ok(dgrad_forms));
+  if (IH > DG_MAXDIM || IW > DG_MAXDIM) return SCAE_ERR_UNSUPPORTED;
+  const DgradLaunch d = plan_dgrad(g, true, false, dgrad_forms);
+  return wgrad_tile_code(plan_wgrad(g, d.mode, SCAE_WGRAD_TILE_BY_SHAPE));
+}
 extern "C" int scae_conv3x3_bwd_pair_forms_f32(const float *dpre, const float *wd,
                                                const float *in, float *din, float *partial,
                                                int B, int IH, int IW, int Cin, int Cout,
@@ -1779,22 +1873,38 @@ extern "C" int scae_conv3x3_wgrad_splits(int B, int OH, int OW, int Cin, int Cou
   return wgrad_splits(B * OH * OW, Cin, Cout);
 }
 
-extern "C" int scae_conv3x3_wgrad_f32(const float *dpre, const float *in, float *partial,
-                                      float *dw, float *db, int B, int IH, int IW, int Cin,
-                                      int Cout, int stride, void *stream) {
+extern "C" int scae_conv3x3_wgrad_tile_f32(const float *dpre, const float *in, float *partial,
+                                           float *dw, float *db, int B, int IH, int IW, int Cin,
+                                           int Cout, int stride, void *stream, int wgrad_tile) {
   ConvGeom g{B, IH, IW, (IH - 3) / stride + 1, (IW - 3) / stride + 1, Cin, Cout, stride};
   int rc = check_geom(g, true);
   if (rc) return rc;
-  SCAE_REQUIRE(dpre && in && partial);
+  SCAE_REQUIRE(dpre && in && partial && wgrad_tile_ok(wgrad_tile));
   const int splits = wgrad_splits(B * g.OH * g.OW, Cin, Cout);
-  scae::launch(conv_wgrad_pipe_kernel<PipeW>, dim3(Cin / 64, Cout / 64, 9 * splits), dim3(pipe::NT),
-               0, (hipStream_t)stream, dpre, in, partial, g, splits);
+  // the tile of the layer's pair launch, on 32-pixel chunks whatever the layer (the stand-alone
+  // launch has no data-gradient tiles to share a CU with)
+  const bool planned = IH <= DG_MAXDIM && IW <= DG_MAXDIM;
+  const WgradForm f =
+      plan_wgrad(g, planned ? plan_dgrad(g, true, false, SCAE_DGRAD_BY_SHAPE).mode : 0, wgrad_tile);
+  hipStream_t st = (hipStream_t)stream;
+  if (f.ta == 128)
+    scae::launch((conv_wgrad_pipe_kernel<PipeW128, 32>), dim3(Cin / 64, Cout / 128, 9 * splits),
+                 dim3(pipe::NT), 0, st, dpre, in, partial, g, splits);
+  else
+    scae::launch((conv_wgrad_pipe_kernel<PipeW, 32>), dim3(Cin / 64, Cout / 64, 9 * splits),
+                 dim3(pipe::NT), 0, st, dpre, in, partial, g, splits);
   if (dw) {  // else: the caller reduces later (scae_conv3x3_wgrad_reduce_batch_f32)
     const int n = 9 * Cout * Cin + Cout;
     scae::launch(reduce_wgrad_kernel, dim3((n + 255) / 256), dim3(256), 0,
                        (hipStream_t)stream, partial, dw, db, Cout, Cin, splits);
   }
   return scae_launch_status();
+}
+extern "C" int scae_conv3x3_wgrad_f32(const float *dpre, const float *in, float *partial,
+                                      float *dw, float *db, int B, int IH, int IW, int Cin,
+                                      int Cout, int stride, void *stream) {
+  return scae_conv3x3_wgrad_tile_f32(dpre, in, partial, dw, db, B, IH, IW, Cin, Cout, stride,
+                                     stream, SCAE_WGRAD_TILE_BY_SHAPE);
 }
 
 extern "C" int scae_conv3x3_wgrad_reduce_batch_f32(int n_layers, const float *const *partial,

@@ -327,6 +327,9 @@ __device__ __forceinline__ void ss_mainloop(int nchunk, float *smem, f32x16 (&ac
   // a batch = the lane's U k of each fragment: the 8 k of one bf16 MFMA
   constexpr int LA = T::NS - 1, S = T::BKW / 2, U = 8, NB = S / U;
   static_assert(NB >= 1 && S % U == 0 && T::PPW % NB == 0, "fragment batches per chunk");
+  // (chunk c + LA's pieces go out over chunk c's batches, the last of them behind the wait for
+  // chunk c + 1: with LA = 1 that wait would be for pieces not yet issued)
+  static_assert(LA >= 2, "at least three stages");
   const int aoff = kk * T::TA + wm * 32 * T::MI + i;
   const int boff = T::TA * T::BKW + kk * T::TB + wn * 32 * T::NI + i;
   float a[2][U][T::MI], b[2][U][T::NI];
