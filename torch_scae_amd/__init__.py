@@ -8,6 +8,7 @@ from . import (cv_ops, distributions, factory, general_utils, math_ops,  # noqa
                part_encoder, set_transformer, stacked_capsule_auto_encoder)
 from . import cluster  # noqa
 from . import cluster_quality  # noqa
+from . import mixture  # noqa
 from . import probe  # noqa
 from . import embed  # noqa
 from . import neighbors  # noqa
